@@ -12,6 +12,10 @@ band pick + Pillow-exact resize to 800x800 → Mask R-CNN R50-FPN forward (fp32 
 probabilities + pasted bit masks in HBM. Tiles shard across ranks (weak scaling: every rank runs K steps of its own
 batches); each step ends with the RCCL gather of the per-tile detections to rank 0 (the hand-off to stitching).
 
+`--steps K` is the number of timed steps of every region (unless --min-seconds asks for longer regions); `ms_per_step`
+is the headline region's time per step. `--dump-outputs DIR` writes the headline region's last step (the detections of its
+batch) as DIR/<name>.npy after the timed steps: the inputs are seeded, so two builds can be compared output for output.
+
 Prints ONE JSON line on rank 0 (contract in the task description) with `roofline` (dominant kernel family =
 conv_igemm, MFMA-bound, timed live with HIP events on the forward's stream) and `cpu_baseline` (the torch-CPU oracle
 on a bounded sample of the same stream, rank 0, N=1 only).
@@ -67,9 +71,13 @@ def parse():
     ap.add_argument("--distinct", type=int, default=16, help="distinct seeds generated (cycled over the stream)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-tiles", type=int, default=16)   # ≈ 13 s of CPU work on 16 threads
-    ap.add_argument("--min-seconds", type=float, default=1.0,
-                    help="every timed region lasts at least this long: the K-step block is repeated R times inside ONE timed region "
-                         "(barrier + synchronize on both sides of the R x K steps) and ms_per_step = seconds / (R x K); 0 = exactly K steps")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="0 (default): every timed region holds exactly --steps steps; > 0: it lasts at least this long, the K-step block "
+                         "repeated R times inside ONE timed region (barrier + synchronize on both sides of the R x K steps) and "
+                         "ms_per_step = seconds / (R x K)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the headline region's last step computed (detections, mask "
+                         "probabilities, a fixed sample of the pasted masks) as DIR/<name>.npy, float32 / float64")
     ap.add_argument("--detail", default=None, help="where the full (uncompacted) result goes; default bench_detail.json beside this script")
     ap.add_argument("--no-profile", action="store_true", help="do not bracket kernels with HIP events")
     ap.add_argument("--no-fp16", action="store_true", help="skip the second timed region with the fp16 engine")
@@ -278,6 +286,45 @@ def emit(full, detail_path=None):
     return s
 
 
+DUMP_LIMIT = 64 << 20       # bytes --dump-outputs may write in all
+MASK_SAMPLE = 8192          # pixel positions of every pasted mask --dump-outputs keeps (fixed, seeded)
+
+
+def dump_outputs(out, hw_out, dirname):
+    """--dump-outputs: one step's output buffers (Engine.alloc_outputs / forward_raw) as the caller unpacks them
+    (engine.unpack_outputs) → DIR/<name>.npy in float32 / float64. Only the valid rows are written: the detections of the
+    batch's tiles are concatenated in tile order and `count` splits them. The pasted masks (bool, one tile each) are written
+    as every mask's pixel count plus its values at MASK_SAMPLE fixed pixel positions (seeded; `mask_sample_index` holds
+    them as row-major indices). → {name: shape}."""
+    from treedetection_amd.engine import unpack_masks
+
+    cnt = out["count"].cpu().numpy()
+    n = [int(c) for c in cnt]
+    host = {k: v.cpu().numpy() for k, v in out.items()}
+    arrays = {"count": cnt.astype(np.float32)}
+    for k in ("boxes", "scores", "classes", "mask_probs"):
+        arrays[k] = np.concatenate([host[k][i, :n[i]] for i in range(len(n))]).astype(np.float32)
+    if "mask_bits" in out:
+        h, w = hw_out[0]
+        assert all(tuple(s) == (h, w) for s in hw_out), "the mask sample assumes tiles of one size"
+        idx = np.sort(np.random.default_rng(0).choice(h * w, size=min(MASK_SAMPLE, h * w), replace=False))
+        area, sample = [], []
+        for i in range(len(n)):
+            m = unpack_masks(host["mask_region"][i], host["mask_offset"][i], host["mask_bits"][i], n[i], h, w).reshape(n[i], h * w)
+            area.append(m.sum(axis=1, dtype=np.float64))
+            sample.append(m[:, idx].astype(np.float32))
+        arrays["mask_region"] = np.concatenate([host["mask_region"][i, :n[i]] for i in range(len(n))]).astype(np.float32)
+        arrays["mask_area"] = np.concatenate(area)
+        arrays["mask_sample"] = np.concatenate(sample)
+        arrays["mask_sample_index"] = idx.astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, f"--dump-outputs would write {total} bytes (limit {DUMP_LIMIT})"
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, f"{k}.npy"), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
+
+
 def main():
     args = parse()
     rank = int(os.environ.get("RANK", "0"))
@@ -327,9 +374,17 @@ def main():
 
     repeats = {}       # region name -> R (how many K-step blocks its timed region held)
 
+    def maybe_dump(name, o):
+        """--dump-outputs: the output buffers of the headline region's last timed step (rank 0), after its clock stopped."""
+        if args.dump_outputs and name == "headline" and rank == 0:
+            torch.cuda.synchronize()
+            shapes = dump_outputs(o, [(S, S)] * B, args.dump_outputs)
+            log(f"outputs of the last timed step written to {args.dump_outputs}: {shapes}")
+
     def measure(enqueue, n, engs, profile, name):
-        """The timed region: `enqueue(first, count)` enqueues steps [first, first + count). One K-step block is timed first
-        (it doubles as extra warm-up and tells how long K steps take); if that is shorter than --min-seconds the region proper
+        """The timed region: `enqueue(first, count)` enqueues steps [first, first + count), exactly K steps by default. With
+        --min-seconds > 0 one K-step block is timed first (it doubles as extra warm-up and tells how long K steps take); if
+        that is shorter than --min-seconds the region proper
         holds R blocks, R = ceil(min_seconds / block time) agreed over the ranks. Barrier + synchronize on both sides, one clock
         around all R x K steps. → (seconds per K steps = region seconds / R, host enqueue seconds per K steps, R)."""
         def region(first, count):
@@ -407,8 +462,10 @@ def main():
         gls = None
         if world > 1 and rank == 0:      # one set of receive buffers per engine: their gathers run on different streams
             gls = [{k: [torch.empty_like(out[k]) for _ in range(world)] for k in gather_keys} for _ in range(ns)]
+        last_step = [0]
 
         def step(i):
+            last_step[0] = i
             e, o = engs[i % ns], outs[i % ns]
             gl = gls[i % ns] if gls is not None else None
             with torch.cuda.stream(streams[i % ns]):
@@ -439,6 +496,7 @@ def main():
                 step(args.warmup + i)
         dt, t_enq, R = measure(enqueue, nsteps, engs, profile, name or precision)
         log(f"timed region done ({precision}): {dt * R:.3f} s for {R} x {nsteps} steps (host enqueue {t_enq * R:.3f} s)")
+        maybe_dump(name, outs[last_step[0] % ns])
         prof = collect_profile(engs, R) if profile else None
         ndet = int(out["count"].sum().item())     # detections of one batch (for the mask-head FLOP estimate)
         tmax = torch.tensor([dt], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
@@ -481,6 +539,7 @@ def main():
         # is short, the 0.4 ms count) and -2.5 % for fp32 (the VALU-heavy stem then competes with the fp32 MFMA convs
         # for the same CUs: conv time 18.1 -> 19.1 ms) — so only the fp16 schedule uses the pre-phase.
         prestage = precision == "fp16"
+        last_step = [0]     # the batch whose final phase was enqueued last
 
         def pre_stage(i):
             """Resize + stem + max-pool of batch i on its engine's side stream (VALU / HBM kernels: they run underneath
@@ -517,6 +576,7 @@ def main():
                     e.forward_phase(pm, main)
                 e.forward_phase(ps, side)
                 if ps == 5:
+                    last_step[0] = i
                     if world > 1:
                         with torch.cuda.stream(side):
                             for k in gather_keys:   # RCCL gather of the finished batch's detections to rank 0
@@ -543,6 +603,7 @@ def main():
                 e.profile_classes(reset=True)
         dt, t_enq, R = measure(lambda first, count: run_batches(nw + first, nw + first + count), nsteps, engs, profile, name or f"{precision}_phases")
         log(f"timed region done ({precision}, pipelined): {dt * R:.3f} s for {R} x {nsteps} steps (host enqueue {t_enq * R:.3f} s)")
+        maybe_dump(name, outs[last_step[0] % 3])
         prof = collect_profile(engs, R) if profile else None
         ndet = int(outs[0]["count"].sum().item())
         tmax = torch.tensor([dt], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
@@ -1021,7 +1082,8 @@ def main():
             "data": "synthetic",
             "config": {"workload": f"BASELINE configs[1]: single model ResNet{args.depth}-FPN Mask R-CNN, "
                                    f"{n_local}-tile synthetic {S}x{S} RGB(+nDSM side band) stream per GPU ({min(args.distinct, n_local)} distinct "
-                                   f"seeds cycled; re-walked R times for the >= 1 s region), batch={B} per GPU, "
+                                   f"seeds cycled{'; re-walked R times for the >= %g s region' % args.min_seconds if args.min_seconds > 0 else ''}), "
+                                   f"batch={B} per GPU, "
                                    f"resize 800x800 + forward + paste on device, inputs resident in HBM",
                        "stream_tiles": n_local, "distinct_tiles": min(args.distinct, n_local), "detections_per_tile": ndet / B,
                        "depth": args.depth, "batch_per_gpu": B, "tile": S, "net_input": "3x800x800",

@@ -305,13 +305,19 @@ def test_pth_checkpoint_round_trip(tmp_path):
         load_checkpoint(str(tmp_path / "bad.pth"))
 
 
-def test_reference_ndsm_raster_reads_as_surveyed():
+def test_reference_ndsm_raster_reads_as_surveyed(tmp_path):
     """The one raster the reference ships (data/nDSM/324125317.tif): 1000 x 1000 float32, 1 m, EPSG:25832, origin
-    (412000, 5318000) .. values 0 .. 50.9 m (SURVEY.md probe table). Skipped where /root/reference is absent."""
-    path = "/root/reference/data/nDSM/324125317.tif"
-    if not os.path.exists(path):
-        pytest.skip("reference data not present on this box")
-    from treedetection_amd.geotiff import GeoTiff
+    (412000, 5318000) .. values 0 .. 50.9 m (SURVEY.md probe table). Rebuilt from tests/golden/ndsm_324125317.npz
+    (tests/golden/make_ndsm_fixture.py): the file's header, IFD and strip table byte for byte, and its pixels as every 5th
+    row and column in centimetres, repeated 5 x 5 — a file of the original length that the verbatim strip table describes."""
+    fx = np.load(os.path.join(HERE, "golden", "ndsm_324125317.npz"))
+    k = int(fx["step"])
+    pixels = (np.repeat(np.repeat(fx["cm"], k, axis=0), k, axis=1).astype(np.float64) / 100).astype("<f4")
+    header = fx["header"].tobytes()
+    assert len(header) == 3542 and header[:4] == b"II*\x00" and pixels.shape == (1000, 1000)
+    path = str(tmp_path / "324125317.tif")
+    with open(path, "wb") as f:
+        f.write(header + pixels.tobytes())
     g = GeoTiff(path)
     try:
         assert (g.width, g.height, g.count) == (1000, 1000, 1) and g.dtype == np.float32 and g.epsg == 25832
@@ -319,6 +325,7 @@ def test_reference_ndsm_raster_reads_as_surveyed():
         assert (left, bottom, right, top) == (412000.0, 5317000.0, 413000.0, 5318000.0)      # origin = upper-left corner
         a = g.read_bounds([left, bottom, right, top])
         assert a.shape[-2:] == (1000, 1000)
+        assert np.array_equal(a.reshape(1000, 1000), pixels)                                  # every strip, in place
         assert a.min() == 0.0 and abs(float(a.max()) - 50.9) < 0.05 and abs(float(a.mean()) - 5.7) < 0.1
         # a 50 m tile with 20 m buffer at the raster's corner is clipped to the extent, as rasterio.mask(crop=True) does
         w = g.read_bounds([left - 20, top - 70, left + 70, top + 20])
