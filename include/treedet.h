@@ -187,7 +187,12 @@ td_status td_bottleneck_tail_nhwc(const void* x, const void* w2, const float* sc
  * (rs = res_shift: 1 = nearest-2x upsampled add, the FPN top-down path), y [B,Ho,Wo,Cout].
  * Cin must be a multiple of 32. precision selects float32 or float16 tensors (weights follow); bits 8..15 of
  * `precision` may carry (block-tile id + 1) to force one kernel variant (parity tests of every variant; 0 = the
- * library chooses); bit 16 with float16 tensors: y is float32 (how the engine runs the RPN / box-predictor heads). */
+ * library chooses); bit 16 with float16 tensors: y is float32 (how the engine runs the RPN / box-predictor heads).
+ * Bit 17 (0x20000, strict tile selection; tests only, the engine never sets it): a forced tile id (bits 8..15, or the
+ * TD_CONV_CFG diagnostic) that cannot run this launch — an fp16-only tile on float32 tensors, a plane-contraction tile
+ * (18-20) off a plain fp32 1x1 / stride-1 layer, the filter-stationary tile (33) where conv_bs_ok fails, a filter-direct
+ * tile where conv_bd_ok fails — returns TD_ERR_INVALID with a message naming the id and the condition, instead of running
+ * the heuristic tile in its place. */
 td_status td_conv2d_nhwc(const void* x, const void* w, const float* scale, const float* bias,
                          const void* residual, int res_shift, void* y, int B, int H, int W, int Cin,
                          int Cout, int KH, int KW, int stride, int pad, int relu, int precision,

@@ -5,6 +5,9 @@ import torch
 from treedetection_amd import _lib
 
 
+STRICT = 0x20000       # td_conv2d_nhwc precision bit: refuse a forced tile id the launch cannot run
+
+
 def dev(a, dtype=None):
     t = torch.as_tensor(np.ascontiguousarray(a))
     if dtype is not None:
@@ -13,8 +16,9 @@ def dev(a, dtype=None):
 
 
 def conv2d_hip(x_nchw, w_oihw, scale=None, bias=None, residual_nchw=None, res_shift=0, stride=1, pad=0, relu=False,
-               precision=0, tile_cfg=-1, out_f32=False):
-    """x [B,C,H,W] np → y [B,Co,Ho,Wo] np through td_conv2d_nhwc (``out_f32``: float16 tensors, float32 output)."""
+               precision=0, tile_cfg=-1, out_f32=False, strict=False):
+    """x [B,C,H,W] np → y [B,Co,Ho,Wo] np through td_conv2d_nhwc (``out_f32``: float16 tensors, float32 output;
+    ``strict``: a forced ``tile_cfg`` this launch cannot run raises instead of running the heuristic tile)."""
     lib = _lib.load()
     dt = torch.float32 if precision == 0 else torch.float16
     x = dev(np.transpose(x_nchw, (0, 2, 3, 1)), dt)
@@ -29,7 +33,8 @@ def conv2d_hip(x_nchw, w_oihw, scale=None, bias=None, residual_nchw=None, res_sh
     rs = dev(np.transpose(residual_nchw, (0, 2, 3, 1)), dt) if residual_nchw is not None else None
     p = lambda t: t.data_ptr() if t is not None else None
     st = lib.td_conv2d_nhwc(p(x), p(w), p(sc), p(bi), p(rs), res_shift, p(y), B, H, W, Cin, Cout, KH, KW, stride, pad,
-                            int(relu), precision | ((tile_cfg + 1) << 8) | (0x10000 if out_f32 else 0), _lib.stream_ptr())
+                            int(relu), precision | ((tile_cfg + 1) << 8) | (0x10000 if out_f32 else 0) | (STRICT if strict else 0),
+                            _lib.stream_ptr())
     _lib.check(st, "td_conv2d_nhwc")
     torch.cuda.synchronize()
     return y.float().cpu().numpy().transpose(0, 3, 1, 2)
@@ -48,7 +53,7 @@ def conv2d_head_hip(x_nchw, w_oihw, bias, head_w, head_b, pad, tile_cfg):
     hw, hb, bi = dev(head_w.reshape(n, 256), torch.float16), dev(head_b, torch.float32), dev(bias, torch.float32)
     y = torch.full((B, Ho, Wo, n), float("nan"), dtype=torch.float32, device="cuda")
     st = lib.td_conv2d_head_nhwc(x.data_ptr(), w.data_ptr(), bi.data_ptr(), hw.data_ptr(), hb.data_ptr(), y.data_ptr(), B, H, W, Cin,
-                                 KH, KW, pad, n, 1 | ((tile_cfg + 1) << 8), _lib.stream_ptr())
+                                 KH, KW, pad, n, 1 | ((tile_cfg + 1) << 8) | STRICT, _lib.stream_ptr())
     _lib.check(st, "td_conv2d_head_nhwc")
     torch.cuda.synchronize()
     return y.cpu().numpy().transpose(0, 3, 1, 2)

@@ -2,11 +2,15 @@
 
 fp32 tolerance: the MFMA accumulates an exact f32 fmaf chain in a different order than the CPU
 library, so |err| <= 2e-5 * sum|a*b| (stated here, checked per case)."""
+import os
+
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import conv_ref as cr
+from tests.conv_ref import Conv
 from tests.gpu_util import conv2d_hip
 
 pytestmark = pytest.mark.gpu
@@ -24,6 +28,30 @@ CASES = [
     (1, 64, 200, 200, 64, 3, 1, 1, True, True, 0, True),
     (2, 1024, 13, 13, 2048, 1, 1, 0, True, True, 1, True),
 ]
+
+
+def _conv_of(case):
+    B, Cin, H, W, Cout, k, stride, pad = case[:8]
+    res = case[10] if len(case) == 12 else case[8]
+    return B, Conv("case", Cin, Cout, k, stride, pad, H, W, res=res)
+
+
+def _forced_tile(case, fp16):
+    """The tile id TD_CONV_CFG forces (test_conv_every_block_tile_variant's child), -1 for none. A forced id this case cannot
+    run must be refused in strict mode (then None: nothing more to check) instead of quietly running the heuristic tile."""
+    forced = int(os.environ.get("TD_CONV_CFG", "-1"))
+    if forced < 0:
+        return -1
+    B, L = _conv_of(case)
+    if cr.tile_runs(forced, L, fp16, B):
+        return forced
+    x = np.zeros((B, L.Cin, L.H, L.W), np.float32)
+    w = np.zeros((L.Cout, L.Cin, L.k, L.k), np.float32)
+    r = None if not L.res else np.zeros((B, L.Cout, L.Ho >> (L.res - 1), L.Wo >> (L.res - 1)), np.float32)
+    with pytest.raises(Exception, match=f"tile_cfg {forced} cannot run"):
+        conv2d_hip(x, w, residual_nchw=r, res_shift=1 if L.res == 2 else 0, stride=L.stride, pad=L.pad, precision=int(fp16),
+                   tile_cfg=forced, strict=True)
+    return None
 
 
 @pytest.mark.parametrize("case", CASES)
@@ -49,7 +77,11 @@ def test_conv_matches_torch(case):
         ref = ref + F.interpolate(torch.from_numpy(r), scale_factor=2.0, mode="nearest")
     if relu:
         ref = F.relu(ref)
-    got = conv2d_hip(x, w, scale, bias, r, res_shift=1 if res == 2 else 0, stride=stride, pad=pad, relu=relu)
+    forced = _forced_tile(case, fp16=False)
+    if forced is None:
+        return
+    got = conv2d_hip(x, w, scale, bias, r, res_shift=1 if res == 2 else 0, stride=stride, pad=pad, relu=relu, tile_cfg=forced,
+                     strict=forced >= 0)
     ref = ref.numpy()
     assert got.shape == ref.shape
     err = np.abs(got - ref).max()
@@ -93,7 +125,11 @@ def test_conv_fp16_matches_torch(case):
         ref = ref + F.interpolate(torch.from_numpy(r), scale_factor=2.0, mode="nearest")
     if relu:
         ref = F.relu(ref)
-    got = conv2d_hip(x, w, scale, bias, r, res_shift=1 if res == 2 else 0, stride=stride, pad=pad, relu=relu, precision=1)
+    forced = _forced_tile(case, fp16=True)
+    if forced is None:
+        return
+    got = conv2d_hip(x, w, scale, bias, r, res_shift=1 if res == 2 else 0, stride=stride, pad=pad, relu=relu, precision=1,
+                     tile_cfg=forced, strict=forced >= 0)
     ref = ref.numpy()
     err = np.abs(got - ref)
     assert (err <= 2e-3 * np.maximum(np.abs(ref), 1.0)).all(), f"max err {err.max()}"
@@ -132,7 +168,7 @@ def test_conv_pp8_equals_the_reference_tile_bit_for_bit(case, cfg256):
     kw = dict(scale=scale, bias=bias, residual_nchw=r, res_shift=1 if res == 2 else 0, stride=stride, pad=pad, relu=relu, precision=1)
     ref = conv2d_hip(x, w, tile_cfg=0, **kw)
     for _ in range(3):                                  # a racy schedule would not repeat
-        got = conv2d_hip(x, w, tile_cfg=cfg256, **kw)
+        got = conv2d_hip(x, w, tile_cfg=cfg256, strict=True, **kw)
         assert got.shape == ref.shape and np.array_equal(got, ref)
     assert np.abs(ref).max() > 0.5
 
@@ -151,6 +187,9 @@ def test_conv_every_block_tile_variant(cfg):
                        text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert f"{len(CASES) + len(FP16_CASES)} passed" in r.stdout
+    # (the child runs the tile in strict mode where it can run and asserts refusal elsewhere: it must run somewhere)
+    assert any(cr.tile_runs(cfg, _conv_of(c)[1], False, _conv_of(c)[0]) for c in CASES) or \
+        any(cr.tile_runs(cfg, _conv_of(c)[1], True, _conv_of(c)[0]) for c in FP16_CASES)
 
 
 WINO_CASES = [
@@ -485,9 +524,14 @@ def test_conv_filter_direct_equals_the_reference_tile_bit_for_bit(case, cfg, pre
     elif res == 2:
         r = rng.standard_normal((B, Cout, Ho // 2, Wo // 2), dtype=np.float32)
     kw = dict(scale=scale, bias=bias, residual_nchw=r, res_shift=1 if res == 2 else 0, stride=stride, pad=pad, relu=relu, precision=prec)
+    if not cr.tile_runs(cfg, Conv("case", Cin, Cout, k, stride, pad, H, W, res=res), prec == 1, B):
+        # e.g. 33 on a 3x3, stride-2 or 3-k-chunk layer: refused by name, not silently replaced by the heuristic tile
+        with pytest.raises(Exception, match=f"tile_cfg {cfg} cannot run"):
+            conv2d_hip(x, w, tile_cfg=cfg, strict=True, **kw)
+        return
     ref = conv2d_hip(x, w, tile_cfg=0, **kw)
     for _ in range(2):
-        got = conv2d_hip(x, w, tile_cfg=cfg, **kw)
+        got = conv2d_hip(x, w, tile_cfg=cfg, strict=True, **kw)
         assert got.shape == ref.shape and np.array_equal(got, ref), float(np.abs(got - ref).max())
     assert np.abs(ref).max() > 0.5
 

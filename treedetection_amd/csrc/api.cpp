@@ -50,6 +50,7 @@ td_status td_conv2d_nhwc(const void* x, const void* w, const float* scale, const
     a.M = B * a.Ho * a.Wo; a.m_dyn = nullptr; a.m_mul = 1;
     a.out_f32 = (precision & 0x10000) && (precision & 0xff) == TD_PRECISION_FP16 ? 1 : 0;      // float16 tensors, float32 y (the heads)
     a.tile_cfg = ((precision >> 8) & 0xff) - 1;          // tests: force one block-tile variant (0 = the library chooses)
+    a.tile_strict = (precision & 0x20000) ? 1 : 0;       // tests: a forced variant that cannot run is an error
     return conv2d_api(a, precision, stream);
 }
 
@@ -77,7 +78,13 @@ td_status td_conv2d_head_nhwc(const void* x, const void* w, const float* bias, c
 static td_status conv2d_api(ConvArgs& a, int precision, void* stream) {
     const int Cin = a.Cin, Cout = a.Cout, KH = a.KH, KW = a.KW;
     const void* w = a.w;
-    if (conv_cfg_is_bd(a.tile_cfg) && Cin % ((precision & 0xff) == TD_PRECISION_FP16 ? 64 : 32) == 0) {
+    const int ke = (precision & 0xff) == TD_PRECISION_FP16 ? 64 : 32;
+    if (a.tile_strict && conv_cfg_is_bd(a.tile_cfg) && Cin % ke != 0) {
+        td_set_error("conv2d: tile_cfg %d cannot run this launch (strict tile selection): filter-direct tiles need Cin %% %d == 0 (Cin = %d)",
+                     a.tile_cfg, ke, Cin);
+        return TD_ERR_INVALID;
+    }
+    if (conv_cfg_is_bd(a.tile_cfg) && Cin % ke == 0) {
         // tests: the filter-direct tiles (conv_bdirect.hip) need the filters in fragment order: packed here from the caller's
         // [Cout][KH][KW][Cin] bank (the engine packs once at load time)
         hipStream_t s = static_cast<hipStream_t>(stream);

@@ -63,6 +63,7 @@ struct ConvArgs {
     int* sk_cnt;
     int tile_cfg;         // -1 = heuristic; 0..3 = block tile 128x128, 128x64, 64x128, 64x64 with 2 LDS stages,
                           // 4..7 = the same tiles with 3 stages (engine autotunes)
+    int tile_strict;      // 1: a forced tile_cfg this launch cannot run is an error, not a silent switch to the heuristic tile (tests)
     // fused 1x1 head (fp16 engine, block tiles that own all 256 output channels: conv_head_capable): the finished fp16
     // tile — this layer's output — is contracted with head_w [head_n <= 32][Cout = 256] straight from its LDS staging and
     // only head_y [M][head_n] (fp32, + head_b) is written; y is NOT written. The RPN's 3x3 conv + its 15-row head.

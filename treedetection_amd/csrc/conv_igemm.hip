@@ -1103,11 +1103,22 @@ td_status conv2d_launch(const ConvArgs& a, int precision, hipStream_t stream) {
         if (forced) cfg = atoi(forced);
     }
     const bool no_fp16_tile = precision != TD_PRECISION_FP16 || a.out_mode != 0 || a.batch_count > 1;
-    if (cfg == 17 && no_fp16_tile) cfg = -1;                       // fp16-only variant
-    if (cfg == 28 && (no_fp16_tile || a.m_dyn)) cfg = -1;          // fp16-only, static row counts only
-    if (cfg >= 18 && cfg <= 20 && !conv_plane_ok(a, precision)) cfg = -1;                                       // plane contractions only
-    if (cfg == 33 && !conv_bs_ok(a, precision)) cfg = -1;                                                       // thin 1x1 layers with packed filters only
-    if (conv_cfg_is_bd(cfg) && !conv_bd_ok(a, precision)) cfg = -1;                                             // needs the fragment-ordered filters
+    // a forced id this launch cannot run falls back to the heuristic tile — or, with tile_strict, is refused by name
+    const char* why = nullptr;
+    if (cfg == 17 && no_fp16_tile) why = "fp16-only tile (float16 tensors, plain output, no batched launch)";
+    else if (cfg == 28 && (no_fp16_tile || a.m_dyn)) why = "fp16-only tile with static row counts";
+    else if (cfg >= 18 && cfg <= 20 && !conv_plane_ok(a, precision))
+        why = "plane-only tile (conv_plane_ok: fp32 1x1, stride 1, no padding, no upsampled residual, Cin a multiple of 32)";
+    else if (cfg == 33 && !conv_bs_ok(a, precision))
+        why = "conv_bs_ok failed (1x1, stride 1, 1 / 2 / 4 k-chunks, 128 <= Cout <= 2048, Cout % 8 == 0, packed filters)";
+    else if (conv_cfg_is_bd(cfg) && !conv_bd_ok(a, precision)) why = "conv_bd_ok failed (packed filters, plain output)";
+    if (why) {
+        if (a.tile_strict) {
+            td_set_error("conv2d: tile_cfg %d cannot run this launch (strict tile selection): %s", cfg, why);
+            return TD_ERR_INVALID;
+        }
+        cfg = -1;
+    }
     // a fused head (ConvArgs::head_w) exists only in the tiles that stage all 256 output channels as one fp16 tile: any other
     // resolution of the tile id would silently write y and leave head_y untouched
     TD_REQUIRE(!a.head_w || (conv_head_capable(cfg, precision) && a.Cout == 256 && !a.res && a.out_mode == 0 && a.head_y && a.head_n >= 1 && a.head_n <= 32),
