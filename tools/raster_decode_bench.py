@@ -1,5 +1,8 @@
-"""Decode rate of LZW / DEFLATE rasters on the GPU (tiffdecode.hip): python tools/raster_decode_bench.py [codec=lzw|deflate] [side=9000] [tile=256|strip=N]
-[predictor=2] [data=tiles|noise|flat]
+"""Decode rate of LZW / DEFLATE / JPEG rasters on the GPU (tiffdecode.hip, jpegdecode.hip): python tools/raster_decode_bench.py
+[codec=lzw|deflate|jpeg] [side=9000] [tile=256|strip=N] [predictor=2] [data=tiles|noise|flat]
+JPEG (three bands, predictor ignored): [quality=90] [subsampling=2 (4:2:0) | 1 (4:2:2) | 0 (4:4:4)] [layout=complete|gdal] [restart=MCUs]
+[host_threads=16] — also times the host reader (Pillow's libjpeg per block, on that many threads) on the same raster and checks that
+both give the same bytes.
 Raster side x side x 4 uint8 (default 9000: the 400 windows of 450 x 450 px the reference cuts from one image, twice over); prints per
 call file → pinned → device → decoded raster in HBM, and the kernels alone (HIP events). Under rocprofv3 --kernel-trace --stats the
 per-kernel durations land in profiles/r06_decode_kernel_stats.csv."""
@@ -37,6 +40,10 @@ else:
             img[:3, r * 1000:(r + 1) * 1000, c * 1000:(c + 1) * 1000] = t.transpose(2, 0, 1)
             img[3, r * 1000:(r + 1) * 1000, c * 1000:(c + 1) * 1000] = t[..., 1]
     img = np.ascontiguousarray(img[:, :side, :side])
+if codec == "jpeg":
+    img, pred = np.ascontiguousarray(img[:3]), 1
+    kw.update(jpeg_quality=int(args.get("quality", 90)), jpeg_subsampling=int(args.get("subsampling", 2)),
+              jpeg_tables=args.get("layout", "complete") == "gdal", jpeg_restart=int(args.get("restart", 0)))
 try:
     t0 = time.perf_counter()
     write_geotiff(path, img, (0.2, 0, 412000.0, 0, -0.2, 5318000.0 + side * 0.2), 25832, compression=codec, predictor=pred, **kw)
@@ -55,12 +62,41 @@ try:
         times.append(time.perf_counter() - t0)
         ktimes.append(check.kernel_ms)
         slow = getattr(check, "slow_codes", 0)
-        if k == 0:
+        if k == 0 and codec == "jpeg":
+            dev0 = got.cpu().numpy()
+        elif k == 0:
             assert np.array_equal(got.cpu().numpy().transpose(2, 0, 1), img), "decoded raster differs from what was written"
         del image, got
+    extra = {}
+    if codec == "jpeg":
+        # the host reader on the same raster: every block through GeoTiff._decode_block (Pillow's libjpeg) on host_threads threads
+        nth = int(args.get("host_threads", 16))
+        keys = [(0, by, bx) for by in range(g._ny) for bx in range(g._nx)]
+        host_s = []
+        for k in range(2):
+            h = GeoTiff(path)
+            h._setup_blocks()
+            t0 = time.perf_counter()
+            with ThreadPoolExecutor(max_workers=nth) as hp:
+                blks = list(hp.map(lambda key: h._decode_block(*key), keys))
+            host_s.append(time.perf_counter() - t0)
+            if k == 0:
+                ref = np.empty_like(dev0)
+                for (_, by, bx), blk in zip(keys, blks):
+                    r0, c0 = by * h._bh, bx * h._bw
+                    piece = blk[:min(blk.shape[0], side - r0), :min(h._bw, side - c0)]
+                    ref[r0:r0 + piece.shape[0], c0:c0 + piece.shape[1]] = piece
+                assert np.array_equal(ref, dev0), "device decode differs from the host reader"
+            del blks
+            h.close()
+        info, segs, sets, ncoef = g._jpeg_plan()
+        extra = {"quality": kw["jpeg_quality"], "subsampling": kw["jpeg_subsampling"], "layout": args.get("layout", "complete"),
+                 "restart": kw["jpeg_restart"], "segments": len(segs), "table_sets": len(sets), "host_threads": nth,
+                 "host_reader_ms": [round(t * 1e3, 1) for t in host_s], "device_equals_host_reader": True}
+        kw = {k: v for k, v in kw.items() if not k.startswith("jpeg_")}
     raw = img.nbytes
     best = min(times[1:])
-    print(json.dumps({"codec": codec, "raster": f"{side}x{side}x4", "layout": kw, "predictor": pred, "data": data, "blocks": g._nx * g._ny, "raw_mb": raw / 1e6,
+    print(json.dumps({**extra, "codec": codec, "raster": f"{side}x{side}x{img.shape[0]}", "layout": kw, "predictor": pred, "data": data, "blocks": g._nx * g._ny, "raw_mb": raw / 1e6,
                       "file_mb": os.path.getsize(path) / 1e6, "ratio": raw / os.path.getsize(path), "encode_s": round(t_enc, 2),
                       "decode_ms": [round(t * 1e3, 1) for t in times], "kernel_ms": [round(t, 1) for t in ktimes],
                       "kernel_gb_per_s": raw / (min(ktimes) * 1e-3) / 1e9, "strings_through_memory": slow, "decode_gb_per_s": raw / best / 1e9,

@@ -34,6 +34,9 @@ int td_polygons_json_text(const int32_t* mask_region, const int64_t* mask_offset
 
 #define TD_KERNEL_CHECK() TD_HIP_CHECK(hipGetLastError())
 
+// tiffdecode.hip: a zeroed work counter for one raster-decode launch on `s` (taken by whole waves) and the device's CU count
+td_status td_decode_ticket(hipStream_t s, int** ticket, int* cus);
+
 static inline int td_cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // ---- convolution (conv_igemm.hip) -------------------------------------------------------------

@@ -1,0 +1,376 @@
+// JPEG-in-TIFF (compression 7) decoded on the GPU (jpegdecode.hip) and, from the same source, by one host thread (jpegcodec.cpp:
+// td_jpeg_decode), so that the CPU suite pins the decoder byte for byte against Pillow's libjpeg without a GPU. Written from ITU-T T.81
+// (sequential Huffman decoding, F.2.2) and the output arithmetic of the IJG decoder that the host reader runs through Pillow:
+//   - dequantisation + the accurate integer IDCT (13-bit constants, 2 extra bits between the passes, "islow") with the decoder's
+//     range-limit table: a result x of the second pass becomes table[x & 1023] — 0..255 for -384 <= x < 512 (clamped), and the
+//     table's wrap-around beyond that;
+//   - "fancy" upsampling of chroma (triangular filter, 3/4 - 1/4 weights, edge samples replicated at the component's real size
+//     ceil(W * h / hmax) x ceil(H * v / vmax); components at most 2 samples wide are replicated instead, as libjpeg does);
+//   - YCbCr → RGB in 16-bit fixed point.
+// What this core decodes: baseline / extended sequential Huffman, 8-bit samples, one component or three with Y sampled 1x1, 2x1 or
+// 2x2 and chroma 1x1, one interleaved scan, restart intervals. The host plan (jpegcodec.cpp) parses the headers, builds the Huffman
+// lookup tables and cuts a block's entropy-coded data into segments (one per restart interval); everything else is unsupported.
+#pragma once
+#include <cstdint>
+
+#ifdef __HIPCC__
+#define TD_JPG_HD __host__ __device__ inline
+#define TD_JPG_INLINE __attribute__((always_inline))
+#else
+#define TD_JPG_HD static inline
+#define TD_JPG_INLINE
+#endif
+
+constexpr int JPG_LOOK = 9;              // Huffman codes up to this length are decoded by one table lookup
+
+// One Huffman table, built on the host (jpegcodec.cpp: jpeg_build_huff).
+struct JpegHuff {
+    uint16_t look[1 << JPG_LOOK];        // next JPG_LOOK bits → (code length << 8) | symbol; 0 = a longer code (or none)
+    int32_t maxcode[18];                 // largest code of length l, -1 when there is none (T.81 F.2.2.3 MAXCODE)
+    int32_t valoff[18];                  // index in vals of the first code of length l, minus that code
+    uint8_t vals[256];                   // symbols in code order (HUFFVAL)
+};
+
+// The tables a block's components use, resolved per component (Y, Cb, Cr). Blocks that use the same tables share one set.
+struct JpegTables {
+    uint16_t q[3][64];                   // quantisation tables in natural (row-major) order
+    JpegHuff dc[3], ac[3];
+};
+
+// Sampling modes: 0 grey, 1 4:4:4, 2 4:2:2 (Y 2x1), 3 4:2:0 (Y 2x2); chroma is always 1x1.
+struct JpegGeom {
+    int ncomp, hmax, vmax, mcus_x, mcus_y;
+    int bw[3], bh[3];                    // 8x8 blocks across / down per component (the MCU grid's, padding included)
+    int cw[3], ch[3];                    // real size of each component in samples
+    int64_t off[3];                      // where the component's coefficients / samples start, in elements from the block's base
+    int64_t total;                       // elements of one block (coefficients, or samples of the component planes)
+};
+
+TD_JPG_HD JpegGeom jpeg_geom(int mode, int w, int h) {
+    JpegGeom g;
+    g.ncomp = mode == 0 ? 1 : 3;
+    g.hmax = mode >= 2 ? 2 : 1;
+    g.vmax = mode == 3 ? 2 : 1;
+    g.mcus_x = (w + 8 * g.hmax - 1) / (8 * g.hmax);
+    g.mcus_y = (h + 8 * g.vmax - 1) / (8 * g.vmax);
+    int64_t o = 0;
+    for (int c = 0; c < 3; ++c) {
+        const bool y = c == 0;
+        g.bw[c] = c < g.ncomp ? g.mcus_x * (y ? g.hmax : 1) : 0;
+        g.bh[c] = c < g.ncomp ? g.mcus_y * (y ? g.vmax : 1) : 0;
+        g.cw[c] = c < g.ncomp ? (y ? w : (w + g.hmax - 1) / g.hmax) : 0;
+        g.ch[c] = c < g.ncomp ? (y ? h : (h + g.vmax - 1) / g.vmax) : 0;
+        g.off[c] = o;
+        o += (int64_t)g.bw[c] * g.bh[c] * 64;
+    }
+    g.total = o;
+    return g;
+}
+
+TD_JPG_HD int jpeg_zigzag(int k) {       // position k of the zig-zag sequence → natural-order index (T.81 figure A.6)
+    constexpr uint8_t ZZ[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                                41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                                30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+    return ZZ[k];
+}
+
+// ---- entropy-coded segment → coefficients ----------------------------------------------------------------------------------------
+// Bit reader over [p, p + n): 0xFF00 is a stuffed 0xFF, any other 0xFF xx (or the end of the bytes) ends the data; zeros are fed
+// past it and counted, and a segment that CONSUMES any of them is corrupt (a marker or the end of data before its last MCU).
+struct JpegBits {
+    const uint8_t* p;
+    uint32_t pos, n;
+    uint64_t acc;                        // MSB-first
+    int have, pad;                       // bits in acc / how many of them are padding
+};
+
+TD_JPG_HD TD_JPG_INLINE void jpeg_fill(JpegBits& b) {
+    while (b.have <= 56) {
+        uint32_t v = 0;
+        if (b.pad == 0 && b.pos < b.n) {
+            v = b.p[b.pos];
+            if (v != 0xFF) {
+                ++b.pos;
+            } else if (b.pos + 1 < b.n && b.p[b.pos + 1] == 0) {
+                b.pos += 2;
+            } else {
+                v = 0;                   // a marker: the data ends here
+                b.pad = 8;
+            }
+        } else {
+            b.pad += 8;
+        }
+        b.acc |= (uint64_t)v << (56 - b.have);
+        b.have += 8;
+    }
+}
+
+TD_JPG_HD uint32_t jpeg_bits(JpegBits& b, int s) {         // s in 1..16
+    if (b.have < s) jpeg_fill(b);
+    const uint32_t v = (uint32_t)(b.acc >> (64 - s));
+    b.acc <<= s;
+    b.have -= s;
+    return v;
+}
+
+TD_JPG_HD int jpeg_extend(uint32_t v, int s) {             // T.81 F.2.2.1 EXTEND
+    return v < (1u << (s - 1)) ? (int)v - (1 << s) + 1 : (int)v;
+}
+
+TD_JPG_HD TD_JPG_INLINE int jpeg_huff(const JpegHuff& H, JpegBits& b) {
+    if (b.have < 16) jpeg_fill(b);
+    const uint32_t e = H.look[b.acc >> (64 - JPG_LOOK)];
+    if (e) {
+        const int l = (int)(e >> 8);
+        b.acc <<= l;
+        b.have -= l;
+        return (int)(e & 255);
+    }
+    for (int l = JPG_LOOK + 1; l <= 16; ++l) {
+        const int32_t code = (int32_t)(b.acc >> (64 - l));
+        if (code <= H.maxcode[l]) {
+            b.acc <<= l;
+            b.have -= l;
+            return H.vals[(H.valoff[l] + code) & 255];
+        }
+    }
+    return -1;                                             // not a code of the table
+}
+
+// One 8x8 block: DC difference + AC run / size pairs, coefficients written (natural order) into a zeroed blk. → 0 or 1 (corrupt).
+// A dequantised coefficient of 8-bit samples lies within 1024 + q / 2 of zero (the DCT of [-128, 127] is at most 1024, and rounding
+// to a multiple of q adds at most q / 2). Larger ones only come out of corrupt data (a flipped bit that still parses): libjpeg's vector
+// IDCT then wraps 16-bit intermediates that this IDCT keeps whole, so such a block is reported instead of decoded differently.
+TD_JPG_HD bool jpeg_coef_ok(int32_t v, uint16_t q) {
+    const int64_t qq = (int16_t)q, d = (int64_t)v * qq;
+    return (d < 0 ? -d : d) <= 1024 + 16 + ((qq < 0 ? -qq : qq) >> 1);
+}
+
+TD_JPG_HD TD_JPG_INLINE int jpeg_block(const JpegHuff& dc, const JpegHuff& ac, const uint16_t* q, JpegBits& b, int32_t& pred, int16_t* blk) {
+    // 8-bit samples: DC differences of at most 11 bits, AC values of at most 10 (T.81 tables F.1, F.2). Larger ones only come out of
+    // corrupt data, where libjpeg's vector IDCT wraps 16-bit products that this one keeps whole: reported instead of decoded differently
+    const int t = jpeg_huff(dc, b);
+    if (t < 0 || t > 11) return 1;
+    const int diff = t ? jpeg_extend(jpeg_bits(b, t), t) : 0;
+    pred = (int32_t)((uint32_t)pred + (uint32_t)diff);       // libjpeg's int predictor, stored as a 16-bit coefficient
+    if (!jpeg_coef_ok(pred, q[0])) return 1;
+    blk[0] = (int16_t)pred;
+    for (int k = 1; k < 64;) {
+        const int rs = jpeg_huff(ac, b);
+        if (rs < 0) return 1;
+        const int r = rs >> 4, s = rs & 15;
+        if (s) {
+            if (s > 10) return 1;
+            k += r;
+            if (k > 63) return 1;                          // a run past coefficient 63
+            const int z = jpeg_zigzag(k), v = jpeg_extend(jpeg_bits(b, s), s);
+            if (!jpeg_coef_ok(v, q[z])) return 1;
+            blk[z] = (int16_t)v;
+            ++k;
+        } else if (r == 15) {
+            k += 16;
+            if (k > 64) return 1;
+        } else {
+            break;                                         // end of block
+        }
+    }
+    return 0;
+}
+
+// MCUs [mcu0, mcu0 + nmcu) of one block from its segment [src, src + nbytes) (one restart interval, or the whole scan) into the
+// block's zeroed coefficient area coef (layout: JpegGeom::off / bw). → 0 ok, 1 corrupt.
+TD_JPG_HD TD_JPG_INLINE int jpeg_decode_segment(const JpegTables& T, const JpegGeom& g, const uint8_t* src, uint32_t nbytes, uint32_t mcu0,
+                                                uint32_t nmcu, int16_t* coef) {
+    JpegBits b;
+    b.p = src;
+    b.pos = 0;
+    b.n = nbytes;
+    b.acc = 0;
+    b.have = 0;
+    b.pad = 0;
+    int32_t pred[3] = {0, 0, 0};
+    for (uint32_t m = mcu0; m < mcu0 + nmcu; ++m) {
+        const int mx = (int)(m % (uint32_t)g.mcus_x), my = (int)(m / (uint32_t)g.mcus_x);
+        if (g.ncomp == 1) {
+            if (jpeg_block(T.dc[0], T.ac[0], T.q[0], b, pred[0], coef + ((int64_t)my * g.bw[0] + mx) * 64)) return 1;
+        } else {
+            for (int v = 0; v < g.vmax; ++v)
+                for (int h = 0; h < g.hmax; ++h)
+                    if (jpeg_block(T.dc[0], T.ac[0], T.q[0], b, pred[0], coef + ((int64_t)(my * g.vmax + v) * g.bw[0] + mx * g.hmax + h) * 64)) return 1;
+            for (int c = 1; c < 3; ++c)
+                if (jpeg_block(T.dc[c], T.ac[c], T.q[c], b, pred[c], coef + g.off[c] + ((int64_t)my * g.bw[c] + mx) * 64)) return 1;
+        }
+        if (b.have < b.pad) return 1;                      // consumed bits past the end of the data
+    }
+    // and the data ends here: at most 7 bits are left before the marker (or the end), all ones (the encoder's padding). A stream
+    // that decodes its MCUs with bytes to spare was misread (a flipped bit) — libjpeg warns about "extraneous bytes" and goes on
+    jpeg_fill(b);
+    const int left = b.have - b.pad;
+    if (b.pad == 0 || left >= 8) return 1;
+    return left > 0 && (uint32_t)(b.acc >> (64 - left)) != (1u << left) - 1u;
+}
+
+// ---- dequantisation + accurate integer IDCT of one 8x8 block ---------------------------------------------------------------------
+TD_JPG_HD uint8_t jpeg_range_limit(int64_t x) {            // the decoder's post-IDCT table, indexed by x & 1023
+    const int i = (int)(x & 1023);
+    return (uint8_t)(i < 128 ? i + 128 : i < 512 ? 255 : i < 896 ? 0 : i - 896);
+}
+
+TD_JPG_HD TD_JPG_INLINE void jpeg_idct_islow(const int16_t* in, const uint16_t* q, uint8_t* out, int64_t stride) {
+    constexpr int CB = 13, P1 = 2;
+    constexpr int64_t F0298 = 2446, F0390 = 3196, F0541 = 4433, F0765 = 6270, F0899 = 7373, F1175 = 9633, F1501 = 12299, F1847 = 15137,
+                      F1961 = 16069, F2053 = 16819, F2562 = 20995, F3072 = 25172;
+    int32_t ws[64];
+    // the decoder holds quantisation values as 16-bit signed multipliers (a 16-bit DQT entry above 32767 turns negative)
+    for (int c = 0; c < 8; ++c) {
+        const int64_t d0 = (int64_t)in[c] * (int16_t)q[c], d1 = (int64_t)in[8 + c] * (int16_t)q[8 + c], d2 = (int64_t)in[16 + c] * (int16_t)q[16 + c],
+                      d3 = (int64_t)in[24 + c] * (int16_t)q[24 + c], d4 = (int64_t)in[32 + c] * (int16_t)q[32 + c],
+                      d5 = (int64_t)in[40 + c] * (int16_t)q[40 + c], d6 = (int64_t)in[48 + c] * (int16_t)q[48 + c],
+                      d7 = (int64_t)in[56 + c] * (int16_t)q[56 + c];
+        if ((in[8 + c] | in[16 + c] | in[24 + c] | in[32 + c] | in[40 + c] | in[48 + c] | in[56 + c]) == 0) {
+            const int32_t dc = (int32_t)(d0 * (1 << P1));
+            for (int r = 0; r < 8; ++r) ws[r * 8 + c] = dc;
+            continue;
+        }
+        int64_t z1 = (d2 + d6) * F0541;
+        int64_t tmp2 = z1 - d6 * F1847, tmp3 = z1 + d2 * F0765;
+        int64_t tmp0 = (d0 + d4) * (1 << CB), tmp1 = (d0 - d4) * (1 << CB);
+        const int64_t t10 = tmp0 + tmp3, t13 = tmp0 - tmp3, t11 = tmp1 + tmp2, t12 = tmp1 - tmp2;
+        tmp0 = d7;
+        tmp1 = d5;
+        tmp2 = d3;
+        tmp3 = d1;
+        z1 = tmp0 + tmp3;
+        int64_t z2 = tmp1 + tmp2, z3 = tmp0 + tmp2, z4 = tmp1 + tmp3;
+        const int64_t z5 = (z3 + z4) * F1175;
+        tmp0 *= F0298;
+        tmp1 *= F2053;
+        tmp2 *= F3072;
+        tmp3 *= F1501;
+        z1 *= -F0899;
+        z2 *= -F2562;
+        z3 *= -F1961;
+        z4 *= -F0390;
+        z3 += z5;
+        z4 += z5;
+        tmp0 += z1 + z3;
+        tmp1 += z2 + z4;
+        tmp2 += z2 + z3;
+        tmp3 += z1 + z4;
+        constexpr int SH = CB - P1;
+        constexpr int64_t RND = (int64_t)1 << (SH - 1);
+        ws[0 * 8 + c] = (int32_t)((t10 + tmp3 + RND) >> SH);
+        ws[7 * 8 + c] = (int32_t)((t10 - tmp3 + RND) >> SH);
+        ws[1 * 8 + c] = (int32_t)((t11 + tmp2 + RND) >> SH);
+        ws[6 * 8 + c] = (int32_t)((t11 - tmp2 + RND) >> SH);
+        ws[2 * 8 + c] = (int32_t)((t12 + tmp1 + RND) >> SH);
+        ws[5 * 8 + c] = (int32_t)((t12 - tmp1 + RND) >> SH);
+        ws[3 * 8 + c] = (int32_t)((t13 + tmp0 + RND) >> SH);
+        ws[4 * 8 + c] = (int32_t)((t13 - tmp0 + RND) >> SH);
+    }
+    for (int r = 0; r < 8; ++r) {
+        const int32_t* w = ws + r * 8;
+        uint8_t* o = out + r * stride;
+        if ((w[1] | w[2] | w[3] | w[4] | w[5] | w[6] | w[7]) == 0) {
+            const uint8_t v = jpeg_range_limit(((int64_t)w[0] + (1 << (P1 + 2))) >> (P1 + 3));
+            for (int k = 0; k < 8; ++k) o[k] = v;
+            continue;
+        }
+        int64_t z2 = w[2], z3 = w[6];
+        int64_t z1 = (z2 + z3) * F0541;
+        int64_t tmp2 = z1 - z3 * F1847, tmp3 = z1 + z2 * F0765;
+        int64_t tmp0 = ((int64_t)w[0] + w[4]) * (1 << CB), tmp1 = ((int64_t)w[0] - w[4]) * (1 << CB);
+        const int64_t t10 = tmp0 + tmp3, t13 = tmp0 - tmp3, t11 = tmp1 + tmp2, t12 = tmp1 - tmp2;
+        tmp0 = w[7];
+        tmp1 = w[5];
+        tmp2 = w[3];
+        tmp3 = w[1];
+        z1 = tmp0 + tmp3;
+        z2 = tmp1 + tmp2;
+        z3 = tmp0 + tmp2;
+        int64_t z4 = tmp1 + tmp3;
+        const int64_t z5 = (z3 + z4) * F1175;
+        tmp0 *= F0298;
+        tmp1 *= F2053;
+        tmp2 *= F3072;
+        tmp3 *= F1501;
+        z1 *= -F0899;
+        z2 *= -F2562;
+        z3 *= -F1961;
+        z4 *= -F0390;
+        z3 += z5;
+        z4 += z5;
+        tmp0 += z1 + z3;
+        tmp1 += z2 + z4;
+        tmp2 += z2 + z3;
+        tmp3 += z1 + z4;
+        constexpr int SH = CB + P1 + 3;
+        constexpr int64_t RND = (int64_t)1 << (SH - 1);
+        o[0] = jpeg_range_limit((t10 + tmp3 + RND) >> SH);
+        o[7] = jpeg_range_limit((t10 - tmp3 + RND) >> SH);
+        o[1] = jpeg_range_limit((t11 + tmp2 + RND) >> SH);
+        o[6] = jpeg_range_limit((t11 - tmp2 + RND) >> SH);
+        o[2] = jpeg_range_limit((t12 + tmp1 + RND) >> SH);
+        o[5] = jpeg_range_limit((t12 - tmp1 + RND) >> SH);
+        o[3] = jpeg_range_limit((t13 + tmp0 + RND) >> SH);
+        o[4] = jpeg_range_limit((t13 - tmp0 + RND) >> SH);
+    }
+}
+
+// ---- one output pixel: fancy upsampling + colour conversion ----------------------------------------------------------------------
+// planes: the block's component planes (layout JpegGeom::off, row stride bw * 8); (x, y) inside the SOF size. ycc: YCbCr → RGB.
+TD_JPG_HD int jpeg_plane_at(const uint8_t* planes, const JpegGeom& g, int c, int x, int y) {
+    return planes[g.off[c] + (int64_t)y * (g.bw[c] * 8) + x];
+}
+
+TD_JPG_HD int jpeg_chroma(const uint8_t* planes, const JpegGeom& g, int c, int x, int y) {
+    const int cw = g.cw[c], ch = g.ch[c];
+    if (g.hmax == 1) return jpeg_plane_at(planes, g, c, x, y);          // 4:4:4
+    const int cx = x >> 1;
+    if (cw <= 2) return jpeg_plane_at(planes, g, c, cx, y >> (g.vmax - 1));      // libjpeg replicates components this narrow
+    if (g.vmax == 1) {                                                   // h2v1: (3 * this + neighbour + 1 or 2) >> 2
+        const int t = jpeg_plane_at(planes, g, c, cx, y);
+        if (!(x & 1)) return cx == 0 ? t : (t * 3 + jpeg_plane_at(planes, g, c, cx - 1, y) + 1) >> 2;
+        return cx == cw - 1 ? t : (t * 3 + jpeg_plane_at(planes, g, c, cx + 1, y) + 2) >> 2;
+    }
+    // h2v2: column sums 3 * near row + far row (rows outside [0, ch) replicate the edge), then 3 * this + neighbour across
+    const int cy = y >> 1;
+    int fy = (y & 1) ? cy + 1 : cy - 1;
+    fy = fy < 0 ? 0 : (fy > ch - 1 ? ch - 1 : fy);
+    const int t = jpeg_plane_at(planes, g, c, cx, cy) * 3 + jpeg_plane_at(planes, g, c, cx, fy);
+    if (!(x & 1)) {
+        if (cx == 0) return (t * 4 + 8) >> 4;
+        const int o = jpeg_plane_at(planes, g, c, cx - 1, cy) * 3 + jpeg_plane_at(planes, g, c, cx - 1, fy);
+        return (t * 3 + o + 8) >> 4;
+    }
+    if (cx == cw - 1) return (t * 4 + 7) >> 4;
+    const int o = jpeg_plane_at(planes, g, c, cx + 1, cy) * 3 + jpeg_plane_at(planes, g, c, cx + 1, fy);
+    return (t * 3 + o + 7) >> 4;
+}
+
+TD_JPG_HD uint8_t jpeg_clamp255(int v) { return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
+
+// → the pixel's samples in px[0 .. ncomp)
+TD_JPG_HD TD_JPG_INLINE void jpeg_pixel(const uint8_t* planes, const JpegGeom& g, int ycc, int x, int y, uint8_t* px) {
+    const int Y = jpeg_plane_at(planes, g, 0, x, y);
+    if (g.ncomp == 1) {
+        px[0] = (uint8_t)Y;
+        return;
+    }
+    const int cb = jpeg_chroma(planes, g, 1, x, y), cr = jpeg_chroma(planes, g, 2, x, y);
+    if (!ycc) {
+        px[0] = (uint8_t)Y;
+        px[1] = (uint8_t)cb;
+        px[2] = (uint8_t)cr;
+        return;
+    }
+    // 16-bit fixed point, ONE_HALF rounding (the IJG colour converter's tables, computed in place)
+    constexpr int64_t FR = 91881, FB = 116130, FGR = 46802, FGB = 22554, HALF = 1 << 15;
+    const int64_t dcr = cr - 128, dcb = cb - 128;
+    const int r = Y + (int)((FR * dcr + HALF) >> 16);
+    const int gg = Y + (int)((-FGB * dcb + HALF - FGR * dcr) >> 16);
+    const int bb = Y + (int)((FB * dcb + HALF) >> 16);
+    px[0] = jpeg_clamp255(r);
+    px[1] = jpeg_clamp255(gg);
+    px[2] = jpeg_clamp255(bb);
+}

@@ -486,6 +486,9 @@ int inflate_ring_choice(int nblocks) {
 
 }  // namespace
 
+// the same per-launch counters for the JPEG decoder's waves (jpegdecode.hip)
+td_status td_decode_ticket(hipStream_t s, int** ticket, int* cus) { return next_ticket(s, ticket, cus); }
+
 extern "C" td_status td_tiff_lzw_decode_dev(const uint8_t* comp, const int64_t* block_off, const int64_t* block_nbytes, int nblocks,
                                             uint8_t* blocks_out, int64_t block_cap, int64_t* decoded, int32_t* status, void* stream) {
     TD_REQUIRE(comp && block_off && block_nbytes && blocks_out && decoded && status, "td_tiff_lzw_decode_dev: null pointer");

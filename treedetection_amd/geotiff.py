@@ -7,6 +7,8 @@ DEFLATE (zlib) / LZW / PackBits (td_tiff_*_decode in libtreedet_hip.so), horizon
 three geo tags (ModelPixelScale / ModelTiepoint / GeoKeyDirectory). JPEG-in-TIFF (compression 7, 8-bit, one or three bands)
 is windowed too: a block's abbreviated stream + the JPEGTables tag form one JPEG stream, decoded by Pillow's libjpeg block by
 block (GDAL does the same through libtiff). Other codecs (old-style JPEG, floating-point predictor, ...): whole image through Pillow.
+Whole rasters can instead be decoded on the GPU and kept in HBM (``decode_to_device``): LZW and DEFLATE (tiffdecode.hip) and
+sequential-Huffman JPEG (jpegdecode.hip, byte-identical to the Pillow path) — see ``device_decodable``.
 """
 from __future__ import annotations
 
@@ -354,16 +356,59 @@ class GeoTiff:
     # -- compressed raster → HBM (tiffdecode.hip) --------------------------------------------------------------------------
     def device_decodable(self) -> bool:
         """True when the raster's blocks can be decoded on the GPU: LZW or DEFLATE (zlib) strips or tiles of pixel-interleaved
-        uint8 samples (<= 4 per pixel), predictor 1 or 2. Everything else keeps the host reader."""
+        uint8 samples (<= 4 per pixel), predictor 1 or 2; JPEG (compression 7) grey or three-band blocks when the host plan
+        (td_tiff_jpeg_plan: sequential Huffman, 8-bit, 4:4:4 / 4:2:2 / 4:2:0) accepts every one of them. Everything else keeps the
+        host reader."""
         self._setup_blocks()
+        if self.compression == 7:
+            if not (hasattr(self, "_jpeg_tables") and self._counts is not None and self._pil is None and self._flat is None):
+                return False
+            plan = self._jpeg_plan()
+            return plan is not None and int(plan[1][:, 1].max()) <= self.JPEG_DEVICE_MAX_SEGMENT
         return (self.compression in (5, 8, 32946) and self.planar == 1 and self.dtype == np.uint8 and 1 <= self.count <= 4
                 and self._predictor in (1, 2) and self._counts is not None and self._pil is None
                 and self._bw * self._bh * self.count < (1 << 31))
 
+    # One lane decodes one entropy-coded segment at ~1.1 MB/s (a 4096² raster in ONE block without restart markers: 4.0 s on the
+    # device against 85 ms for the host reader; DESIGN.md §7): rasters with a larger segment stay with the host reader
+    JPEG_DEVICE_MAX_SEGMENT = 32 << 10
+
+    def _jpeg_plan(self):
+        """The JPEG raster's decode plan (td_tiff_jpeg_plan over the blocks as they lie in the file), or None when a block is not one
+        the device decoder takes. Computed once: (block_info [nb, 8], segments [nseg, 4] with file offsets, table sets, coefficients)."""
+        if getattr(self, "_jpeg_plan_cache", False) is not False:
+            return self._jpeg_plan_cache
+        from . import _lib
+        lib = _lib.load()
+        nb = self._nx * self._ny
+        offs = np.asarray(self._offs, dtype=np.int64)
+        cnts = np.asarray(self._counts, dtype=np.int64)
+        plan = None
+        if len(offs) == nb == len(cnts) and int((offs + cnts).max()) <= self._mm.size and int(offs.min()) >= 0:
+            rows = np.array([self._block_rows(by) for by in range(self._ny) for _ in range(self._nx)], dtype=np.int32)
+            tables = np.frombuffer(self._jpeg_tables, dtype=np.uint8) if self._jpeg_tables else np.zeros(1, np.uint8)
+            photometric = int(self.tags.get(262, [2 if self.count == 3 else 1])[0])
+            info = np.zeros((nb, 8), dtype=np.int64)
+            totals = np.zeros(4, dtype=np.int64)
+            segs, sets = np.zeros((nb, 4), dtype=np.int64), np.zeros((4, _lib.JPEG_TABSET_BYTES), dtype=np.uint8)
+            for _ in range(2):                                  # the second call with the sizes the first one reported
+                st = lib.td_tiff_jpeg_plan(tables.ctypes.data, len(self._jpeg_tables), self._mm.ctypes.data, offs.ctypes.data,
+                                           cnts.ctypes.data, nb, photometric, self.count, self._bw, rows.ctypes.data, info.ctypes.data,
+                                           segs.ctypes.data, len(segs), sets.ctypes.data, len(sets), totals.ctypes.data)
+                if st != _lib.ERR_CAPACITY:
+                    break
+                segs = np.zeros((int(totals[0]), 4), dtype=np.int64)
+                sets = np.zeros((int(totals[1]), _lib.JPEG_TABSET_BYTES), dtype=np.uint8)
+            _lib.check(st, "td_tiff_jpeg_plan")
+            if totals[3] == 0:
+                plan = (info, segs[:int(totals[0])], sets[:int(totals[1])], int(totals[2]))
+        self._jpeg_plan_cache = plan
+        return plan
+
     def decode_to_device(self, device, stream=None, pinned=None, pool=None):
         """The whole raster decoded in HBM: the compressed blocks are read as they lie in the file (one pread of the span that
         holds them, into pinned memory), copied to the device once, decoded one wave per block (td_tiff_lzw_decode_dev /
-        td_tiff_inflate_dev) and
+        td_tiff_inflate_dev; JPEG: one lane per entropy-coded segment, td_tiff_jpeg_decode_dev, planned once by td_tiff_jpeg_plan) and
         laid out as [height, width, bands] uint8 with predictor 2 undone (td_tiff_blocks_to_image_dev). → (image tensor,
         check) where ``check()`` waits for the kernels and raises ValueError when a block did not decode to its size (the
         caller then falls back to the host reader). Everything is enqueued on ``stream`` (default: the current one). ``pinned``:
@@ -415,11 +460,13 @@ class GeoTiff:
         with torch.cuda.device(dev), ctx:
             st = _lib.stream_ptr()
             comp = pin[:span + 16].to(dev, non_blocking=True)
+            k0, k1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            if self.compression == 7:
+                return self._jpeg_to_device(dev, pin, comp, lo, span, k0, k1)
             meta = torch.from_numpy(np.stack([offs - lo, cnts])).to(dev, non_blocking=True)
             blocks = torch.empty((nb, block_cap), dtype=torch.uint8, device=dev)
             decoded = torch.empty((nb,), dtype=torch.int64, device=dev)
             status = torch.empty((2 * nb + 1,), dtype=torch.int32, device=dev)      # [nb] status + scratch of the wide-table pass
-            k0, k1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             k0.record()
             fn, fname = (lib.td_tiff_lzw_decode_dev, "td_tiff_lzw_decode_dev") if self.compression == 5 else (lib.td_tiff_inflate_dev, "td_tiff_inflate_dev")
             _lib.check(fn(comp.data_ptr(), meta[0].data_ptr(), meta[1].data_ptr(), nb, blocks.data_ptr(), block_cap,
@@ -451,6 +498,52 @@ class GeoTiff:
             return image
         check.event = done
         check.compressed_bytes = span
+        return image, check
+
+    def _jpeg_to_device(self, dev, pin, comp, lo, span, k0, k1):
+        """decode_to_device for JPEG blocks (inside its device / stream context, the compressed bytes already on their way to ``comp``):
+        the plan's arrays go to the device, td_tiff_jpeg_decode_dev decodes (entropy segments one per lane, IDCT, upsampling + colour)
+        straight into the raster. Same (image, check) contract; ``check()`` names the first block whose data is corrupt."""
+        import torch
+        from . import _lib
+        lib = _lib.load()
+        info, segs, sets, ncoef = self._jpeg_plan()
+        nb = len(info)
+        segs = segs.copy()
+        segs[:, 0] -= lo                                        # file offsets → offsets in the copied span
+        info_d = torch.from_numpy(info).to(dev, non_blocking=True)
+        segs_d = torch.from_numpy(segs).to(dev, non_blocking=True)
+        sets_d = torch.from_numpy(sets).to(dev, non_blocking=True)
+        coef = torch.empty((max(ncoef, 64),), dtype=torch.int16, device=dev)
+        planes = torch.empty((max(ncoef, 64),), dtype=torch.uint8, device=dev)
+        status = torch.empty((nb,), dtype=torch.int32, device=dev)
+        image = torch.empty((self.height, self.width, self.count), dtype=torch.uint8, device=dev)
+        st = _lib.stream_ptr()
+        k0.record()
+        _lib.check(lib.td_tiff_jpeg_decode_dev(comp.data_ptr(), info_d.data_ptr(), nb, segs_d.data_ptr(), len(segs), sets_d.data_ptr(),
+                                               coef.data_ptr(), planes.data_ptr(), ncoef, status.data_ptr(), image.data_ptr(), self.width,
+                                               self.height, self.count, self._bw, self._bh, self._nx, st), "td_tiff_jpeg_decode_dev")
+        k1.record()
+        done = torch.cuda.Event()
+        done.record()
+        st_h = torch.empty((nb,), dtype=torch.int32, pin_memory=True)
+        st_h.copy_(status, non_blocking=True)
+        copied = torch.cuda.Event(blocking=True)
+        copied.record()
+        keep = [pin, comp, info_d, segs_d, sets_d, coef, planes, status]     # alive until check() has run: the kernels read them
+
+        def check():
+            copied.synchronize()
+            check.kernel_ms = k0.elapsed_time(k1)          # entropy decode + IDCT + upsampling / colour
+            keep.clear()
+            bad = np.nonzero(st_h.numpy() != 0)[0]
+            if bad.size:
+                b = int(bad[0])
+                raise ValueError(f"{self.path}: JPEG block {b} is corrupt (status {int(st_h[b])})")
+            return image
+        check.event = done
+        check.compressed_bytes = span
+        check.segments = len(segs)
         return image, check
 
     def device_uploadable(self) -> bool:
@@ -620,26 +713,53 @@ class _NullCtx:
         return False
 
 
-def _jpeg_block(blk: np.ndarray, quality: int = 90) -> bytes:
+def _jpeg_block(blk: np.ndarray, quality: int = 90, subsampling: int = 2, restart: int = 0) -> bytes:
     """One strip / tile as a COMPLETE JPEG stream (its own tables: the JPEGTables tag is optional, TIFF Technical Note 2), YCbCr 4:2:0
-    for three bands — Pillow's libjpeg encoder. Lossy: a test fixture for the windowed JPEG reader, not an archive format."""
+    for three bands (``subsampling`` 0 = 4:4:4, 1 = 4:2:2), a restart marker every ``restart`` MCUs when > 0 — Pillow's libjpeg
+    encoder. Lossy: a test fixture for the windowed JPEG reader, not an archive format."""
     import io
     from PIL import Image
     buf = io.BytesIO()
-    Image.fromarray(blk[:, :, 0] if blk.shape[2] == 1 else blk).save(buf, "JPEG", quality=quality, subsampling=2 if blk.shape[2] == 3 else 0)
+    kw = {"restart_marker_blocks": int(restart)} if restart else {}
+    Image.fromarray(blk[:, :, 0] if blk.shape[2] == 1 else blk).save(buf, "JPEG", quality=quality,
+                                                                       subsampling=subsampling if blk.shape[2] == 3 else 0, **kw)
     return buf.getvalue()
+
+
+def _jpeg_split(stream: bytes) -> Tuple[bytes, bytes]:
+    """A complete JPEG stream → (its tables as a JPEGTables tag: SOI, DQT / DHT segments, EOI; the abbreviated stream without them
+    and without JFIF) — the layout GDAL / libtiff write (TIFF Technical Note 2)."""
+    tables, rest = [b"\xff\xd8"], [b"\xff\xd8"]
+    pos = 2
+    while pos < len(stream):
+        m = stream[pos + 1]
+        if m == 0xDA:                                       # SOS: the scan and everything after it stay in the block
+            rest.append(stream[pos:])
+            break
+        n = struct.unpack(">H", stream[pos + 2:pos + 4])[0]
+        seg = stream[pos:pos + 2 + n]
+        if m in (0xDB, 0xC4):
+            tables.append(seg)
+        elif m != 0xE0:
+            rest.append(seg)
+        pos += 2 + n
+    return b"".join(tables) + b"\xff\xd9", b"".join(rest)
 
 
 def write_geotiff(path: str, data: np.ndarray, transform: Sequence[float], epsg: int = 25832, *,
                   tile: Optional[Tuple[int, int]] = None, rows_per_strip: Optional[int] = None,
                   compression: Optional[str] = None, predictor: int = 1, planar: bool = False,
-                  nodata: Optional[float] = None) -> None:
+                  nodata: Optional[float] = None, jpeg_tables: bool = False, jpeg_restart: int = 0,
+                  jpeg_quality: int = 90, jpeg_subsampling: int = 2) -> None:
     """Classic little-endian TIFF with the GeoTIFF tags the reader understands. data: [bands, rows, cols] or
     [rows, cols]; uint8 / uint16 / float32. Defaults: one uncompressed pixel-interleaved strip (what the tile reader
     maps without copying). Options: ``tile=(tile_rows, tile_cols)`` (multiples of 16) or ``rows_per_strip``,
     ``compression`` None / "deflate" / "lzw" (td_tiff_lzw_encode, blocks encoded on host threads) / "jpeg" (lossy; Pillow's encoder per
     block), ``predictor`` 1 / 2
-    (horizontal differencing, integer samples), ``planar`` (one block grid per band)."""
+    (horizontal differencing, integer samples), ``planar`` (one block grid per band). JPEG: ``jpeg_tables`` writes the GDAL / libtiff
+    layout (the quantisation and Huffman tables once, in the JPEGTables tag; abbreviated blocks without JFIF) instead of complete
+    streams; ``jpeg_restart`` > 0 puts a restart marker every that many MCUs; ``jpeg_quality``, ``jpeg_subsampling`` (2 = 4:2:0,
+    1 = 4:2:2, 0 = 4:4:4 for three bands)."""
     arr = np.asarray(data)
     if arr.ndim == 2:
         arr = arr[None]
@@ -671,10 +791,17 @@ def write_geotiff(path: str, data: np.ndarray, transform: Sequence[float], epsg:
                 if predictor == 2:
                     blk[:, 1:] = blk[:, 1:] - blk[:, :-1]          # modulo the sample width
                 if compression == "jpeg":
-                    blocks.append(_jpeg_block(blk))
+                    blocks.append(_jpeg_block(blk, jpeg_quality, jpeg_subsampling, jpeg_restart))
                     continue
                 raw = blk.tobytes()
                 blocks.append(zlib.compress(raw, 6) if compression == "deflate" else raw)
+    tables_tag = None
+    if compression == "jpeg" and jpeg_tables:
+        split = [_jpeg_split(b) for b in blocks]
+        tables_tag = split[0][0]
+        if any(t != tables_tag for t, _ in split):
+            raise ValueError("jpeg_tables: the blocks do not share their tables")
+        blocks = [b for _, b in split]
     if compression == "lzw":
         from . import _lib
         lib = _lib.load()
@@ -695,7 +822,7 @@ def write_geotiff(path: str, data: np.ndarray, transform: Sequence[float], epsg:
             raw = values.encode("latin1") + b"\0"
             entries.append((tag, typ, len(raw), raw))
             return
-        code = {3: "H", 4: "I", 12: "d"}[typ]
+        code = {3: "H", 4: "I", 7: "B", 12: "d"}[typ]
         entries.append((tag, typ, len(values), struct.pack("<" + str(len(values)) + code, *values)))
 
     add(256, 4, [W])
@@ -720,7 +847,9 @@ def write_geotiff(path: str, data: np.ndarray, transform: Sequence[float], epsg:
         add(338, 3, [0] * (C - 3))
     add(339, 3, [fmt[0]] * C)
     if compression == "jpeg" and C == 3:
-        add(530, 3, [2, 2])                    # YCbCrSubSampling: 4:2:0, what _jpeg_block encodes
+        add(530, 3, {0: [1, 1], 1: [2, 1]}.get(jpeg_subsampling, [2, 2]))       # YCbCrSubSampling: what _jpeg_block encodes
+    if tables_tag is not None:
+        add(347, 7, list(tables_tag))          # JPEGTables (UNDEFINED)
     add(33550, 12, [a, -e, 0.0])
     add(33922, 12, [0.0, 0.0, 0.0, c, f, 0.0])
     add(34735, 3, [1, 1, 0, 3, 1024, 0, 1, 1, 1025, 0, 1, 1, 3072, 0, 1, int(epsg)])

@@ -200,8 +200,8 @@ class Predictor:
         the kernel tails of one forward run under the MFMA-bound contractions of the others (bench: 615 vs 554 tiles/s
         fp32, 1868 vs 1550 fp16); "phases" = the phase pipeline described above."""
         self.cfg = cfg
-        # LZW rasters are decoded on the GPU, whole, and their tile windows are cut in HBM (GeoTiff.decode_to_device; images this
-        # process predicts alone: submit). "auto" / True: every LZW raster that qualifies; False: the host reader for everything
+        # LZW, DEFLATE and JPEG rasters are decoded on the GPU, whole, and their tile windows are cut in HBM (GeoTiff.decode_to_device;
+        # images this process predicts alone: submit). "auto" / True: every raster that qualifies; False: the host reader for everything
         if device_decode == "auto" and os.environ.get("TD_DEVICE_DECODE"):       # diagnostics: override the default
             device_decode = {"0": False, "false": False, "all": "all"}.get(os.environ["TD_DEVICE_DECODE"], "auto")
         if device_decode not in (True, False, "auto", "true", "false", "all"):
@@ -377,11 +377,11 @@ class Predictor:
 
     # -- compressed rasters decoded on the GPU -------------------------------------------------------------------
     def prefetch(self, tifpath) -> None:
-        """Starts, on a thread of its own, what the NEXT image needs before its first batch can be cut: an LZW raster's compressed
-        blocks read into pinned memory, copied to the device and decoded there (GeoTiff.decode_to_device), or an uncompressed
+        """Starts, on a thread of its own, what the NEXT image needs before its first batch can be cut: an LZW, DEFLATE or JPEG raster's
+        compressed blocks read into pinned memory, copied to the device and decoded there (GeoTiff.decode_to_device), or an uncompressed
         raster's bytes copied to the device in large sequential pieces (GeoTiff.upload_to_device) — while the current image
         predicts. ``detection.walk_images`` calls it with the path after the one it submits. No-op for rasters the host reader
-        serves (DEFLATE, PackBits, planar, 16-bit) and when ``device_decode`` is off."""
+        serves (PackBits, planar, 16-bit, JPEG blocks the device decoder does not take) and when ``device_decode`` is off."""
         if not self.device_decode or tifpath in self._rasters:
             return
         if self._raster_pool is None:
