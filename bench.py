@@ -17,8 +17,14 @@ is the headline region's time per step. `--dump-outputs DIR` writes the headline
 batch) as DIR/<name>.npy after the timed steps: the inputs are seeded, so two builds can be compared output for output.
 
 Prints ONE JSON line on rank 0 (contract in the task description) with `roofline` (dominant kernel family =
-conv_igemm, MFMA-bound, timed live with HIP events on the forward's stream) and `cpu_baseline` (the torch-CPU oracle
-on a bounded sample of the same stream, rank 0, N=1 only).
+conv_igemm, MFMA-bound, timed live with HIP events on the forward's stream).
+
+A plain run is the headline region alone: set-up, warm-up, the timed steps, --dump-outputs, the line. `--full` adds every
+other region after it (fp16, single-stream / per-launch detail / phase pipeline, R101, fp16 batch 32, two-model, files to
+files) and `cpu_baseline` (the torch-CPU oracle on a bounded sample of the same stream, rank 0, N=1 only); the --no-*
+flags then leave out single regions:
+
+    python bench.py --full --gpus 1
 """
 from __future__ import annotations
 
@@ -58,7 +64,11 @@ SCHED = {"streams": "{n} engines, each a whole forward on its own HIP stream, ba
          "plain": "plain loop: one batch at a time ({n} stream(s))"}
 
 
-def parse():
+# switches of the regions a plain run leaves out: everything after the headline region (--full runs them)
+FULL_ONLY = ("no_fp16", "no_serial", "no_r101", "no_fp16_b32", "no_two_model", "no_e2e", "no_lzw", "no_cpu_baseline")
+
+
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=32)     # 32 x 8 = the 256-tile stream of BASELINE config #2
@@ -98,7 +108,12 @@ def parse():
     ap.add_argument("--streams", type=int, default=0, help="engines / HIP streams the batches alternate over (default 3 for "
                     "--schedule streams, 1 for plain): the HBM-bound kernels and the kernel tails of one forward run under the "
                     "MFMA-bound contractions of the others")
-    a = ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="after the headline region, run every other region and the CPU baseline "
+                    "(the --no-* flags leave out single ones); without it only the headline region runs")
+    a = ap.parse_args(argv)
+    if not a.full:
+        for k in FULL_ONLY:
+            setattr(a, k, True)
     if a.no_pipeline:
         a.schedule = "plain"
     if a.streams <= 0:

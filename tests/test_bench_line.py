@@ -98,3 +98,34 @@ def test_emit_refuses_an_oversize_line():
     with pytest.raises(AssertionError, match="compact bench line"):
         with redirect_stdout(io.StringIO()), redirect_stderr(io.StringIO()):
             bench.emit(full, None)
+
+
+def test_a_plain_run_is_the_headline_region_alone():
+    """Without --full every region after the headline and the CPU baseline are off; the headline region keeps its defaults
+    (three streams, HIP-event profile). With --full the --no-* flags mean what they say."""
+    a = bench.parse(["--steps", "20", "--warmup", "5"])
+    assert not a.full and all(getattr(a, k) for k in bench.FULL_ONLY)
+    assert (a.steps, a.warmup, a.batch, a.precision, a.schedule, a.streams, a.no_profile) == (20, 5, 8, "fp32", "streams", 3, False)
+    f = bench.parse(["--full", "--no-lzw"])
+    assert f.full and f.no_lzw and not any(getattr(f, k) for k in bench.FULL_ONLY if k != "no_lzw")
+    # every region switch is one a plain run turns off (a new region belongs to --full unless it is the headline's own)
+    switches = {k for k in vars(f) if k.startswith("no_")} - {"no_profile", "no_pipeline"}
+    assert switches == set(bench.FULL_ONLY)
+
+
+def test_compact_line_of_a_plain_run(tmp_path):
+    """A plain run's result holds the headline alone: the line keeps the contract keys and `roofline`, and no regions."""
+    full = _full()
+    keep = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+            "dtype", "data", "config", "ranks", "roofline", "breakdown_ms_per_step")
+    plain = {k: full[k] for k in keep if k in full}
+    plain["roofline"].pop("exclusive", None)
+    plain.update(repeats={"headline": 1}, timed_steps=plain["steps"], timed_seconds=1.0, detail_file="bench_detail.json")
+    with redirect_stdout(io.StringIO()) as out, redirect_stderr(io.StringIO()):
+        s = bench.emit(plain, str(tmp_path / "bench_detail.json"))
+    c = json.loads(s)
+    assert out.getvalue().strip() == s
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert c[k] == (pytest.approx(full[k], rel=1e-5) if isinstance(full[k], float) else full[k]), k
+    assert c["roofline"]["frac"] <= 1.0 and "exclusive_frac" not in c["roofline"]
+    assert "cpu_baseline" not in c and c["regions"] == {}

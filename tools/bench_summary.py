@@ -1,5 +1,6 @@
 """One-line-per-region view of bench.py's FULL result: python tools/bench_summary.py bench_detail.json (the detail file
-bench.py writes beside its compact stdout line), or the full JSON on stdin."""
+bench.py writes beside its compact stdout line), or the full JSON on stdin. Regions beyond the headline come from
+`bench.py --full`."""
 import json
 import sys
 

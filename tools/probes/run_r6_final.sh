@@ -4,7 +4,7 @@ set -e
 O=gpurun_out/r6_final
 rm -rf $O && mkdir -p $O
 nproc > $O/nproc.txt
-timeout -k 10 500 python3 bench.py --detail $O/r06_bench_n1_detail.json > $O/bench.log 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+timeout -k 10 500 python3 bench.py --full --detail $O/r06_bench_n1_detail.json > $O/bench.log 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
 grep "^{" $O/bench.log | tail -1 > $O/r06_bench_n1.json
 echo bench done
 for args in "codec=lzw side=9000" "codec=lzw side=20000" "codec=lzw side=5000" "codec=deflate side=9000" "codec=deflate side=20000" "codec=deflate side=5000"; do
