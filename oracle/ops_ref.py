@@ -148,17 +148,12 @@ def level_assign(boxes: np.ndarray, min_level=2, max_level=5, canon_size=224, ca
 # ----------------------------------------------------------------------------------------------
 # RoIAlign (aligned=True, sampling_ratio=0)  — Appendix A item 9
 # ----------------------------------------------------------------------------------------------
-def roi_align(feat: np.ndarray, rois: np.ndarray, spatial_scale: float, pooled: int) -> np.ndarray:
-    """feat [C,H,W] float32, rois [R,4] (x1,y1,x2,y2) in image units → [R,C,pooled,pooled].
-
-    Same operation order as the torchvision CPU kernel: per bin, sum over the adaptive sample
-    grid of (w1*v1 + w2*v2 + w3*v3 + w4*v4), then divide by the sample count.
-    """
-    feat = np.asarray(feat, dtype=F32)
-    C, H, W = feat.shape
+def roi_align_samples(rois: np.ndarray, H: int, W: int, spatial_scale: float, pooled: int):
+    """The float32 sampling geometry of :func:`roi_align` on an H x W map: yields one tuple per output bin,
+    ``(r, ph, pw, count, taps)``, with ``taps`` the in-map samples in summation order (iy outer, ix inner), each
+    ``(yl, yh, xl, xh, w1, w2, w3, w4)``: the four corner pixels and their float32 weights."""
     rois = np.asarray(rois, dtype=F32).reshape(-1, 4)
     R = rois.shape[0]
-    out = np.zeros((R, C, pooled, pooled), dtype=F32)
     sc = F32(spatial_scale)
     half = F32(0.5)
     for r in range(R):
@@ -175,7 +170,7 @@ def roi_align(feat: np.ndarray, rois: np.ndarray, spatial_scale: float, pooled: 
         count = F32(max(gh * gw, 1))
         for ph in range(pooled):
             for pw in range(pooled):
-                acc = np.zeros(C, dtype=F32)
+                taps = []
                 for iy in range(gh):
                     y = sh + F32(ph) * bh + (F32(iy) + half) * bh / F32(gh)
                     for ix in range(gw):
@@ -200,10 +195,27 @@ def roi_align(feat: np.ndarray, rois: np.ndarray, spatial_scale: float, pooled: 
                         lx = F32(xx - F32(xl))
                         hy = F32(1) - ly
                         hx = F32(1) - lx
-                        w1, w2, w3, w4 = hy * hx, hy * lx, ly * hx, ly * lx
-                        acc = acc + (w1 * feat[:, yl, xl] + w2 * feat[:, yl, xh]
-                                     + w3 * feat[:, yh, xl] + w4 * feat[:, yh, xh])
-                out[r, :, ph, pw] = acc / count
+                        taps.append((yl, yh, xl, xh, hy * hx, hy * lx, ly * hx, ly * lx))
+                yield r, ph, pw, count, taps
+
+
+def roi_align(feat: np.ndarray, rois: np.ndarray, spatial_scale: float, pooled: int) -> np.ndarray:
+    """feat [C,H,W] float32, rois [R,4] (x1,y1,x2,y2) in image units → [R,C,pooled,pooled].
+
+    Same operation order as the torchvision CPU kernel: per bin, sum over the adaptive sample
+    grid of (w1*v1 + w2*v2 + w3*v3 + w4*v4), then divide by the sample count.
+    """
+    feat = np.asarray(feat, dtype=F32)
+    C, H, W = feat.shape
+    rois = np.asarray(rois, dtype=F32).reshape(-1, 4)
+    R = rois.shape[0]
+    out = np.zeros((R, C, pooled, pooled), dtype=F32)
+    for r, ph, pw, count, taps in roi_align_samples(rois, H, W, spatial_scale, pooled):
+        acc = np.zeros(C, dtype=F32)
+        for yl, yh, xl, xh, w1, w2, w3, w4 in taps:
+            acc = acc + (w1 * feat[:, yl, xl] + w2 * feat[:, yl, xh]
+                         + w3 * feat[:, yh, xl] + w4 * feat[:, yh, xh])
+        out[r, :, ph, pw] = acc / count
     return out
 
 

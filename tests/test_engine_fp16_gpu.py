@@ -436,3 +436,112 @@ def test_fp16_flip_rate_is_bounded_over_64_tiles():
           f"{100 * clusters / max(flips, 1):.0f} % of them duplicate-cluster flips (IoU >= 0.5 partner)")
     assert rate <= 0.03
     assert clusters >= 0.5 * flips
+
+
+# ---- stage-wise checks on identical inputs (the fp16 counterparts of tests/test_engine_gpu.py's) ------------------------
+@pytest.fixture(scope="module")
+def stages16():
+    """setup16's network and images plus a 480 x 544 image, through an fp16 engine of its own (so setup16's engine keeps
+    its own last forward). None of this seeded network's proposals reaches
+    p5 (sqrt(area) >= 448), not even on an 800 x 960 image; p5 differs from p2-p4 only in which map the same kernel
+    reads, and tests/test_roi_align_gpu.py covers that kernel on its own."""
+    from treedetection_amd.engine import Engine
+    sd = make_synthetic_state_dict(50, seed=5)
+    rng = np.random.default_rng(21)
+    inputs = [{"image": smooth_image(rng, 256, 320), "height": 320, "width": 400},
+              {"image": smooth_image(rng, 224, 256), "height": 224, "width": 256},
+              {"image": smooth_image(rng, 480, 544), "height": 480, "width": 544}]
+    eng = Engine(sd, precision="fp16")
+    got = eng(inputs)
+    sizes = [(int(i["image"].shape[1]), int(i["image"].shape[2])) for i in inputs]
+    feats = {f"p{l}": torch.from_numpy(nchw(eng.tensor(f"p{l}").float())) for l in (2, 3, 4, 5)}
+    return dict(sd=sd, oracle=MaskRCNNOracle(sd), inputs=inputs, eng=eng, got=got, sizes=sizes, feats=feats)
+
+
+def _pooled_bits_check(oracle, feats, n, boxes, got_rows, pooled):
+    """got_rows [R, pooled, pooled, C] fp16 must be float16(oracle.roi_pool) of the engine's own (widened) maps; on a
+    mismatch the message names the RoIs, their oracle FPN level and sqrt(area) / 224 (a level-boundary case shows there)."""
+    ref, lv = oracle.roi_pool({k: v[n:n + 1] for k, v in feats.items()}, [boxes], pooled)
+    want = ref[0].astype(np.float16)
+    g = got_rows.transpose(0, 3, 1, 2)
+    bad = np.nonzero((g != want).reshape(len(boxes), -1).any(axis=1))[0]
+    msg = ""
+    if bad.size:
+        b = boxes[bad[:8]]
+        s = np.sqrt((b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])) / 224.0
+        msg = (f"image {n}: {bad.size} of {len(boxes)} RoIs differ from float16(oracle); first: rows {bad[:8].tolist()}, "
+               f"boxes {b.tolist()}, oracle levels {(lv[0][bad[:8]] + 2).tolist()}, sqrt(area)/224 {s.tolist()}")
+    return set(lv[0].tolist()), msg
+
+
+def test_fp16_pooled7_bit_exact_on_identical_inputs(stages16):
+    eng, oracle, feats = stages16["eng"], stages16["oracle"], stages16["feats"]
+    props = eng.tensor("proposals").cpu().numpy()
+    pc = eng.tensor("proposal_count").cpu().numpy()
+    pooled = eng.tensor("pooled7")
+    assert pooled.dtype == torch.float16
+    pooled = pooled.cpu().numpy()
+    P = props.shape[1]
+    levels, msgs = set(), []
+    for n in range(props.shape[0]):
+        lv, msg = _pooled_bits_check(oracle, feats, n, props[n, :pc[n]], pooled[n * P: n * P + pc[n]], 7)
+        levels |= lv
+        msgs += [msg] if msg else []
+    assert levels >= {0, 1, 2}, f"proposals cover FPN levels {sorted(levels)} only"
+    assert not msgs, "\n".join(msgs)
+
+
+def test_fp16_pooled14_bit_exact_on_identical_inputs(stages16):
+    eng, oracle, feats, got = stages16["eng"], stages16["oracle"], stages16["feats"], stages16["got"]
+    dbn = eng.tensor("det_boxes_net").cpu().numpy()
+    pooled = eng.tensor("pooled14").cpu().numpy()
+    row, msgs = 0, []
+    for n in range(len(got)):
+        k = len(got[n]["scores"])
+        assert k > 0
+        _, msg = _pooled_bits_check(oracle, feats, n, dbn[n, :k], pooled[row:row + k], 14)
+        msgs += [msg] if msg else []
+        row += k
+    assert not msgs, "\n".join(msgs)
+
+
+def test_fp16_detections_from_the_engines_box_pred(stages16):
+    """oracle.detections + postprocess on the fp16 engine's own box-predictor outputs: the same detections in the same
+    order, scores <= 1e-6, boxes <= 1e-3 (the fp32 engine's bar, test_box_head_and_detections_on_identical_inputs)."""
+    eng, oracle, got = stages16["eng"], stages16["oracle"], stages16["got"]
+    props = eng.tensor("proposals").cpu().numpy()
+    pc = eng.tensor("proposal_count").cpu().numpy()
+    pred = eng.tensor("box_pred").cpu().numpy()
+    P = props.shape[1]
+    for n in range(props.shape[0]):
+        p = pred[n * P: n * P + pc[n]]
+        b, s, _ = oracle.detections(p[:, :2], p[:, 2:], props[n, :pc[n]], stages16["sizes"][n])
+        inp = stages16["inputs"][n]
+        ob, os_, _, _ = oracle.postprocess(b, s, np.zeros((len(s), 28, 28), np.float32), stages16["sizes"][n],
+                                           (inp["height"], inp["width"]), paste=False)
+        assert len(got[n]["scores"]) == len(os_) > 0
+        assert np.abs(got[n]["scores"] - os_).max() <= 1e-6
+        assert np.abs(got[n]["pred_boxes"] - ob).max() <= 1e-3
+
+
+def test_fp16_mask_predictor_against_float64(stages16):
+    """mask_predict_kernel<_Float16> on the engine's own deconv output: logits within (C + 8) 2^-24 sum|x w| + 2^-24 |b|
+    of the float64 dot product, and the returned probabilities within 4 float32 ulp of the float64 sigmoid of those logits."""
+    eng, sd, got = stages16["eng"], stages16["sd"], stages16["got"]
+    total = sum(len(g["scores"]) for g in got)
+    x = eng.tensor("mask_deconv")
+    assert x.dtype == torch.float16 and x.shape[1:3] == (28, 28)
+    C = x.shape[3]
+    x = x[:total].cpu().numpy().astype(np.float64).reshape(-1, C)
+    w = np.asarray(sd["roi_heads.mask_head.predictor.weight"], np.float32).reshape(-1).astype(np.float64)
+    b = float(np.asarray(sd["roi_heads.mask_head.predictor.bias"], np.float32).reshape(-1)[0])
+    assert w.size == C
+    ref = x @ w + b
+    bound = (C + 8) * 2.0 ** -24 * (np.abs(x) @ np.abs(w)) + 2.0 ** -24 * abs(b)
+    logits = eng.tensor("mask_logits")[:total].cpu().numpy().reshape(-1).astype(np.float64)
+    err = np.abs(logits - ref)
+    assert (err <= bound).all(), f"worst err / bound {np.max(err / bound):.3g}"
+    probs = np.concatenate([g["mask_probs"] for g in got]).reshape(-1)
+    sig = 1.0 / (1.0 + np.exp(-logits))
+    assert (np.abs(probs.astype(np.float64) - sig) <= 4 * np.spacing(sig.astype(np.float32)).astype(np.float64)).all()
+    assert np.ptp(ref) > 1.0          # (a predictor that sees real features, not a constant)

@@ -100,8 +100,7 @@ def test_roi_align_matches_oracle(pooled, scale, C, H, W):
                                 _lib.stream_ptr()), "td_roi_align")
     torch.cuda.synchronize()
     got = out.cpu().numpy().transpose(0, 3, 1, 2)
-    assert np.allclose(got, ref, rtol=0, atol=2e-6 * max(1.0, np.abs(ref).max()))
-    assert (got == ref).mean() > 0.99     # same op order: bit-identical almost everywhere
+    assert np.array_equal(got, ref)       # same float32 operation order as the oracle: bit-identical
 
 
 def test_roi_align_linear_ramp_known_answer():

@@ -269,8 +269,9 @@ __global__ __launch_bounds__(256) void roi_align_kernel(FeatLevels fl, const flo
 // on two NEIGHBOURING BINS of the RoI at once (bin b on lanes 0-31, bin b + 1 on lanes 32-63): both bins have the same
 // gh x gw sample grid, so the halves run in lockstep through (iy, ix) and differ only in their table entries — half the
 // load instructions, half the per-sample bookkeeping. Tables are packed {lo, hi, l, h} (one ds_read_b128 per axis);
-// addresses are 32-bit element offsets from the level's base. Per channel the arithmetic and its order are those of
-// roi_align_kernel → bit-identical outputs.
+// addresses are 32-bit element offsets from the image's map, so a launch may use this kernel only while every level's
+// map holds fewer than 2^32 elements (h * w * C < 2^32, roi_h8_ok); larger maps go to roi_align_kernel, which indexes
+// in size_t. Per channel the arithmetic and its order are those of roi_align_kernel → bit-identical outputs.
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 template <int D>
 __global__ __launch_bounds__(256) void roi_align_h8_kernel(FeatLevels fl, const float* __restrict__ rois,
@@ -620,17 +621,20 @@ __global__ __launch_bounds__(256) void paste_fill_kernel(const float* __restrict
 }  // namespace
 
 // ring depth of roi_align_kernel (samples in flight per wave); TD_ROI_DEPTH overrides it for diagnostics (tools/roi_bench.py)
-static bool roi_h8_ok(int C) {
+// roi_align_h8_kernel's table path forms 32-bit element offsets inside one image's map: only maps below 2^32 elements
+static bool roi_h8_ok(const FeatLevels& fl) {
     static const char* env = getenv("TD_ROI_H8");      // diagnostics: 0 = the 4-channel-per-lane kernel for fp16 too
     if (env && atoi(env) == 0) return false;
-    return C <= 256 && C % 8 == 0;
+    for (int l = 0; l < ROI_LEVELS; ++l)
+        if ((size_t)fl.h[l] * (size_t)fl.w[l] * (size_t)fl.C >= ((size_t)1 << 32)) return false;
+    return fl.C <= 256 && fl.C % 8 == 0;
 }
 
 template <typename T>
 static void roi_align_dispatch(dim3 grid, hipStream_t stream, int depth, const FeatLevels& fl, const float* rois, const int* counts,
                                int items, int roi_stride, int pooled, int compact, T* out, int* total_rows, int single_level, int parts) {
     if constexpr (std::is_same<T, _Float16>::value) {
-        if (roi_h8_ok(fl.C)) {
+        if (roi_h8_ok(fl)) {
 #define TD_ROI_LAUNCH8(DD) hipLaunchKernelGGL((roi_align_h8_kernel<DD>), grid, dim3(256), 0, stream, fl, rois, counts, items, \
                                               roi_stride, pooled, compact, out, total_rows, single_level, parts)
             switch (depth) {
