@@ -76,43 +76,31 @@ td_status td_conv2d_head_nhwc(const void* x, const void* w, const float* bias, c
 }
 
 static td_status conv2d_api(ConvArgs& a, int precision, void* stream) {
-    const int Cin = a.Cin, Cout = a.Cout, KH = a.KH, KW = a.KW;
-    const void* w = a.w;
-    const int ke = (precision & 0xff) == TD_PRECISION_FP16 ? 64 : 32;
-    if (a.tile_strict && conv_cfg_is_bd(a.tile_cfg) && Cin % ke != 0) {
-        td_set_error("conv2d: tile_cfg %d cannot run this launch (strict tile selection): filter-direct tiles need Cin %% %d == 0 (Cin = %d)",
-                     a.tile_cfg, ke, Cin);
-        return TD_ERR_INVALID;
-    }
-    if (conv_cfg_is_bd(a.tile_cfg) && Cin % ke == 0) {
-        // tests: the filter-direct tiles (conv_bdirect.hip) need the filters in fragment order: packed here from the caller's
-        // [Cout][KH][KW][Cin] bank (the engine packs once at load time)
-        hipStream_t s = static_cast<hipStream_t>(stream);
-        const int es = (precision & 0xff) == TD_PRECISION_FP16 ? 2 : 4;
-        const size_t n = (size_t)Cout * KH * KW * Cin;
-        std::vector<unsigned char> bits(n * es), packed;
-        TD_HIP_CHECK(hipStreamSynchronize(s));
-        TD_HIP_CHECK(hipMemcpy(bits.data(), w, n * es, hipMemcpyDeviceToHost));
-        conv_bd_pack(bits.data(), es, Cout, KH, KW, Cin, packed);
-        void* wf = nullptr;
-        td_status st = scratch(&wf, packed.size());
-        if (st < 0) return st;
-        hipError_t herr = hipMemcpy(wf, packed.data(), packed.size(), hipMemcpyHostToDevice);
-        a.w_frag = wf;
-        if (herr == hipSuccess) st = conv2d_launch(a, precision & 0xff, s);
-        hipError_t herr2 = hipStreamSynchronize(s);
-        (void)hipFree(wf);
-        if (st < 0) return st;
-        TD_HIP_CHECK(herr);
-        TD_HIP_CHECK(herr2);
-        return TD_OK;
-    }
-    if (a.tile_cfg == 21 || a.tile_cfg == 22 || a.tile_cfg == 28) {
-        td_set_error("conv2d: tile_cfg %d (stream-K / 4-wave 256x256) is an experiment that lost to the block tiles; it lives in "
-                     "csrc/experimental/ and is not part of the product library", a.tile_cfg);
-        return TD_ERR_INVALID;
-    }
-    return conv2d_launch(a, precision & 0xff, static_cast<hipStream_t>(stream));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    ConvArgs with_frag = a;
+    with_frag.w_frag = a.w;          // stands in for the copy packed below: made only for a launch the tile can run
+    if (!conv_tile(a.tile_cfg) || !conv_tile(a.tile_cfg)->frag || conv_tile_refusal(a.tile_cfg, with_frag, precision & 0xff))
+        return conv2d_launch(a, precision & 0xff, s);
+    // tests: the filter-direct tiles (conv_bdirect.hip) need the filters in fragment order: packed here from the caller's
+    // [Cout][KH][KW][Cin] bank (the engine packs once at load time)
+    const int es = (precision & 0xff) == TD_PRECISION_FP16 ? 2 : 4;
+    const size_t n = (size_t)a.Cout * a.KH * a.KW * a.Cin;
+    std::vector<unsigned char> bits(n * es), packed;
+    TD_HIP_CHECK(hipStreamSynchronize(s));
+    TD_HIP_CHECK(hipMemcpy(bits.data(), a.w, n * es, hipMemcpyDeviceToHost));
+    conv_bd_pack(bits.data(), es, a.Cout, a.KH, a.KW, a.Cin, packed);
+    void* wf = nullptr;
+    td_status st = scratch(&wf, packed.size());
+    if (st < 0) return st;
+    hipError_t herr = hipMemcpy(wf, packed.data(), packed.size(), hipMemcpyHostToDevice);
+    a.w_frag = wf;
+    if (herr == hipSuccess) st = conv2d_launch(a, precision & 0xff, s);
+    hipError_t herr2 = hipStreamSynchronize(s);
+    (void)hipFree(wf);
+    if (st < 0) return st;
+    TD_HIP_CHECK(herr);
+    TD_HIP_CHECK(herr2);
+    return TD_OK;
 }
 
 static td_status wino_api(const float* x, const float* w, const float* scale, const float* bias, float* y, int B, int H, int W, int Cin,

@@ -60,14 +60,10 @@ struct ConvArgs {
     // whose 16 transform planes are 16 independent 1x1 contractions (winograd.hip). 0 / 1 = a plain launch.
     int batch_count;
     long long x_bs, w_bs, y_bs;
-    const void* w_frag;   // the same filters in MFMA fragment order (conv_bdirect.hip: tile ids 23 - 27), or nullptr
-    // only read by csrc/experimental/conv_streamk.hip (not in the product library): partial-tile slots / ticket counters
-    float* sk_ws;
-    int* sk_cnt;
-    int tile_cfg;         // -1 = heuristic; 0..3 = block tile 128x128, 128x64, 64x128, 64x64 with 2 LDS stages,
-                          // 4..7 = the same tiles with 3 stages (engine autotunes)
+    const void* w_frag;   // the same filters in MFMA fragment order (the tiles with ConvTile::frag), or nullptr
+    int tile_cfg;         // -1 = heuristic; else an id of TD_CONV_TILES (engine autotunes)
     int tile_strict;      // 1: a forced tile_cfg this launch cannot run is an error, not a silent switch to the heuristic tile (tests)
-    // fused 1x1 head (fp16 engine, block tiles that own all 256 output channels: conv_head_capable): the finished fp16
+    // fused 1x1 head (fp16 engine, block tiles that own all 256 output channels: ConvTile::head): the finished fp16
     // tile — this layer's output — is contracted with head_w [head_n <= 32][Cout = 256] straight from its LDS staging and
     // only head_y [M][head_n] (fp32, + head_b) is written; y is NOT written. The RPN's 3x3 conv + its 15-row head.
     const void* head_w;
@@ -88,31 +84,69 @@ struct ConvArgs {
     } lev[5];
     int ntiles;                   // tiles of all levels
 };
-// tile ids whose block owns 256 output channels at once (fp16): the head fusion above applies
-static inline bool conv_head_capable(int cfg, int precision) {
-    // (the single-stage 256-wide tiles 14 / 16 stage their output as fp32 wave-rows, not as one fp16 tile: not capable)
-    return precision == TD_PRECISION_FP16 && (cfg == 9 || cfg == 10 || cfg == 12 || cfg == 13 || cfg == 17 || cfg == 23 || cfg == 27 || cfg == 29);
-}
-// tile_cfg ids (conv_igemm.hip:dispatch): 0..3 4-wave tiles 128x128 / 128x64 / 64x128 / 64x64 (2 LDS stages), 4..7 the same
-// with 3 stages (measured no better: not tuned over), 8 = 256x128 / 9 = 128x256 (8 waves), 10 = 256x256 (16 waves),
-// 11..13 = 256x256 with larger per-wave tiles, 14..16 = single-LDS-stage 256x256 / 128x128 / 128x256 (thin 1x1 layers),
-// 17 = conv_pp8_kernel: 256x256, 8 waves, ping-pong phases, DMA 1.5 k-chunks ahead (fp16 only),
-// 18..20 = plane_gemm_kernel: persistent 64x128 / 128x128 / 64x64 tile walk for the fp32 Winograd plane contractions,
-// 21 / 22 / 28 = retired ids (stream-K and the 4-wave 256x256 tile: measured slower in round 3, sources kept under csrc/experimental/, not built
-// into the product; conv2d_launch refuses them), 23 / 24 / 25 / 26 / 27 = conv_bd_kernel: 64x256 / 64x128 / 64x128 with two k-chunks per barrier / 64x128 with three k-steps of loads in flight / 64x256 with two, filter fragments
-// straight from a fragment-ordered copy of the filters into registers (conv_bdirect.hip)
-// 29 / 30 = conv_bd_kernel 128x256 / 128x128, three k-steps of loads in flight: taller tiles, half the filter re-reads (round 4)
-// 31 / 32 = conv_igemm_kernel 256x32 / 128x32 (4 x 1 waves): layers with at most 32 output channels (round 4)
-// 33 = conv_bs_kernel (conv_bstat.hip, round 4): filter-stationary 1x1 for the thin-K layers (<= 4 k-chunks), one block per CU
-#define TD_CONV_TILE_CFG_MAX 33
-static inline bool conv_cfg_is_bd(int cfg) { return (cfg >= 23 && cfg <= 27) || cfg == 29 || cfg == 30 || cfg == 33; }      // tiles that read the fragment-ordered filter copy
-// Tried in this order — from the tile that moves the fewest bytes per FLOP to the one that moves the most — and a later candidate
+// ---- block tiles (ConvArgs::tile_cfg): one row per id. Tune-cache files, tests and profiles/ name tiles by these ids, so an
+// id keeps its number and a retired one keeps its row. Adding a tile: a row here and a case in its family's launcher.
+// Families: conv_igemm_kernel (conv_igemm.hip:dispatch); conv_pp8_kernel (8 waves, ping-pong phases, DMA 1.5 k-chunks ahead);
+// plane_gemm_kernel (persistent walk over the fp32 Winograd planes); conv_bd_kernel (conv_bdirect.hip: filter fragments from the
+// fragment-ordered copy straight into registers); conv_bs_kernel (conv_bstat.hip: filter-stationary 1x1, one block per CU).
+enum ConvFamily : unsigned char { TILE_IGEMM, TILE_PP8, TILE_PLANE, TILE_BD, TILE_BS, TILE_RETIRED };
+enum : unsigned char { TILE_F32 = 1 << TD_PRECISION_FP32, TILE_F16 = 1 << TD_PRECISION_FP16, TILE_ANY = TILE_F32 | TILE_F16 };
+struct ConvTile {
+    ConvFamily family;
+    unsigned char variant;      // TILE_BD: conv_bd_launch's variant
+    unsigned char prec;         // TILE_F32 / TILE_F16: the precisions it runs
+    bool head;                  // owns all 256 output channels as one fp16 tile: a fused head (ConvArgs::head_w) applies
+    bool frag;                  // reads the fragment-ordered filter copy (ConvArgs::w_frag)
+    signed char tune_rank;      // position in the tuner's order, -1 = never timed
+    unsigned char max_ksteps;   // tuner only: at most this many k-steps (KH * KW * Cin / k-chunk), 0 = any
+    short min_cout, max_cout;   // tuner only: output channels, 0 = no limit
+};
+// Tuning order (tune_rank): from the tile that moves the fewest bytes per FLOP to the one that moves the most; a later candidate
 // replaces the best so far only when it is more than TD_TUNE_HYST percent faster (default 2): among tiles that tie within the
 // measurement noise the one with the larger footprint wins, which keeps the choice (and with it the HBM / L2 traffic the PMC
 // passes report) from flipping between runs — fc1 was seen on the 128 x 128 tile in one run and on a 64 x 128 tile (+2 GB of filter
 // re-reads per step, same time) in the next.
-// 15 / 16 only for <= 4 k-steps, 17 only for fp16, 18-20 only for plane contractions, 23-27 / 29 / 30 / 33 only with packed filters, 31 / 32 only for <= 32 output channels, 33 only where conv_bs_ok
-static const int TD_CONV_TUNE_CANDIDATES[] = {33, 10, 17, 29, 16, 0, 15, 30, 23, 27, 1, 2, 24, 25, 26, 31, 3, 32, 18, 19, 20};
+inline constexpr ConvTile TD_CONV_TILES[] = {
+    //  family        var  prec      head   frag  rank kstp cout>=  <=      id: block tile
+    {TILE_IGEMM,   0, TILE_ANY, false, false,  5, 0,   0,  0},     //  0: 128x128, 4 waves, 2 LDS stages
+    {TILE_IGEMM,   0, TILE_ANY, false, false, 10, 0,   0,  0},     //  1: 128x64
+    {TILE_IGEMM,   0, TILE_ANY, false, false, 11, 0,   0,  0},     //  2: 64x128
+    {TILE_IGEMM,   0, TILE_ANY, false, false, 16, 0,   0,  0},     //  3: 64x64
+    {TILE_IGEMM,   0, TILE_ANY, false, false, -1, 0,   0,  0},     //  4..7: 0..3 with 3 LDS stages (measured no better)
+    {TILE_IGEMM,   0, TILE_ANY, false, false, -1, 0,   0,  0},
+    {TILE_IGEMM,   0, TILE_ANY, false, false, -1, 0,   0,  0},
+    {TILE_IGEMM,   0, TILE_ANY, false, false, -1, 0,   0,  0},
+    {TILE_IGEMM,   0, TILE_ANY, false, false, -1, 0,   0,  0},     //  8: 256x128, 8 waves
+    {TILE_IGEMM,   0, TILE_ANY, true,  false, -1, 0,   0,  0},     //  9: 128x256, 8 waves
+    {TILE_IGEMM,   0, TILE_ANY, true,  false,  1, 0,   0,  0},     // 10: 256x256, 16 waves
+    {TILE_IGEMM,   0, TILE_ANY, false, false, -1, 0,   0,  0},     // 11..13: 256x256 with larger per-wave tiles
+    {TILE_IGEMM,   0, TILE_ANY, true,  false, -1, 0,   0,  0},
+    {TILE_IGEMM,   0, TILE_ANY, true,  false, -1, 0,   0,  0},
+    {TILE_IGEMM,   0, TILE_ANY, false, false, -1, 4,   0,  0},     // 14..16: one LDS stage, 256x256 / 128x128 / 128x256 (thin 1x1 layers;
+    {TILE_IGEMM,   0, TILE_ANY, false, false,  6, 4,   0,  0},     //   14 / 16 stage their output as fp32 wave-rows: no fused head)
+    {TILE_IGEMM,   0, TILE_ANY, false, false,  4, 4,   0,  0},
+    {TILE_PP8,     0, TILE_F16, true,  false,  2, 0, 128,  0},     // 17: conv_pp8_kernel 256x256
+    {TILE_PLANE,   0, TILE_F32, false, false, 18, 0,   0,  0},     // 18: plane_gemm_kernel 64x128
+    {TILE_PLANE,   0, TILE_F32, false, false, 19, 0,   0,  0},     // 19: 128x128
+    {TILE_PLANE,   0, TILE_F32, false, false, 20, 0,   0,  0},     // 20: 64x64
+    {TILE_RETIRED, 0, 0,        false, false, -1, 0,   0,  0},     // 21, 22: stream-K (retired: measured slower, deleted)
+    {TILE_RETIRED, 0, 0,        false, false, -1, 0,   0,  0},
+    {TILE_BD,      0, TILE_ANY, true,  true,   8, 0,   0,  0},     // 23: conv_bd_kernel 64x256
+    {TILE_BD,      1, TILE_ANY, false, true,  12, 0,   0,  0},     // 24: 64x128
+    {TILE_BD,      2, TILE_ANY, false, true,  13, 0,   0,  0},     // 25: 64x128, two k-chunks per barrier
+    {TILE_BD,      3, TILE_ANY, false, true,  14, 0,   0,  0},     // 26: 64x128, three k-steps of loads in flight
+    {TILE_BD,      4, TILE_ANY, true,  true,   9, 0,   0,  0},     // 27: 64x256, two k-steps in flight
+    {TILE_RETIRED, 0, 0,        false, false, -1, 0,   0,  0},     // 28: the 4-wave 256x256 tile
+    {TILE_BD,      5, TILE_ANY, true,  true,   3, 0,   0,  0},     // 29: 128x256, three k-steps in flight (half the filter re-reads)
+    {TILE_BD,      6, TILE_ANY, false, true,   7, 0,   0,  0},     // 30: 128x128, three k-steps in flight
+    {TILE_IGEMM,   0, TILE_ANY, false, false, 15, 0,   0, 32},     // 31: 256x32, 4 x 1 waves (the thin heads)
+    {TILE_IGEMM,   0, TILE_ANY, false, false, 17, 0,   0, 32},     // 32: 128x32
+    {TILE_BS,      0, TILE_ANY, false, true,   0, 4, 128,  0},     // 33: conv_bs_kernel (its other tuning rules: conv_bs_ok)
+};
+static inline const ConvTile* conv_tile(int id) { return id >= 0 && id < (int)(sizeof TD_CONV_TILES / sizeof *TD_CONV_TILES) ? &TD_CONV_TILES[id] : nullptr; }
+static inline bool conv_head_capable(int id, int precision) { return precision == TD_PRECISION_FP16 && conv_tile(id) && conv_tile(id)->head; }
+// nullptr when tile `id` can run this launch, else why not (-1, the heuristic tile, runs every launch)
+const char* conv_tile_refusal(int id, const ConvArgs& a, int precision);
 td_status conv2d_launch(const ConvArgs& a, int precision, hipStream_t stream);
 // a.nlev levels (x / w / bias / y / head_y / H / W filled in; M, tile0, ntiles are computed here) in one conv_pp8_kernel grid;
 // everything else (B, Cin, Cout = 256, KH = KW = 3, relu, head_w / head_b / head_n) from the common fields. Bit-identical to one
@@ -125,7 +159,6 @@ td_status conv_bd_launch(const ConvArgs& a, int precision, int variant, hipStrea
 // filter-stationary form (conv_bstat.hip, tile id 33)
 bool conv_bs_ok(const ConvArgs& a, int precision);
 td_status conv_bs_launch(const ConvArgs& a, int precision, hipStream_t stream);
-bool conv_plane_ok(const ConvArgs& a, int precision);       // tile ids 18-20 apply to this launch
 td_status wino_gemm_launch(const ConvArgs& a, hipStream_t stream);     // Winograd plane contractions, input transform fused (fp32)
 
 // ---- fused bottleneck tail (bottleneck.hip): 3x3 (mid -> mid) + BN + ReLU, then 1x1 (mid -> 4 mid) + BN + shortcut + ReLU ----

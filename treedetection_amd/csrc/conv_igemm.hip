@@ -1005,37 +1005,32 @@ td_status dispatch(const ConvArgs& a, int cfg, hipStream_t stream) {
         // quarters of its MFMAs on padding — the RPN head at p2 (M = 320 000, K = 256) was MFMA-bound on it (round 4)
         case 31: return launch<T, TO, 2, 1, 2, 4, 1>(a, stream);    // 256 x 32, 4 waves of 64 x 32
         case 32: return launch<T, TO, 1, 1, 2, 4, 1>(a, stream);    // 128 x 32, 4 waves of 32 x 32
-        case 17:                                                     // 256 x 256, 8 waves, ping-pong phases (fp16 only)
-            if constexpr (std::is_same<T, _Float16>::value) {
-                const int tiles = td_cdiv(a.M, 256) * td_cdiv(a.Cout, 256);
-                hipLaunchKernelGGL((conv_pp8_kernel<TO>), dim3(tiles), dim3(512), 0, stream, a);
-                TD_KERNEL_CHECK();
-                return TD_OK;
-            } else {
-                td_set_error("conv2d: tile_cfg 17 is an fp16 kernel");
-                return TD_ERR_INVALID;
-            }
-        case 18:                                                     // persistent plane contractions (fp32 Winograd planes)
-        case 19:
-        case 20:
-            if constexpr (std::is_same<T, float>::value && std::is_same<TO, float>::value) {
-                const int planes = a.batch_count > 1 ? a.batch_count : 1;
-                const int bm = cfg == 19 ? 128 : 64, bn = cfg == 20 ? 64 : 128;
-                const long long total = (long long)td_cdiv(a.M, bm) * td_cdiv(a.Cout, bn) * planes;
-                const int per_cu = (160 * 1024) / (2 * (bm + bn) * CHUNK_BYTES);       // resident blocks per CU by LDS
-                const long long cap = 256ll * (per_cu > 0 ? per_cu : 1);
-                const unsigned grid = (unsigned)(total < cap ? total : cap);
-                if (cfg == 18) hipLaunchKernelGGL((plane_gemm_kernel<1, 2>), dim3(grid), dim3(256), 0, stream, a);
-                else if (cfg == 19) hipLaunchKernelGGL((plane_gemm_kernel<2, 2>), dim3(grid), dim3(256), 0, stream, a);
-                else hipLaunchKernelGGL((plane_gemm_kernel<1, 1>), dim3(grid), dim3(256), 0, stream, a);
-                TD_KERNEL_CHECK();
-                return TD_OK;
-            } else {
-                td_set_error("conv2d: tile_cfg 18-20 are fp32 kernels");
-                return TD_ERR_INVALID;
-            }
         default: td_set_error("conv2d: bad tile_cfg %d", cfg); return TD_ERR_INVALID;
     }
+}
+
+// tile id 17: 256 x 256, 8 waves, ping-pong phases (fp16 inputs)
+template <typename TO>
+td_status pp8_launch(const ConvArgs& a, hipStream_t stream) {
+    const int tiles = td_cdiv(a.M, 256) * td_cdiv(a.Cout, 256);
+    hipLaunchKernelGGL((conv_pp8_kernel<TO>), dim3(tiles), dim3(512), 0, stream, a);
+    TD_KERNEL_CHECK();
+    return TD_OK;
+}
+
+// tile ids 18-20: persistent plane contractions (fp32 Winograd planes)
+td_status plane_launch(const ConvArgs& a, int cfg, hipStream_t stream) {
+    const int planes = a.batch_count > 1 ? a.batch_count : 1;
+    const int bm = cfg == 19 ? 128 : 64, bn = cfg == 20 ? 64 : 128;
+    const long long total = (long long)td_cdiv(a.M, bm) * td_cdiv(a.Cout, bn) * planes;
+    const int per_cu = (160 * 1024) / (2 * (bm + bn) * CHUNK_BYTES);       // resident blocks per CU by LDS
+    const long long cap = 256ll * (per_cu > 0 ? per_cu : 1);
+    const unsigned grid = (unsigned)(total < cap ? total : cap);
+    if (cfg == 18) hipLaunchKernelGGL((plane_gemm_kernel<1, 2>), dim3(grid), dim3(256), 0, stream, a);
+    else if (cfg == 19) hipLaunchKernelGGL((plane_gemm_kernel<2, 2>), dim3(grid), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL((plane_gemm_kernel<1, 1>), dim3(grid), dim3(256), 0, stream, a);
+    TD_KERNEL_CHECK();
+    return TD_OK;
 }
 
 }  // namespace
@@ -1050,15 +1045,6 @@ td_status wino_gemm_launch(const ConvArgs& a, hipStream_t stream) {
     hipLaunchKernelGGL(wino_gemm_kernel, dim3((unsigned)nblk), dim3(512), 0, stream, a);
     TD_KERNEL_CHECK();
     return TD_OK;
-}
-
-// tile ids 18-20 (plane_gemm_kernel) take the fp32 contractions with plain rows: the Winograd planes and the 1x1 / stride-1
-// layers (scale, bias, same-size residual and ReLU are applied in the accumulator layout)
-bool conv_plane_ok(const ConvArgs& a, int precision) {
-    return precision == TD_PRECISION_FP32 && a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0 && a.out_mode == 0 &&
-           a.res_shift == 0 && !a.out_f32 && a.m_off == 0 && a.Cin >= 32 && a.Cin % 32 == 0 && a.M > 0 && a.Cout > 0 &&
-           (a.batch_count <= 1 || !a.res) &&
-           (size_t)a.M * a.Cin * 4 < 0xfffffff0ull - (1u << 20);
 }
 
 td_status conv_pp8_grouped_launch(ConvArgs a, hipStream_t stream) {
@@ -1087,9 +1073,42 @@ td_status conv_pp8_grouped_launch(ConvArgs a, hipStream_t stream) {
     return TD_OK;
 }
 
+const char* conv_tile_refusal(int id, const ConvArgs& a, int precision) {
+    const ConvTile* t = conv_tile(id);
+    if (!t) return id < 0 ? nullptr : "no such tile id";
+    if (t->family == TILE_RETIRED)
+        return "a retired experiment (stream-K / the 4-wave 256x256 tile) that lost to the block tiles and left the library";
+    const unsigned prec_bit = precision == TD_PRECISION_FP16 ? TILE_F16 : precision == TD_PRECISION_FP32 ? TILE_F32 : 0;
+    if (!(t->prec & prec_bit)) return t->prec == TILE_F16 ? "fp16-only tile" : "fp32-only tile";
+    if (t->family == TILE_PP8 && (a.out_mode != 0 || a.batch_count > 1)) return "plain output, no batched launch only";
+    // plane_gemm_kernel: fp32 contractions with plain rows (scale, bias, same-size residual, ReLU in the accumulator layout)
+    if (t->family == TILE_PLANE && !(a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0 && a.out_mode == 0 && a.res_shift == 0 && !a.out_f32 &&
+                                     a.m_off == 0 && a.Cin >= 32 && a.Cin % 32 == 0 && a.M > 0 && a.Cout > 0 && (a.batch_count <= 1 || !a.res) &&
+                                     (size_t)a.M * a.Cin * 4 < 0xfffffff0ull - (1u << 20)))
+        return "plane-only tile (fp32 1x1, stride 1, no padding, no upsampled residual, Cin a multiple of 32)";
+    if (t->family == TILE_BS && !conv_bs_ok(a, precision))
+        return "conv_bs_ok failed (1x1, stride 1, 1 / 2 / 4 k-chunks, 128 <= Cout <= 2048, Cout % 8 == 0, packed filters)";
+    if (t->family == TILE_BD && !conv_bd_ok(a, precision)) return "conv_bd_ok failed (packed filters, plain output)";
+    return nullptr;
+}
+
 td_status conv2d_launch(const ConvArgs& a, int precision, hipStream_t stream) {
-    const int ke = precision == TD_PRECISION_FP16 ? 64 : 32;
     TD_REQUIRE(precision == TD_PRECISION_FP32 || precision == TD_PRECISION_FP16, "conv2d: bad precision %d", precision);
+    int cfg = a.tile_cfg;
+    if (cfg < 0) {
+        const char* forced = getenv("TD_CONV_CFG");      // diagnostics / tests only (read per call: tests switch it)
+        if (forced) cfg = atoi(forced);
+    }
+    // a forced id this launch cannot run falls back to the heuristic tile — or, with tile_strict, is refused by name; an id
+    // that names no tile of the library is always refused
+    if (const char* why = conv_tile_refusal(cfg, a, precision)) {
+        if (a.tile_strict || !conv_tile(cfg) || conv_tile(cfg)->family == TILE_RETIRED) {
+            td_set_error("conv2d: tile_cfg %d cannot run this launch%s: %s", cfg, a.tile_strict ? " (strict tile selection)" : "", why);
+            return TD_ERR_INVALID;
+        }
+        cfg = -1;
+    }
+    const int ke = precision == TD_PRECISION_FP16 ? 64 : 32;
     TD_REQUIRE(a.Cin % ke == 0, "conv2d: Cin=%d must be a multiple of %d", a.Cin, ke);
     TD_REQUIRE(a.M > 0 && a.Cout > 0, "conv2d: empty problem (M=%d, Cout=%d)", a.M, a.Cout);
     const size_t es = precision == TD_PRECISION_FP16 ? 2 : 4;
@@ -1097,41 +1116,22 @@ td_status conv2d_launch(const ConvArgs& a, int precision, hipStream_t stream) {
     TD_REQUIRE((size_t)a.Cout * a.KH * a.KW * a.Cin * es < 0xfffffff0ull - (1u << 20), "conv2d: weight tensor must stay below 4 GB");
     TD_REQUIRE(a.KH * a.KW <= 32, "conv2d: at most 32 filter taps (got %dx%d)", a.KH, a.KW);
     TD_REQUIRE(a.out_mode == 0 || (a.Cout % 32 == 0 && !a.res), "conv2d: bad deconv configuration");
-    int cfg = a.tile_cfg;
-    if (cfg < 0) {
-        const char* forced = getenv("TD_CONV_CFG");            // diagnostics / tests only (read per call: tests switch it)
-        if (forced) cfg = atoi(forced);
-    }
-    const bool no_fp16_tile = precision != TD_PRECISION_FP16 || a.out_mode != 0 || a.batch_count > 1;
-    // a forced id this launch cannot run falls back to the heuristic tile — or, with tile_strict, is refused by name
-    const char* why = nullptr;
-    if (cfg == 17 && no_fp16_tile) why = "fp16-only tile (float16 tensors, plain output, no batched launch)";
-    else if (cfg == 28 && (no_fp16_tile || a.m_dyn)) why = "fp16-only tile with static row counts";
-    else if (cfg >= 18 && cfg <= 20 && !conv_plane_ok(a, precision))
-        why = "plane-only tile (conv_plane_ok: fp32 1x1, stride 1, no padding, no upsampled residual, Cin a multiple of 32)";
-    else if (cfg == 33 && !conv_bs_ok(a, precision))
-        why = "conv_bs_ok failed (1x1, stride 1, 1 / 2 / 4 k-chunks, 128 <= Cout <= 2048, Cout % 8 == 0, packed filters)";
-    else if (conv_cfg_is_bd(cfg) && !conv_bd_ok(a, precision)) why = "conv_bd_ok failed (packed filters, plain output)";
-    if (why) {
-        if (a.tile_strict) {
-            td_set_error("conv2d: tile_cfg %d cannot run this launch (strict tile selection): %s", cfg, why);
-            return TD_ERR_INVALID;
-        }
-        cfg = -1;
-    }
     // a fused head (ConvArgs::head_w) exists only in the tiles that stage all 256 output channels as one fp16 tile: any other
     // resolution of the tile id would silently write y and leave head_y untouched
     TD_REQUIRE(!a.head_w || (conv_head_capable(cfg, precision) && a.Cout == 256 && !a.res && a.out_mode == 0 && a.head_y && a.head_n >= 1 && a.head_n <= 32),
                "conv2d: a fused head needs a 256-channel fp16 layer on a tile that owns all its channels (tile id %d)", cfg);
-    if (cfg == 33) return conv_bs_launch(a, precision, stream);
-    if (conv_cfg_is_bd(cfg)) return conv_bd_launch(a, precision, cfg <= 27 ? cfg - 23 : cfg - 24, stream);
-    TD_REQUIRE(a.batch_count <= 1 || (a.KH == 1 && a.KW == 1 && !a.res), "conv2d: batched launches are 1x1 contractions");
     if (cfg < 0) {
         // heuristic (the engine replaces it by a measured choice per layer shape): wide N for wide layers, 64-row
         // tiles when there is less than one 128-row tile per CU
         const bool small_m = a.M <= 64 * 256;
         cfg = a.Cout <= 64 ? (small_m ? 3 : 1) : (small_m ? 2 : 0);
     }
+    const ConvTile& t = *conv_tile(cfg);
+    if (t.family == TILE_BS) return conv_bs_launch(a, precision, stream);
+    if (t.family == TILE_BD) return conv_bd_launch(a, precision, t.variant, stream);
+    TD_REQUIRE(a.batch_count <= 1 || (a.KH == 1 && a.KW == 1 && !a.res), "conv2d: batched launches are 1x1 contractions");
+    if (t.family == TILE_PP8) return a.out_f32 ? pp8_launch<float>(a, stream) : pp8_launch<_Float16>(a, stream);
+    if (t.family == TILE_PLANE) return plane_launch(a, cfg, stream);
     if (precision == TD_PRECISION_FP32) return dispatch<float, float>(a, cfg, stream);
     if (a.out_f32) return dispatch<_Float16, float>(a, cfg, stream);
     return dispatch<_Float16, _Float16>(a, cfg, stream);

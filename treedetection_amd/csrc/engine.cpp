@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <functional>
 #include <map>
 #include <optional>
 #include <string>
@@ -220,7 +221,7 @@ td_status upload_w(td_engine* e, const std::vector<float>& h, void** d) {
     return st;
 }
 
-// second copy of a filter bank in MFMA fragment order for conv_bd_kernel (tile ids 23 - 27), both precisions
+// second copy of a filter bank in MFMA fragment order for the tiles with ConvTile::frag, both precisions
 td_status upload_frag(td_engine* e, const std::vector<float>& h, ConvLayer& L) {
     L.w_frag = nullptr;
     static const bool off = getenv("TD_BDIRECT") && atoi(getenv("TD_BDIRECT")) == 0;
@@ -355,23 +356,6 @@ td_status load_conv_bias(td_engine* e, const TensorMap& tm, const std::string& p
     return upload(e, std::vector<float>(b->data, b->data + L.cout), &L.bias);
 }
 
-td_status run_conv_raw(const ConvLayer& L, const void* x, int B, int H, int W, int stride, int pad, bool relu, void* y,
-                       const void* res, int res_shift, hipStream_t s, int precision, const int* m_dyn, int m_mul,
-                       int out_mode, int tile_cfg = -1, const ConvLayer* head = nullptr, float* head_y = nullptr) {
-    ConvArgs a{};
-    if (head) {          // fused 1x1 head (ConvArgs::head_w): the caller checked conv_head_capable(tile_cfg)
-        a.head_w = head->w; a.head_b = head->bias; a.head_y = head_y; a.head_n = head->cout;
-    }
-    a.x = x; a.w = L.w; a.w_frag = L.w_frag; a.scale = L.scale; a.bias = L.bias; a.res = res; a.y = y;
-    a.B = B; a.H = H; a.W = W; a.Cin = L.cin; a.Cout = L.cout; a.KH = L.kh; a.KW = L.kw;
-    a.stride = stride; a.pad = pad;
-    a.Ho = (H + 2 * pad - L.kh) / stride + 1;
-    a.Wo = (W + 2 * pad - L.kw) / stride + 1;
-    a.res_shift = res_shift; a.relu = relu ? 1 : 0; a.out_mode = out_mode;
-    a.M = B * a.Ho * a.Wo; a.m_dyn = m_dyn; a.m_mul = m_mul; a.tile_cfg = tile_cfg; a.out_f32 = L.out_f32 ? 1 : 0;
-    return conv2d_launch(a, precision, s);
-}
-
 void set_named(td_engine* e, const char* name, void* p, int64_t d0, int64_t d1 = 0, int64_t d2 = 0, int64_t d3 = 0,
                int elem = 4) {
     NamedTensor t;
@@ -456,7 +440,7 @@ void load_tune_cache(td_engine* e) {
     if (FILE* f = fopen(e->tune_cache.c_str(), "r")) {
         int pr, a0, a1, a2, a3, a4, cfg;
         while (fscanf(f, "%d %d %d %d %d %d %d", &pr, &a0, &a1, &a2, &a3, &a4, &cfg) == 7) {
-            if (pr == e->desc.precision && cfg >= 0 && cfg <= TD_CONV_TILE_CFG_MAX) e->tuned[std::make_tuple(a0, a1, a2, a3, a4)] = cfg;
+            if (pr == e->desc.precision && conv_tile(cfg)) e->tuned[std::make_tuple(a0, a1, a2, a3, a4)] = cfg;
         }
         fclose(f);
     }
@@ -808,6 +792,120 @@ td_status td_engine_reserve(td_engine* e, int B, int Hp, int Wp) {
 
 namespace {
 
+// Times `launch` on the live buffers (idempotent: same inputs, same outputs); launches shorter than ~100 us are timed again
+// over a longer run (event granularity and clock ramps otherwise pick the wrong tile for them).
+td_status time_launch(td_engine* e, hipStream_t s, hipEvent_t ea, hipEvent_t eb, const std::function<td_status()>& launch, float* ms_out) {
+    td_status st = launch();
+    if (st < 0) return st;
+    static const bool evict = !(getenv("TD_TUNE_EVICT") && atoi(getenv("TD_TUNE_EVICT")) == 0);
+    if (evict && !e->tune_evict) {      // one launch per timed interval, L2 emptied before it; the fastest of five
+        e->tune_evict_bytes = (size_t)64 << 20;
+        if (hipMalloc(&e->tune_evict, e->tune_evict_bytes) != hipSuccess) {      // no room for the scratch: time the hot loop instead
+            (void)hipGetLastError();
+            e->tune_evict = nullptr;
+            e->tune_evict_bytes = 0;
+        }
+    }
+    const bool cold = evict && e->tune_evict;       // cold: five rounds of one launch; hot: 2 launches, then 8 when under 0.1 ms
+    float ms = 1e30f;
+    for (int round = 0, reps = cold ? 1 : 2; round < (cold ? 5 : 2); ++round, reps = cold ? 1 : 8) {
+        if (cold) TD_HIP_CHECK(hipMemsetAsync(e->tune_evict, round, e->tune_evict_bytes, s));
+        TD_HIP_CHECK(hipEventRecord(ea, s));
+        for (int rep = 0; rep < reps; ++rep)
+            if ((st = launch()) < 0) return st;
+        TD_HIP_CHECK(hipEventRecord(eb, s));
+        TD_HIP_CHECK(hipEventSynchronize(eb));
+        float t = 0.f;
+        TD_HIP_CHECK(hipEventElapsedTime(&t, ea, eb));
+        t /= (float)reps;
+        if (t < ms) ms = t;
+        if (!cold && ms > 0.1f) break;
+    }
+    *ms_out = ms;
+    return TD_OK;
+}
+
+// Measured block tile of one launch shape (cached per engine, shared through the TD_TUNE_CACHE file). The candidates are the
+// tiles of TD_CONV_TILES with a tuning rank, in rank order, within their tuning limits and able to run `a` — the ConvArgs the
+// timed launch carries — so the id recorded is the tile that ran. launch_cfg(id) runs the launch on tile id.
+td_status tuned_cfg(td_engine* e, const std::tuple<int, int, int, int, int>& key, int prec, const ConvArgs& a, hipStream_t s,
+                    const std::function<td_status(int)>& launch_cfg, int* cfg_out) {
+    const int ksteps = a.KH * a.KW * a.Cin / (prec == TD_PRECISION_FP16 ? 64 : 32);
+    auto candidate = [&](int id) {
+        const ConvTile* t = conv_tile(id);
+        return t && (!t->max_ksteps || ksteps <= t->max_ksteps) && a.Cout >= t->min_cout && (!t->max_cout || a.Cout <= t->max_cout) &&
+               !conv_tile_refusal(id, a, prec);
+    };
+    static const int forced = getenv("TD_FORCE_CFG") ? atoi(getenv("TD_FORCE_CFG")) : -1;      // diagnostics: one block tile everywhere it applies
+    if (candidate(forced)) {
+        *cfg_out = forced;
+        return TD_OK;
+    }
+    auto it = e->tuned.find(key);
+    if (it == e->tuned.end()) {
+        load_tune_cache(e);                   // another engine of this process may have measured it meanwhile
+        it = e->tuned.find(key);
+    }
+    if (it != e->tuned.end()) {
+        *cfg_out = it->second;
+        return TD_OK;
+    }
+    std::vector<int> order;
+    for (const ConvTile& t : TD_CONV_TILES)
+        if (t.tune_rank >= 0 && candidate((int)(&t - TD_CONV_TILES))) order.push_back((int)(&t - TD_CONV_TILES));
+    std::sort(order.begin(), order.end(), [](int x, int y) { return TD_CONV_TILES[x].tune_rank < TD_CONV_TILES[y].tune_rank; });
+    float best = 1e30f;
+    int best_cfg = -1;
+    hipEvent_t ea, eb;
+    TD_HIP_CHECK(hipEventCreate(&ea));
+    TD_HIP_CHECK(hipEventCreate(&eb));
+    td_status st = TD_OK;
+    for (int c : order) {
+        float ms = 1e30f;
+        if ((st = time_launch(e, s, ea, eb, [&]() { return launch_cfg(c); }, &ms)) < 0) break;
+        static const float hyst = 1.f - 0.01f * (getenv("TD_TUNE_HYST") ? (float)atof(getenv("TD_TUNE_HYST")) : 2.f);
+        if (best_cfg < 0 || ms < best * hyst) { best = ms; best_cfg = c; }
+    }
+    (void)hipEventDestroy(ea);
+    (void)hipEventDestroy(eb);
+    if (st < 0) return st;
+    e->tuned.emplace(key, best_cfg);
+    if (FILE* f = e->tune_cache.empty() ? nullptr : fopen(e->tune_cache.c_str(), "a")) {
+        fprintf(f, "%d %d %d %d %d %d %d\n", prec, std::get<0>(key), std::get<1>(key), std::get<2>(key), std::get<3>(key), std::get<4>(key), best_cfg);
+        fclose(f);
+    }
+    *cfg_out = best_cfg;
+    return TD_OK;
+}
+
+// The 16 plane contractions of Winograd F(2x2,3x3) slab [t0, t0 + n) of layer L: V [16][n][cin] x U [16][cout][cin] -> M as ONE
+// batched launch, or (wino_fused) the contraction that reads the layer input x [B,H,W,cin] and transforms it in its A staging
+ConvArgs wino_plane_args(const td_engine* e, const ConvLayer& L, const void* x, int B, int H, int W, int n, long long t0,
+                         const int* m_dyn, int m_mul) {
+    ConvArgs a{};
+    a.w = L.wino_u; a.y = e->wino_m;
+    a.Cin = L.cin; a.Cout = L.cout; a.KH = a.KW = 1; a.stride = 1; a.pad = 0;
+    a.M = n; a.m_dyn = m_dyn; a.m_mul = m_dyn ? m_mul / 4 : 1;    // even H, W with a device row count: tiles = rows / 4
+    a.m_off = (int)t0;
+    a.w_bs = (long long)L.cout * L.cin; a.y_bs = (long long)n * L.cout;
+    if (e->wino_fused) { a.x = x; a.B = B; a.H = H; a.W = W; }
+    else { a.x = e->wino_v; a.B = 1; a.H = 1; a.W = n; a.Ho = 1; a.Wo = n; a.batch_count = 16; a.x_bs = (long long)n * L.cin; }
+    return a;
+}
+
+// The 36 plane contractions of Winograd F(4x4,3x3) over a whole layer as ONE batched launch: V [36][T][cin] x U -> M [36][T][cout]
+ConvArgs wino43_plane_args(const td_engine* e, const ConvLayer& L, int B, int H, int W, const int* m_dyn) {
+    const int tiles_img = ((H + 3) / 4) * ((W + 3) / 4);
+    const long long T = (long long)B * tiles_img;
+    ConvArgs a{};
+    a.x = e->wino_v; a.w = L.wino_u43; a.y = e->wino_m;
+    a.Cin = L.cin; a.Cout = L.cout; a.KH = a.KW = 1; a.stride = 1; a.pad = 0;
+    a.B = 1; a.H = 1; a.W = (int)T; a.Ho = 1; a.Wo = (int)T;
+    a.M = (int)T; a.m_dyn = m_dyn; a.m_mul = m_dyn ? tiles_img : 1;
+    a.batch_count = 36; a.x_bs = T * L.cin; a.w_bs = (long long)L.cout * L.cin; a.y_bs = T * L.cout;
+    return a;
+}
+
 // The forward in six phases. Contractions (0 trunk: stem..RPN heads, 2 box-head FCs, 4 mask-head convs) and the
 // low-occupancy selection work (1 RPN top-k/NMS/merge + RoIAlign 7x7, 3 detections + RoIAlign 14x14, 5 mask
 // predictor/scatter/paste) alternate, so a caller can keep three batches in flight: contraction phases of successive
@@ -823,113 +921,6 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
     auto PH = [&](int k) { return (phase_mask >> k) & 1u; };
     if (PH(0)) e->named.clear();
     td_status st;
-    // Times `launch(cfg)` for every candidate block tile on the live buffers (idempotent: same inputs, same outputs) and
-    // returns the fastest; launches shorter than ~100 us are timed again over a longer run (event granularity and clock
-    // ramps otherwise pick the wrong tile for them).
-    auto time_launch = [&](hipStream_t s_, hipEvent_t ea, hipEvent_t eb, auto&& launch, float* ms_out) -> td_status {
-        td_status st2 = launch();
-        if (st2 < 0) return st2;
-        static const bool evict = !(getenv("TD_TUNE_EVICT") && atoi(getenv("TD_TUNE_EVICT")) == 0);
-        if (evict) {
-            // one launch per timed interval, L2 emptied before it; the fastest of five
-            if (!e->tune_evict) {
-                e->tune_evict_bytes = (size_t)64 << 20;
-                if (hipMalloc(&e->tune_evict, e->tune_evict_bytes) != hipSuccess) {      // no room for the scratch: time the hot loop instead
-                    (void)hipGetLastError();
-                    e->tune_evict = nullptr;
-                    e->tune_evict_bytes = 0;
-                }
-            }
-        }
-        if (evict && e->tune_evict) {
-            float ms = 1e30f;
-            for (int rep = 0; rep < 5; ++rep) {
-                TD_HIP_CHECK(hipMemsetAsync(e->tune_evict, rep, e->tune_evict_bytes, s_));
-                TD_HIP_CHECK(hipEventRecord(ea, s_));
-                if ((st2 = launch()) < 0) return st2;
-                TD_HIP_CHECK(hipEventRecord(eb, s_));
-                TD_HIP_CHECK(hipEventSynchronize(eb));
-                float t = 0.f;
-                TD_HIP_CHECK(hipEventElapsedTime(&t, ea, eb));
-                if (t < ms) ms = t;
-            }
-            *ms_out = ms;
-            return TD_OK;
-        }
-        float ms = 1e30f;
-        for (int round = 0, reps = 2; round < 2; ++round, reps = 8) {
-            TD_HIP_CHECK(hipEventRecord(ea, s_));
-            for (int rep = 0; rep < reps; ++rep)
-                if ((st2 = launch()) < 0) return st2;
-            TD_HIP_CHECK(hipEventRecord(eb, s_));
-            TD_HIP_CHECK(hipEventSynchronize(eb));
-            float t = 0.f;
-            TD_HIP_CHECK(hipEventElapsedTime(&t, ea, eb));
-            t /= (float)reps;
-            if (t < ms) ms = t;
-            if (ms > 0.1f) break;
-        }
-        *ms_out = ms;
-        return TD_OK;
-    };
-    // measured block tile of one launch shape (cached per engine, shared through the TD_TUNE_CACHE file)
-    // bd_ok: the launch being tuned has a fragment-ordered filter copy and a plain output (filter-direct tiles 23-27); the
-    // Winograd plane contractions pass false (their ConvArgs carry no w_frag: conv2d_launch would remap the id to the heuristic tile)
-    auto tuned_cfg = [&](const std::tuple<int, int, int, int, int>& key, int prec_, int ksteps, bool pp8_ok, bool plane_ok, bool bd_ok, hipStream_t s_,
-                         auto&& launch_cfg, int* cfg_out, float* best_ms) -> td_status {
-        static const int forced = getenv("TD_FORCE_CFG") ? atoi(getenv("TD_FORCE_CFG")) : -1;      // diagnostics: one block tile everywhere it applies
-        if (forced >= 0 && forced <= TD_CONV_TILE_CFG_MAX && !best_ms && !(forced >= 14 && forced <= 16 && ksteps > 4) && !(forced == 17 && !pp8_ok) &&
-            !(forced >= 18 && forced <= 20 && !plane_ok) && !(conv_cfg_is_bd(forced) && !bd_ok)) {
-            *cfg_out = forced;
-            return TD_OK;
-        }
-        auto it = e->tuned.find(key);
-        if (it == e->tuned.end()) {
-            load_tune_cache(e);                   // another engine of this process may have measured it meanwhile
-            it = e->tuned.find(key);
-        }
-        if (it != e->tuned.end() && !best_ms) {
-            *cfg_out = it->second;
-            return TD_OK;
-        }
-        float best = 1e30f;
-        int best_cfg = -1;
-        hipEvent_t ea, eb;
-        TD_HIP_CHECK(hipEventCreate(&ea));
-        TD_HIP_CHECK(hipEventCreate(&eb));
-        for (int c : TD_CONV_TUNE_CANDIDATES) {
-            if (it != e->tuned.end() && c != it->second) continue;       // known choice: only its time is wanted
-            if (c >= 14 && c <= 16 && ksteps > 4) continue;      // single-stage tiles only pay on the thin 1x1 layers
-            if (c == 17 && !pp8_ok) continue;                    // fp16 256x256 ping-pong tile
-            if (c >= 18 && c <= 20 && !plane_ok) continue;       // persistent tile walk: Winograd plane contractions only
-            if (conv_cfg_is_bd(c) && !bd_ok) continue;          // filter-direct tiles: layers with a fragment-ordered filter copy
-            if (c == 33 && !(std::get<2>(key) == 17 && (std::get<4>(key) & ~1) == 4 && std::get<0>(key) >= 128 && ksteps <= 4 && ksteps != 3)) continue;      // filter-stationary: 1x1, stride 1, plain output, <= 4 k-chunks
-            if ((c == 31 || c == 32) && std::get<0>(key) > 32) continue;      // 32-column tiles: the thin heads only
-            float ms = 1e30f;
-            td_status st2 = time_launch(s_, ea, eb, [&]() { return launch_cfg(c); }, &ms);
-            if (st2 < 0) {
-                (void)hipEventDestroy(ea);
-                (void)hipEventDestroy(eb);
-                return st2;
-            }
-            static const float hyst = 1.f - 0.01f * (getenv("TD_TUNE_HYST") ? (float)atof(getenv("TD_TUNE_HYST")) : 2.f);
-            if (best_cfg < 0 || ms < best * hyst) { best = ms; best_cfg = c; }
-        }
-        (void)hipEventDestroy(ea);
-        (void)hipEventDestroy(eb);
-        if (it == e->tuned.end()) {
-            e->tuned.emplace(key, best_cfg);
-            if (!e->tune_cache.empty()) {
-                if (FILE* f = fopen(e->tune_cache.c_str(), "a")) {
-                    fprintf(f, "%d %d %d %d %d %d %d\n", prec_, std::get<0>(key), std::get<1>(key), std::get<2>(key), std::get<3>(key), std::get<4>(key), best_cfg);
-                    fclose(f);
-                }
-            }
-        }
-        *cfg_out = best_cfg;
-        if (best_ms) *best_ms = best;
-        return TD_OK;
-    };
     // Winograd F(2x2,3x3) path of a stride-1 3x3 layer (fp32 engine): input transform → ONE batched launch of the 16
     // plane contractions through conv_igemm_kernel → output transform with the layer's scale / bias / ReLU (winograd.hip)
     auto run_wino = [&](const ConvLayer& L, const void* x_, int B_, int H_, int W_, bool relu, void* y_, hipStream_t s_,
@@ -939,12 +930,7 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
         for (long long t0 = 0; t0 < T; t0 += Ts) {
             const int n = (int)std::min<long long>(Ts, T - t0);
             td_status st2;
-            ConvArgs a{};
-            a.w = L.wino_u; a.y = e->wino_m;
-            a.Cin = L.cin; a.Cout = L.cout; a.KH = a.KW = 1; a.stride = 1; a.pad = 0;
-            a.M = n; a.m_dyn = m_dyn; a.m_mul = m_dyn ? m_mul / 4 : 1;    // even H, W with a device row count: tiles = rows / 4
-            a.m_off = (int)t0;
-            a.w_bs = (long long)L.cout * L.cin; a.y_bs = (long long)n * L.cout;
+            ConvArgs a = wino_plane_args(e, L, x_, B_, H_, W_, n, t0, m_dyn, m_mul);
             // speed-of-light model (static row counts only): 16 plane products of [n x cin] x [cin x cout]; V = 4x the input,
             // M = 4x the output, each crossing HBM once per direction
             const double xb = 4.0 * B_ * H_ * W_ * L.cin, yb = 4.0 * B_ * H_ * W_ * L.cout, ub = 4.0 * 16 * L.cout * L.cin;
@@ -953,13 +939,10 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
             if (e->wino_fused) {
                 // input transform fused into the contraction's A staging (wino_gemm_kernel): V never exists in memory
                 ClassScope cs(e, s_, dyn ? TD_CLS_MASK_HEAD : TD_CLS_WINO_GEMM, dyn ? 0.0 : pf, dyn ? 0.0 : xb + ub + mb);
-                a.x = x_; a.B = B_; a.H = H_; a.W = W_;
                 if ((st2 = wino_gemm_launch(a, s_)) < 0) return st2;
             } else {
                 { ClassScope cs(e, s_, dyn ? TD_CLS_MASK_HEAD : TD_CLS_WINO_XFORM, 0.0, dyn ? 0.0 : xb + vb);
                 if ((st2 = wino_input_launch(static_cast<const float*>(x_), B_, H_, W_, L.cin, e->wino_v, m_dyn, m_mul, t0, n, s_)) < 0) return st2; }
-                a.x = e->wino_v; a.B = 1; a.H = 1; a.W = n; a.Ho = 1; a.Wo = n;
-                a.batch_count = 16; a.x_bs = (long long)n * L.cin;
                 a.tile_cfg = gemm_cfg;
                 ClassScope cs(e, s_, dyn ? TD_CLS_MASK_HEAD : TD_CLS_WINO_GEMM, dyn ? 0.0 : pf, dyn ? 0.0 : vb + ub + mb);
                 if ((st2 = conv2d_launch(a, TD_PRECISION_FP32, s_)) < 0) return st2;
@@ -1003,12 +986,7 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
         }
         { ClassScope cs(e, s_, dyn ? TD_CLS_MASK_HEAD : TD_CLS_WINO_XFORM, 0.0, dyn ? 0.0 : xb + vb);
         if ((st2 = wino43_input_launch(static_cast<const float*>(x_), B_, H_, W_, L.cin, e->wino_v, m_dyn, s_)) < 0) return st2; }
-        ConvArgs a{};
-        a.x = e->wino_v; a.w = L.wino_u43; a.y = e->wino_m;
-        a.Cin = L.cin; a.Cout = L.cout; a.KH = a.KW = 1; a.stride = 1; a.pad = 0;
-        a.B = 1; a.H = 1; a.W = (int)T; a.Ho = 1; a.Wo = (int)T;
-        a.M = (int)T; a.m_dyn = m_dyn; a.m_mul = m_dyn ? tiles_img : 1;
-        a.batch_count = 36; a.x_bs = T * L.cin; a.w_bs = (long long)L.cout * L.cin; a.y_bs = T * L.cout;
+        ConvArgs a = wino43_plane_args(e, L, B_, H_, W_, m_dyn);
         a.tile_cfg = gemm_cfg;
         { ClassScope cs(e, s_, dyn ? TD_CLS_MASK_HEAD : TD_CLS_WINO_GEMM, dyn ? 0.0 : pf, dyn ? 0.0 : vb + ub + mb);
         if ((st2 = conv2d_launch(a, TD_PRECISION_FP32, s_)) < 0) return st2; }
@@ -1039,15 +1017,15 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
         int cfg = -1, wino_cfg = -1;
         bool use_wino = false, use_43 = false, use_fold = false;
         td_status st2;
+        ConvArgs ca{};          // the direct launch (tuned tile, fused head below)
+        ca.x = x_; ca.w = L.w; ca.w_frag = L.w_frag; ca.scale = L.scale; ca.bias = L.bias; ca.res = res_; ca.y = y_;
+        ca.B = B_; ca.H = H_; ca.W = W_; ca.Cin = L.cin; ca.Cout = L.cout; ca.KH = L.kh; ca.KW = L.kw;
+        ca.stride = stride; ca.pad = pad; ca.Ho = Ho; ca.Wo = Wo;
+        ca.res_shift = res_shift; ca.relu = relu ? 1 : 0; ca.out_mode = out_mode;
+        ca.M = B_ * Ho * Wo; ca.m_dyn = m_dyn; ca.m_mul = m_mul; ca.tile_cfg = -1; ca.out_f32 = L.out_f32 ? 1 : 0;
         if (e->autotune) {
             const auto key = std::make_tuple(L.cout, L.cin, L.kh * 16 + L.kw, B_ * Ho * Wo, stride * 4 + out_mode * 2 + (res_ ? 1 : 0));
-            const int ksteps = L.kh * L.kw * L.cin / (prec_ == TD_PRECISION_FP16 ? 64 : 32);
-            const bool pp8_ok = prec_ == TD_PRECISION_FP16 && out_mode == 0 && L.cout >= 128;
-            const bool bd_ok = out_mode == 0 && L.w_frag != nullptr;
-            // persistent tile walk (tile ids 18-20): fp32 1x1 / stride-1 layers, same-size residual at most
-            const bool plane_ok = prec_ == TD_PRECISION_FP32 && L.kh == 1 && L.kw == 1 && stride == 1 && pad == 0 && out_mode == 0 && res_shift == 0 &&
-                                  !L.out_f32 && L.cin >= 32 && L.cin % 32 == 0;
-            auto direct = [&](int c) { return run_conv_raw(L, x_, B_, H_, W_, stride, pad, relu, y_, res_, res_shift, s_, prec_, m_dyn, m_mul, out_mode, c); };
+            auto direct = [&](int c) { ConvArgs a = ca; a.tile_cfg = c; return conv2d_launch(a, prec_, s_); };
             const bool wino_ok = prec_ == TD_PRECISION_FP32 && L.wino_u && e->wino_v && stride == 1 && pad == 1 && !res_ && out_mode == 0 &&
                                  (!m_dyn || ((H_ | W_) & 1) == 0) &&
                                  (size_t)16 * std::min<long long>((long long)B_ * ((H_ + 1) / 2) * ((W_ + 1) / 2), wino_slab_tiles(e, L)) *
@@ -1082,11 +1060,12 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
                 if (use_43 && !use_fold) {
                     const auto key43 = std::make_tuple(L.cout, L.cin, 1 * 16 + 1, (int)T43, 4 + 64);
                     auto w43 = [&](int c) { return run_wino43(L, x_, B_, H_, W_, relu, y_, s_, m_dyn, c); };
-                    if ((st2 = tuned_cfg(key43, prec_, L.cin / 32, false, true, false, s_, w43, &wino_cfg, nullptr)) < 0) return st2;
+                    if ((st2 = tuned_cfg(e, key43, prec_, wino43_plane_args(e, L, B_, H_, W_, m_dyn), s_, w43, &wino_cfg)) < 0) return st2;
                 }
-                if (use_wino && !use_43 && !e->wino_fused && (st2 = tuned_cfg(wkey, prec_, L.cin / 32, false, true, false, s_, wino, &wino_cfg, nullptr)) < 0) return st2;
+                if (use_wino && !use_43 && !e->wino_fused &&
+                    (st2 = tuned_cfg(e, wkey, prec_, wino_plane_args(e, L, x_, B_, H_, W_, T, 0, m_dyn, m_mul), s_, wino, &wino_cfg)) < 0) return st2;
             }
-            if (!use_wino && (st2 = tuned_cfg(key, prec_, ksteps, pp8_ok, plane_ok, bd_ok, s_, direct, &cfg, nullptr)) < 0) return st2;
+            if (!use_wino && (st2 = tuned_cfg(e, key, prec_, ca, s_, direct, &cfg)) < 0) return st2;
         }
         ProfScope ps(e, s_, m_dyn ? 7 : 0, m_dyn ? 0.0 : flops, m_dyn ? 0.0 : bytes);
         if (e->prof && !m_dyn) {          // category 8: FLOPs the MFMA pipe really executes
@@ -1111,6 +1090,7 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
         const bool fuse_head = head && e->fuse_head && !m_dyn && out_mode == 0 && !res_ && relu && L.cout == 256 && head->cin == 256 &&
                                head->kh == 1 && head->kw == 1 && head->cout <= 32 && head->out_f32 && !head->scale && conv_head_capable(cfg, prec_);
         if (head_fused) *head_fused = fuse_head;
+        ca.tile_cfg = cfg;
         if (fuse_head) {
             const double hflops = 2.0 * M * head->cout * L.cout, hbytes = 4.0 * M * head->cout + es * head->cout * L.cout;
             const double bytes_f = bytes - es * M * L.cout + hbytes;
@@ -1120,11 +1100,12 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
                 e->prof_launches[0] += 1;          // two layers of the reference in one launch: "launches" keeps counting layers
                 e->prof_bytes[0] += hbytes + es * M * L.cout;       // the unfused pair's algorithmic bytes (every tensor of every layer once)
             }
+            ca.head_w = head->w; ca.head_b = head->bias; ca.head_y = head_y; ca.head_n = head->cout;
             ClassScope cs(e, s_, cls, flops + hflops, bytes_f);
-            return run_conv_raw(L, x_, B_, H_, W_, stride, pad, relu, y_, res_, res_shift, s_, prec_, m_dyn, m_mul, out_mode, cfg, head, head_y);
+            return conv2d_launch(ca, prec_, s_);
         }
         ClassScope cs(e, s_, cls, m_dyn ? 0.0 : flops, m_dyn ? 0.0 : bytes);
-        return run_conv_raw(L, x_, B_, H_, W_, stride, pad, relu, y_, res_, res_shift, s_, prec_, m_dyn, m_mul, out_mode, cfg);
+        return conv2d_launch(ca, prec_, s_);
     };
     // The same 3x3 layer shape on several pyramid levels as ONE launch (conv_pp8_grouped_launch, fp16 engine): the FPN's output
     // convs, the RPN conv with its head. The small levels (p4-p6: 79 / 20 / 6 tiles of 256 rows) cannot fill 256 CUs on their own;
