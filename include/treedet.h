@@ -114,7 +114,11 @@ td_status td_engine_forward_phase(td_engine* e, int phase, const void* images, i
                                   const int32_t* hw_out, int B, int Hp, int Wp, void* stream, td_detections* out);
 /* Expose an internal activation of the last forward() for stage-wise parity tests: names
  * "stem","pool","res2".."res5","p2".."p6","rpn_logits","rpn_deltas","proposals","proposal_scores",
- * "proposal_count","pooled7","cls_logits","box_deltas","det_boxes_net","pooled14","mask_logits".
+ * "proposal_count","pooled7","cls_logits","box_deltas","det_boxes_net","pooled14","mask_logits"; of the proposal
+ * stage also "rpn_head2".."rpn_head6" ([B,h,w,15] float32 in both precisions: 3 logits, then 12 deltas per position),
+ * "rpn_cand_idx","rpn_cand_scores","rpn_cand_valid","rpn_cand_boxes" ([B,5,1024(,4)]), "rpn_keep" ([B,5,1024]) and
+ * "rpn_keep_count" ([B,5]). The "rpn_head*" pointers may be overwritten between phase 0 and phase 1 of
+ * td_engine_forward_phase (after phase 0 has completed on its stream): stage tests feed crafted heads that way.
  * dims is filled with up to 4 extents (0-padded); *elem_size with the element size in bytes. */
 td_status td_engine_tensor(td_engine* e, const char* name, void** dev_ptr, int64_t dims[4], int* elem_size);
 /* Copy that activation into a caller-owned device buffer of `bytes` bytes (asynchronous on `stream`). */

@@ -57,3 +57,20 @@ def conv2d_head_hip(x_nchw, w_oihw, bias, head_w, head_b, pad, tile_cfg):
     _lib.check(st, "td_conv2d_head_nhwc")
     torch.cuda.synchronize()
     return y.cpu().numpy().transpose(0, 3, 1, 2)
+
+
+class _DeviceArray:
+    """A raw device pointer dressed as a __cuda_array_interface__ object (what torch.as_tensor takes for a zero-copy view)."""
+
+    def __init__(self, ptr, shape, typestr):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2}
+
+
+def engine_tensor_view(eng, name):
+    """Zero-copy float32 torch view of an engine buffer (the raw pointer td_engine_tensor returns), for stage tests that
+    overwrite it between two phases: ``view.copy_(crafted)``. The engine owns the memory; use the view at once."""
+    import ctypes as C
+    ptr, dims, elem = C.c_void_p(), (C.c_int64 * 4)(), C.c_int()
+    _lib.check(eng.lib.td_engine_tensor(eng._h, name.encode(), C.byref(ptr), dims, C.byref(elem)), "td_engine_tensor")
+    assert elem.value == 4 and ptr.value, (name, elem.value)
+    return torch.as_tensor(_DeviceArray(ptr.value, [int(d) for d in dims if d > 0], "<f4"), device=torch.device("cuda", eng.device))

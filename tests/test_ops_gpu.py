@@ -43,6 +43,21 @@ def test_nms_index_order_bit_exact(n, thr, seed):
     assert np.array_equal(got, ref)
 
 
+@pytest.mark.parametrize("n", [5, 777, 1024, 1025, 3000])
+def test_nms_index_order_bit_exact_with_signed_zero_scores(n):
+    """Same family as above with scores that are mostly zeros of either sign: -0.0 == +0.0, so the order among them is
+    the index order (sort_boxes_kernel up to 1024 boxes, rank_sort_kernel beyond; both form their keys with float_to_key)."""
+    rng = np.random.default_rng(100 + n)
+    boxes = random_boxes(rng, n, span=800.0)
+    scores = np.where(rng.random(n) < 0.5, np.float32(0.0), np.float32(-0.0)).astype(np.float32)
+    some = rng.random(n) < 0.2
+    scores[some] = rng.standard_normal(int(some.sum())).astype(np.float32)
+    assert np.signbit(scores[scores == 0]).any() and not np.signbit(scores[scores == 0]).all()
+    got = nms_hip(boxes, scores, 0.5)
+    ref = R.nms(boxes, scores, 0.5)
+    assert np.array_equal(got, ref)
+
+
 def test_nms_ties_and_threshold_edge():
     # duplicated scores (ties → lower index first) and IoU exactly at the threshold (strict >, so both stay)
     boxes = np.array([[0, 0, 10, 10], [0, 0, 10, 10], [5, 0, 15, 10], [0, 0, 10, 10], [100, 100, 110, 110],

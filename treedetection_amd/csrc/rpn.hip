@@ -12,7 +12,8 @@
 namespace {
 
 __device__ __forceinline__ uint32_t float_to_key(float f) {
-    const uint32_t u = __float_as_uint(f);
+    uint32_t u = __float_as_uint(f);
+    if (u == 0x80000000u) u = 0u;                        // -0.0 == +0.0: one key, so that tie too goes to the lower index
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);   // larger float → larger key
 }
 __device__ __forceinline__ float key_to_float(uint32_t k) {
@@ -289,7 +290,9 @@ __global__ __launch_bounds__(TOPK_THREADS) void rpn_topk_decode_kernel(RpnLevels
             const float ax2 = __fadd_rn(sx, lv.base[level][a][2]), ay2 = __fadd_rn(sy, lv.base[level][a][3]);
             const float* d = head + (size_t)pos * RPN_HEAD_C + RPN_A + a * 4;
             decode_box(ax1, ay1, ax2, ay2, d[0], d[1], d[2], d[3], 1.f, 1.f, 1.f, 1.f, x1, y1, x2, y2);
-            const bool fin = isfinite(x1) && isfinite(y1) && isfinite(x2) && isfinite(y2) && isfinite(score);
+            // (fminf in decode_box's clamp returns the other operand for a NaN dw / dh where the oracle's minimum keeps the NaN)
+            const bool fin = isfinite(x1) && isfinite(y1) && isfinite(x2) && isfinite(y2) && isfinite(score) &&
+                             !isnan(d[2]) && !isnan(d[3]);
             const float ih = (float)valid.h[b], iw = (float)valid.w[b];
             x1 = fminf(fmaxf(x1, 0.f), iw);
             y1 = fminf(fmaxf(y1, 0.f), ih);
