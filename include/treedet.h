@@ -176,6 +176,19 @@ td_status td_resize_batch_u8(const uint8_t* const* src_tiles, int n, int h, int 
  * rounded to float32 once. */
 td_status td_resize_bilinear_f64(const double* src, int c, int h, int w, float* dst, int out_h, int out_w, int dst_pitch_px,
                                  int64_t dst_plane_stride, void* stream);
+/* The same step for 16-bit rasters that lie decoded in HBM (td_tiff_blocks_to_image_u16_dev, or uploaded whole): the rule of
+ * prediction.py:166-169 and the float resize in two launches per batch, no float64 tile crossing PCIe. raster: DEVICE uint16
+ * [height, width, c] (pixel-interleaved, c >= 3). windows: HOST int32 [n][8], one row per tile window of ONE common size (n <=
+ * 64) = {r0, c0, h, w, vy0, vy1, vx0, vx1}: the window's first row / column in the raster, its size, and the rows [vy0, vy1) /
+ * columns [vx0, vx1) of the window whose pixel centres lie inside the tile's bounds (rasterio.mask; everything else reads 0).
+ * Launch 1 writes band1_max[i] (DEVICE int32 [n]) = the maximum of file band 1 over the masked window; launch 2 picks bands
+ * (2, 1, 0), turns every tap x into 255 * x / 65535 in float64 (one multiplication, one IEEE division) where band1_max[i] > 255
+ * and into (double)x elsewhere, then interpolates exactly as td_resize_bilinear_f64 does. dst: DEVICE float32, written at
+ * dst[i * dst_image_stride + ch * dst_plane_stride + y * dst_pitch_px + x] for y < out_h, x < out_w (the caller zero-fills the
+ * padding). Bit-identical to td_resize_bilinear_f64 fed with numpy's `255.0 * bgr / 65535.0`. Asynchronous on `stream`. */
+td_status td_windows_u16_to_input(const uint16_t* raster, int height, int width, int c, const int32_t* windows, int n, int32_t* band1_max,
+                                  float* dst, int out_h, int out_w, int dst_pitch_px, int64_t dst_plane_stride, int64_t dst_image_stride,
+                                  void* stream);
 /* ResizeShortestEdge(800, 1333) output shape for an h x w tile (Appendix A item 2). */
 void td_resize_shape(int h, int w, int short_edge, int max_size, int* out_h, int* out_w);
 
@@ -337,6 +350,10 @@ int64_t td_tiff_inflate(const uint8_t* src, int64_t n, uint8_t* dst, int64_t cap
  * spp <= 4. Asynchronous on `stream`. */
 td_status td_tiff_blocks_to_image_dev(const uint8_t* blocks, int64_t block_cap, int block_w, int block_h, int blocks_across,
                                       int blocks_down, int spp, int predictor, uint8_t* image, int width, int height, void* stream);
+/* The same for two-byte samples: blocks hold little-endian uint16 (block_cap still counts BYTES), image is [height][width][spp]
+ * uint16 (DEVICE), and predictor 2 is undone per whole sample modulo 65536 (TIFF 6.0 section 14). spp <= 4. Asynchronous on `stream`. */
+td_status td_tiff_blocks_to_image_u16_dev(const uint8_t* blocks, int64_t block_cap, int block_w, int block_h, int blocks_across,
+                                          int blocks_down, int spp, int predictor, uint16_t* image, int width, int height, void* stream);
 /* ---- JPEG-in-TIFF (compression 7; jpeg_core.h, jpegcodec.cpp, jpegdecode.hip): sequential Huffman, 8-bit, grey or three components
  * (Y 1x1 / 2x1 / 2x2, chroma 1x1), restart intervals; the output equals the host reader's (Pillow's libjpeg: accurate integer IDCT, fancy
  * upsampling, its YCbCr → RGB) byte for byte. Everything else is unsupported and stays with the host reader. */

@@ -201,6 +201,13 @@ td_status td_resize_bilinear_f64(const double* src, int c, int h, int w, float* 
     return resize_bilinear_f64_launch(src, c, h, w, dst, out_h, out_w, dst_pitch_px, (long long)dst_plane_stride, static_cast<hipStream_t>(stream));
 }
 
+td_status td_windows_u16_to_input(const uint16_t* raster, int height, int width, int c, const int32_t* windows, int n, int32_t* band1_max,
+                                  float* dst, int out_h, int out_w, int dst_pitch_px, int64_t dst_plane_stride, int64_t dst_image_stride,
+                                  void* stream) {
+    return windows_u16_to_input_launch(raster, height, width, c, windows, n, band1_max, dst, out_h, out_w, dst_pitch_px,
+                                       (long long)dst_plane_stride, (long long)dst_image_stride, static_cast<hipStream_t>(stream));
+}
+
 void td_resize_shape(int h, int w, int short_edge, int max_size, int* out_h, int* out_w) {
     // detectron2 ResizeShortestEdge.get_output_shape (python doubles; int(x + 0.5)) — Appendix A item 2
     const double scale = (double)short_edge / (double)(h < w ? h : w);

@@ -502,11 +502,11 @@ td_status resize_tile_u8_launch(const uint8_t* src, int h, int w, int c, uint8_t
 // src = max(scale * (dst + 0.5) - 0.5, 0), i1 = (int)src, lambda1 = src - i1, lambda0 = 1 - lambda1, neighbour index
 // clamped at the border, value = h0 * (w0 * v00 + w1 * v01) + h1 * (w0 * v10 + w1 * v11) — one IEEE operation per step
 // (-ffp-contract=off), then ONE rounding to float32 (the reference's .astype("float32")). HBM-bound: 8 B in, 4 B out.
-__global__ __launch_bounds__(256) void resize_bilinear_f64_kernel(const double* __restrict__ src, int C, int h, int w, float* __restrict__ dst,
-                                                                   int out_h, int out_w, int dst_pitch, long long dst_plane) {
-    const int ox = blockIdx.x * blockDim.x + threadIdx.x;
-    const int oy = blockIdx.y;
-    if (ox >= out_w || oy >= out_h) return;
+// tap(c, y, x) → the float64 value of channel c at source pixel (y, x): the ONE statement of the interpolation, shared by the
+// float64 tiles and the 16-bit windows below.
+template <typename Tap>
+__device__ __forceinline__ void bilinear_f64_pixel(Tap tap, int C, int h, int w, float* __restrict__ dst, int out_h, int out_w, int dst_pitch,
+                                                   long long dst_plane, int ox, int oy) {
     const double sh = (double)h / (double)out_h, sw = (double)w / (double)out_w;
     double fy = sh * ((double)oy + 0.5) - 0.5;
     double fx = sw * ((double)ox + 0.5) - 0.5;
@@ -517,12 +517,68 @@ __global__ __launch_bounds__(256) void resize_bilinear_f64_kernel(const double* 
     const double h1 = fy - (double)y1, h0 = 1.0 - h1;
     const double w1 = fx - (double)x1, w0 = 1.0 - w1;
     for (int c = 0; c < C; ++c) {
-        const double* p = src + ((size_t)c * h + y1) * w + x1;
-        const double v00 = p[0], v01 = p[xp], v10 = p[(size_t)yp * w], v11 = p[(size_t)yp * w + xp];
+        const double v00 = tap(c, y1, x1), v01 = tap(c, y1, x1 + xp), v10 = tap(c, y1 + yp, x1), v11 = tap(c, y1 + yp, x1 + xp);
         const double top = __dadd_rn(__dmul_rn(w0, v00), __dmul_rn(w1, v01));
         const double bot = __dadd_rn(__dmul_rn(w0, v10), __dmul_rn(w1, v11));
         dst[(size_t)c * dst_plane + (size_t)oy * dst_pitch + ox] = (float)__dadd_rn(__dmul_rn(h0, top), __dmul_rn(h1, bot));
     }
+}
+
+__global__ __launch_bounds__(256) void resize_bilinear_f64_kernel(const double* __restrict__ src, int C, int h, int w, float* __restrict__ dst,
+                                                                   int out_h, int out_w, int dst_pitch, long long dst_plane) {
+    const int ox = blockIdx.x * blockDim.x + threadIdx.x;
+    const int oy = blockIdx.y;
+    if (ox >= out_w || oy >= out_h) return;
+    bilinear_f64_pixel([&](int c, int y, int x) { return src[((size_t)c * h + y) * w + x]; }, C, h, w, dst, out_h, out_w, dst_pitch, dst_plane, ox, oy);
+}
+
+// ---- 16-bit rasters kept in HBM: tile windows → the engine's float32 CHW input ----------------------------------------
+// The reference's rule for 16-bit orthophotos (prediction.py:166-169): a tile whose file band 1 exceeds 255 somewhere becomes
+// 255 * x / 65535 in float64, every other tile stays as it is; then the float resize above. Two launches per batch of
+// windows of one size, nothing crosses PCIe: the rule pass reduces band 1 of every masked window to its maximum (one int per
+// window), the resize pass reads the raster's uint16 samples (bands 2, 1, 0), applies the rule per tap — 255 * x is exact and
+// the division is IEEE's, so the value is numpy's `255.0 * bgr / 65535.0` bit for bit — and interpolates. A window comes with
+// the rectangle rasterio.mask keeps (pixel centres inside the tile's bounds); taps outside it read 0. HBM-bound: the rule
+// pass reads 2 B per window pixel (in 2 C-byte strides), the resize pass reads <= 4 x 6 B (neighbouring lanes share them)
+// and writes 12 B per output pixel.
+struct WindowTable {          // the windows of one batch, passed by value: {r0, c0, vy0, vy1, vx0, vx1} (valid: rows / columns inside the window)
+    int v[TD_MAX_BATCH][6];
+};
+
+__global__ __launch_bounds__(256) void windows_u16_band1_max_kernel(const uint16_t* __restrict__ raster, int W, int C, WindowTable win,
+                                                                    int* __restrict__ band1_max) {
+    const int b = blockIdx.y;
+    const int r0 = win.v[b][0], c0 = win.v[b][1], vy0 = win.v[b][2], vy1 = win.v[b][3], vx0 = win.v[b][4], vx1 = win.v[b][5];
+    const int vw = vx1 - vx0;
+    const long long total = (long long)(vy1 - vy0) * vw;
+    int m = 0;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const int y = (int)(i / vw), x = (int)(i - (long long)y * vw);
+        const int v = raster[((size_t)(r0 + vy0 + y) * W + (c0 + vx0 + x)) * C + 1];
+        m = v > m ? v : m;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const int o = __shfl_xor(m, d);
+        m = o > m ? o : m;
+    }
+    if ((threadIdx.x & 63) == 0 && m > 0) atomicMax(band1_max + b, m);
+}
+
+__global__ __launch_bounds__(256) void windows_u16_resize_kernel(const uint16_t* __restrict__ raster, int W, int C, WindowTable win, int h, int w,
+                                                                 const int* __restrict__ band1_max, float* __restrict__ dst, int out_h, int out_w,
+                                                                 int dst_pitch, long long dst_plane, long long dst_image) {
+    const int ox = blockIdx.x * blockDim.x + threadIdx.x;
+    const int oy = blockIdx.y, b = blockIdx.z;
+    if (ox >= out_w || oy >= out_h) return;
+    const int r0 = win.v[b][0], c0 = win.v[b][1], vy0 = win.v[b][2], vy1 = win.v[b][3], vx0 = win.v[b][4], vx1 = win.v[b][5];
+    const bool rescale = band1_max[b] > 255;
+    auto tap = [&](int c, int y, int x) {
+        const bool inside = y >= vy0 && y < vy1 && x >= vx0 && x < vx1;
+        const double v = inside ? (double)raster[((size_t)(r0 + y) * W + (c0 + x)) * C + (2 - c)] : 0.0;
+        return rescale ? __ddiv_rn(__dmul_rn(255.0, v), 65535.0) : v;
+    };
+    bilinear_f64_pixel(tap, 3, h, w, dst + (size_t)b * dst_image, out_h, out_w, dst_pitch, dst_plane, ox, oy);
 }
 
 td_status resize_bilinear_f64_launch(const double* src, int c, int h, int w, float* dst, int out_h, int out_w, int dst_pitch,
@@ -531,6 +587,36 @@ td_status resize_bilinear_f64_launch(const double* src, int c, int h, int w, flo
                "resize_bilinear_f64: bad geometry (%d x %d x %d -> %d x %d, pitch %d)", c, h, w, out_h, out_w, dst_pitch);
     hipLaunchKernelGGL(resize_bilinear_f64_kernel, dim3(td_cdiv(out_w, 256), out_h), dim3(256), 0, stream, src, c, h, w, dst, out_h, out_w,
                        dst_pitch, dst_plane);
+    TD_KERNEL_CHECK();
+    return TD_OK;
+}
+
+td_status windows_u16_to_input_launch(const uint16_t* raster, int H, int W, int C, const int32_t* windows, int n, int* band1_max, float* dst,
+                                      int out_h, int out_w, int dst_pitch, long long dst_plane, long long dst_image, hipStream_t stream) {
+    TD_REQUIRE(raster && windows && band1_max && dst, "windows_u16_to_input: null pointer");
+    TD_REQUIRE(n >= 1 && n <= TD_MAX_BATCH && H >= 1 && W >= 1 && C >= 3, "windows_u16_to_input: %d windows of a %d x %d x %d raster", n, H, W, C);
+    const int h = windows[2], w = windows[3];
+    TD_REQUIRE(h >= 1 && w >= 1 && out_h >= 1 && out_w >= 1 && dst_pitch >= out_w && dst_plane >= (long long)out_h * dst_pitch && dst_image >= 3 * dst_plane,
+               "windows_u16_to_input: bad geometry (%d x %d -> %d x %d, pitch %d)", h, w, out_h, out_w, dst_pitch);
+    WindowTable t{};
+    long long most = 1;
+    for (int i = 0; i < n; ++i) {
+        const int32_t* q = windows + 8 * i;      // {r0, c0, h, w, valid y0, y1, x0, x1}
+        TD_REQUIRE(q[2] == h && q[3] == w, "windows_u16_to_input: window %d is %d x %d, the first one %d x %d (one size per call)", i, q[2], q[3], h, w);
+        TD_REQUIRE(q[0] >= 0 && q[1] >= 0 && (long long)q[0] + h <= H && (long long)q[1] + w <= W,
+                   "windows_u16_to_input: window %d (%d, %d, %d x %d) leaves the %d x %d raster", i, q[0], q[1], h, w, H, W);
+        TD_REQUIRE(q[4] >= 0 && q[4] <= q[5] && q[5] <= h && q[6] >= 0 && q[6] <= q[7] && q[7] <= w,
+                   "windows_u16_to_input: window %d: valid rectangle rows %d..%d, columns %d..%d outside %d x %d", i, q[4], q[5], q[6], q[7], h, w);
+        t.v[i][0] = q[0], t.v[i][1] = q[1], t.v[i][2] = q[4], t.v[i][3] = q[5], t.v[i][4] = q[6], t.v[i][5] = q[7];
+        const long long px = (long long)(q[5] - q[4]) * (q[7] - q[6]);
+        most = px > most ? px : most;
+    }
+    TD_HIP_CHECK(hipMemsetAsync(band1_max, 0, (size_t)n * sizeof(int), stream));
+    const int groups = (int)((most + 256 * 8 - 1) / (256 * 8));       // eight pixels per thread
+    hipLaunchKernelGGL(windows_u16_band1_max_kernel, dim3(groups < 1024 ? groups : 1024, n), dim3(256), 0, stream, raster, W, C, t, band1_max);
+    TD_KERNEL_CHECK();
+    hipLaunchKernelGGL(windows_u16_resize_kernel, dim3(td_cdiv(out_w, 256), out_h, n), dim3(256), 0, stream, raster, W, C, t, h, w, band1_max, dst,
+                       out_h, out_w, dst_pitch, dst_plane, dst_image);
     TD_KERNEL_CHECK();
     return TD_OK;
 }

@@ -361,22 +361,24 @@ __global__ __launch_bounds__(64 * WPB) void tiff_inflate_blocks_kernel(const uin
     }
 }
 
-// Decoded blocks → the raster [height][width][spp] (uint8, pixel-interleaved), undoing predictor 2 (TIFF 6.0 section 14:
-// each sample is the difference to the same sample of the pixel on its left, within the row of its block) on the way. One
+// Decoded blocks → the raster [height][width][spp] (pixel-interleaved samples of type T: uint8, or uint16 in the GPU's own
+// little-endian order), undoing predictor 2 (TIFF 6.0 section 14: each SAMPLE is the difference to the same sample of the
+// pixel on its left, within the row of its block — modulo 256 or 65536, which is T's own arithmetic) on the way. One
 // workgroup per (image row, block column): a block row of bw pixels is a prefix sum per sample — per-thread runs, a scan of
-// the 256 run totals in LDS, then the stores. HBM-bound: one read and one write of the raster.
+// the 256 run totals in LDS, then the stores. block_cap counts BYTES (a multiple of sizeof(T)). HBM-bound: one read and one
+// write of the raster (2 x spp x sizeof(T) bytes per pixel).
 constexpr int SC_THREADS = 256, SC_MAX_SPP = 4;
-template <int spp>
+template <typename T, int spp>
 __global__ __launch_bounds__(SC_THREADS) void tiff_blocks_to_image_kernel(const uint8_t* __restrict__ blocks, int64_t block_cap, int bw, int bh,
                                                                           int blocks_across, int predictor,
-                                                                          uint8_t* __restrict__ image, int width, int height) {
-    __shared__ uint8_t tot[SC_THREADS][SC_MAX_SPP];
+                                                                          T* __restrict__ image, int width, int height) {
+    __shared__ T tot[SC_THREADS][SC_MAX_SPP];
     const int y = blockIdx.x, bx = blockIdx.y, tid = threadIdx.x;
     const int by = y / bh;
-    const uint8_t* src = blocks + ((int64_t)by * blocks_across + bx) * block_cap + (int64_t)(y - by * bh) * bw * spp;
+    const T* src = reinterpret_cast<const T*>(blocks + ((int64_t)by * blocks_across + bx) * block_cap) + (int64_t)(y - by * bh) * bw * spp;
     const int x0 = bx * bw;
     const int valid = min(bw, width - x0);                 // pixels of this block row that lie inside the raster
-    uint8_t* dst = image + ((int64_t)y * width + x0) * spp;
+    T* dst = image + ((int64_t)y * width + x0) * spp;
     const int per = (bw + SC_THREADS - 1) / SC_THREADS;    // pixels per thread (contiguous run)
     const int p0 = tid * per, p1 = min(p0 + per, bw);
     if (predictor != 2) {
@@ -384,26 +386,26 @@ __global__ __launch_bounds__(SC_THREADS) void tiff_blocks_to_image_kernel(const 
             for (int c = 0; c < spp; ++c) dst[p * spp + c] = src[p * spp + c];
         return;
     }
-    uint8_t run[spp];
+    T run[spp];
 #pragma unroll
     for (int c = 0; c < spp; ++c) run[c] = 0;
     for (int p = p0; p < p1; ++p)
-        for (int c = 0; c < spp; ++c) run[c] = (uint8_t)(run[c] + src[p * spp + c]);
+        for (int c = 0; c < spp; ++c) run[c] = (T)(run[c] + src[p * spp + c]);
     for (int c = 0; c < spp; ++c) tot[tid][c] = run[c];
     __syncthreads();
     // inclusive scan of the run totals (Hillis-Steele over 256 entries, all samples at once)
     for (int off = 1; off < SC_THREADS; off <<= 1) {
-        uint8_t add[spp];
+        T add[spp];
         for (int c = 0; c < spp; ++c) add[c] = tid >= off ? tot[tid - off][c] : 0;
         __syncthreads();
-        for (int c = 0; c < spp; ++c) tot[tid][c] = (uint8_t)(tot[tid][c] + add[c]);
+        for (int c = 0; c < spp; ++c) tot[tid][c] = (T)(tot[tid][c] + add[c]);
         __syncthreads();
     }
-    uint8_t base[spp];
+    T base[spp];
     for (int c = 0; c < spp; ++c) base[c] = tid > 0 ? tot[tid - 1][c] : 0;
     for (int p = p0; p < p1; ++p)
         for (int c = 0; c < spp; ++c) {
-            base[c] = (uint8_t)(base[c] + src[p * spp + c]);
+            base[c] = (T)(base[c] + src[p * spp + c]);
             if (p < valid) dst[p * spp + c] = base[c];
         }
 }
@@ -555,29 +557,34 @@ extern "C" td_status td_tiff_inflate_dev(const uint8_t* comp, const int64_t* blo
     return TD_OK;
 }
 
-extern "C" td_status td_tiff_blocks_to_image_dev(const uint8_t* blocks, int64_t block_cap, int block_w, int block_h, int blocks_across,
-                                                 int blocks_down, int spp, int predictor, uint8_t* image, int width, int height,
-                                                 void* stream) {
-    TD_REQUIRE(blocks && image, "td_tiff_blocks_to_image_dev: null pointer");
-    TD_REQUIRE(block_w >= 1 && block_h >= 1 && blocks_across >= 1 && blocks_down >= 1 && width >= 1 && height >= 1,
-               "td_tiff_blocks_to_image_dev: bad geometry");
-    TD_REQUIRE(spp >= 1 && spp <= SC_MAX_SPP && (predictor == 1 || predictor == 2), "td_tiff_blocks_to_image_dev: %d samples per pixel, predictor %d",
-               spp, predictor);
-    TD_REQUIRE((int64_t)block_w * block_h * spp <= block_cap, "td_tiff_blocks_to_image_dev: a %d x %d x %d block does not fit %lld bytes", block_w,
+namespace {
+
+// the checks and the launch of both sample widths; `what` names the entry point in messages
+template <typename T>
+td_status blocks_to_image(const char* what, const uint8_t* blocks, int64_t block_cap, int block_w, int block_h, int blocks_across, int blocks_down,
+                          int spp, int predictor, T* image, int width, int height, void* stream) {
+    TD_REQUIRE(blocks && image, "%s: null pointer", what);
+    TD_REQUIRE(block_w >= 1 && block_h >= 1 && blocks_across >= 1 && blocks_down >= 1 && width >= 1 && height >= 1, "%s: bad geometry", what);
+    TD_REQUIRE(spp >= 1 && spp <= SC_MAX_SPP && (predictor == 1 || predictor == 2), "%s: %d samples per pixel, predictor %d", what, spp, predictor);
+    TD_REQUIRE((int64_t)block_w * block_h * spp * (int64_t)sizeof(T) <= block_cap, "%s: a %d x %d x %d block does not fit %lld bytes", what, block_w,
                block_h, spp, (long long)block_cap);
     TD_REQUIRE((int64_t)blocks_across * block_w >= width && (int64_t)blocks_down * block_h >= height && (int64_t)(blocks_across - 1) * block_w < width &&
-               (int64_t)(blocks_down - 1) * block_h < height, "td_tiff_blocks_to_image_dev: %d x %d blocks of %d x %d do not tile a %d x %d raster",
+               (int64_t)(blocks_down - 1) * block_h < height, "%s: %d x %d blocks of %d x %d do not tile a %d x %d raster", what,
                blocks_across, blocks_down, block_w, block_h, width, height);
-    TD_REQUIRE(blocks_across <= 65535, "td_tiff_blocks_to_image_dev: too many block columns");
+    TD_REQUIRE(blocks_across <= 65535, "%s: too many block columns", what);
+    TD_REQUIRE(block_cap % sizeof(T) == 0 && reinterpret_cast<uintptr_t>(blocks) % sizeof(T) == 0 && reinterpret_cast<uintptr_t>(image) % sizeof(T) == 0,
+               "%s: blocks, image and block_cap must be multiples of the sample size", what);
     const dim3 grid(height, blocks_across);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (spp == 4 && block_cap % 4 == 0 && reinterpret_cast<uintptr_t>(blocks) % 4 == 0 && reinterpret_cast<uintptr_t>(image) % 4 == 0) {
-        hipLaunchKernelGGL(tiff_blocks_to_image_rgbi_kernel, dim3((height + 3) / 4, blocks_across), dim3(256), 0, s, blocks, block_cap, block_w, block_h,
-                           blocks_across, predictor, image, width, height);
-        TD_KERNEL_CHECK();
-        return TD_OK;
+    if constexpr (sizeof(T) == 1) {
+        if (spp == 4 && block_cap % 4 == 0 && reinterpret_cast<uintptr_t>(blocks) % 4 == 0 && reinterpret_cast<uintptr_t>(image) % 4 == 0) {
+            hipLaunchKernelGGL(tiff_blocks_to_image_rgbi_kernel, dim3((height + 3) / 4, blocks_across), dim3(256), 0, s, blocks, block_cap, block_w,
+                               block_h, blocks_across, predictor, image, width, height);
+            TD_KERNEL_CHECK();
+            return TD_OK;
+        }
     }
-#define TD_SCATTER(N) hipLaunchKernelGGL(tiff_blocks_to_image_kernel<N>, grid, dim3(SC_THREADS), 0, s, blocks, block_cap, block_w, block_h, \
+#define TD_SCATTER(N) hipLaunchKernelGGL((tiff_blocks_to_image_kernel<T, N>), grid, dim3(SC_THREADS), 0, s, blocks, block_cap, block_w, block_h, \
                                          blocks_across, predictor, image, width, height)
     switch (spp) {
         case 1: TD_SCATTER(1); break;
@@ -588,4 +595,20 @@ extern "C" td_status td_tiff_blocks_to_image_dev(const uint8_t* blocks, int64_t 
 #undef TD_SCATTER
     TD_KERNEL_CHECK();
     return TD_OK;
+}
+
+}  // namespace
+
+extern "C" td_status td_tiff_blocks_to_image_dev(const uint8_t* blocks, int64_t block_cap, int block_w, int block_h, int blocks_across,
+                                                 int blocks_down, int spp, int predictor, uint8_t* image, int width, int height,
+                                                 void* stream) {
+    return blocks_to_image<uint8_t>("td_tiff_blocks_to_image_dev", blocks, block_cap, block_w, block_h, blocks_across, blocks_down, spp, predictor,
+                                    image, width, height, stream);
+}
+
+extern "C" td_status td_tiff_blocks_to_image_u16_dev(const uint8_t* blocks, int64_t block_cap, int block_w, int block_h, int blocks_across,
+                                                     int blocks_down, int spp, int predictor, uint16_t* image, int width, int height,
+                                                     void* stream) {
+    return blocks_to_image<uint16_t>("td_tiff_blocks_to_image_u16_dev", blocks, block_cap, block_w, block_h, blocks_across, blocks_down, spp,
+                                     predictor, image, width, height, stream);
 }

@@ -236,6 +236,36 @@ class Engine:
                        "td_resize_bilinear_f64")
         return x, shapes
 
+    def preprocess_windows_u16(self, raster: torch.Tensor, windows):
+        """Tile windows of a 16-bit raster that lies in HBM (torch.uint16 [rows, cols, bands >= 3], band order of the file) →
+        (float32 [B,3,Hp,Wp] batch, hw_valid) exactly as the host path builds it — BGR pick, 255 * x / 65535 in float64 where
+        the window's band 1 exceeds 255 (reference prediction.py:166-167), float resize, zero padding — without a float64
+        tile crossing PCIe: td_windows_u16_to_input, one launch pair per group of windows of one size. ``windows``: (r0, c0, h,
+        w, mask) per tile, mask = GeoTiff.outside_mask's (columns, rows) to keep, or None."""
+        assert raster.is_cuda and raster.dtype == torch.uint16 and raster.is_contiguous() and raster.shape[2] >= 3
+        shapes = [self.resize_shape(h, w) for _, _, h, w, _ in windows]
+        Hp = _round_up(max(s[0] for s in shapes), 32)
+        Wp = _round_up(max(s[1] for s in shapes), 32)
+        dev = torch.device("cuda", self.device)
+        x = torch.zeros((len(windows), 3, Hp, Wp), dtype=torch.float32, device=dev)
+        flags = torch.empty((len(windows),), dtype=torch.int32, device=dev)      # max(band 1) per window, written by the rule pass
+        table = np.empty((len(windows), 8), dtype=np.int32)
+        for i, (r0, c0, h, w, mask) in enumerate(windows):
+            vy, vx = (0, h), (0, w)
+            if mask is not None:                                # pixel centres inside the bounds: one run of columns, one of rows
+                okx, oky = mask
+                vx = (int(np.argmax(okx)), int(np.argmax(okx)) + int(okx.sum())) if okx.any() else (0, 0)
+                vy = (int(np.argmax(oky)), int(np.argmax(oky)) + int(oky.sum())) if oky.any() else (0, 0)
+            table[i] = (r0, c0, h, w, *vy, *vx)
+        st = _lib.stream_ptr()
+        H, W, C_ = (int(v) for v in raster.shape)
+        one_size = len({(h, w) for _, _, h, w, _ in windows}) == 1      # the common case: one launch pair for the whole batch
+        for i0, n in ([(0, len(windows))] if one_size else [(i, 1) for i in range(len(windows))]):
+            oh, ow = shapes[i0]
+            _lib.check(self.lib.td_windows_u16_to_input(raster.data_ptr(), H, W, C_, table[i0:].ctypes.data, n, flags[i0:].data_ptr(),
+                                                        x[i0].data_ptr(), oh, ow, Wp, Hp * Wp, 3 * Hp * Wp, st), "td_windows_u16_to_input")
+        return x, shapes
+
     CONTOUR_MAX = 256         # TD_CONTOUR_MAX
 
     def alloc_contours(self, B: int, points_cap: int = 65536) -> Dict[str, torch.Tensor]:

@@ -7,8 +7,8 @@ DEFLATE (zlib) / LZW / PackBits (td_tiff_*_decode in libtreedet_hip.so), horizon
 three geo tags (ModelPixelScale / ModelTiepoint / GeoKeyDirectory). JPEG-in-TIFF (compression 7, 8-bit, one or three bands)
 is windowed too: a block's abbreviated stream + the JPEGTables tag form one JPEG stream, decoded by Pillow's libjpeg block by
 block (GDAL does the same through libtiff). Other codecs (old-style JPEG, floating-point predictor, ...): whole image through Pillow.
-Whole rasters can instead be decoded on the GPU and kept in HBM (``decode_to_device``): LZW and DEFLATE (tiffdecode.hip) and
-sequential-Huffman JPEG (jpegdecode.hip, byte-identical to the Pillow path) — see ``device_decodable``.
+Whole rasters can instead be decoded on the GPU and kept in HBM (``decode_to_device``): LZW and DEFLATE (tiffdecode.hip; uint8 and
+native-order uint16 samples) and sequential-Huffman JPEG (jpegdecode.hip, byte-identical to the Pillow path) — see ``device_decodable``.
 """
 from __future__ import annotations
 
@@ -356,18 +356,23 @@ class GeoTiff:
     # -- compressed raster → HBM (tiffdecode.hip) --------------------------------------------------------------------------
     def device_decodable(self) -> bool:
         """True when the raster's blocks can be decoded on the GPU: LZW or DEFLATE (zlib) strips or tiles of pixel-interleaved
-        uint8 samples (<= 4 per pixel), predictor 1 or 2; JPEG (compression 7) grey or three-band blocks when the host plan
-        (td_tiff_jpeg_plan: sequential Huffman, 8-bit, 4:4:4 / 4:2:2 / 4:2:0) accepts every one of them. Everything else keeps the
-        host reader."""
+        uint8 or native-order (little-endian) uint16 samples (<= 4 per pixel), predictor 1 or 2; JPEG (compression 7) grey or
+        three-band blocks when the host plan (td_tiff_jpeg_plan: sequential Huffman, 8-bit, 4:4:4 / 4:2:2 / 4:2:0) accepts every
+        one of them. Everything else keeps the host reader: big-endian and planar files, PackBits, int16 and float32 samples,
+        12-bit JPEG."""
         self._setup_blocks()
         if self.compression == 7:
             if not (hasattr(self, "_jpeg_tables") and self._counts is not None and self._pil is None and self._flat is None):
                 return False
             plan = self._jpeg_plan()
             return plan is not None and int(plan[1][:, 1].max()) <= self.JPEG_DEVICE_MAX_SEGMENT
-        return (self.compression in (5, 8, 32946) and self.planar == 1 and self.dtype == np.uint8 and 1 <= self.count <= 4
+        return (self.compression in (5, 8, 32946) and self.planar == 1 and self._device_samples() and 1 <= self.count <= 4
                 and self._predictor in (1, 2) and self._counts is not None and self._pil is None
-                and self._bw * self._bh * self.count < (1 << 31))
+                and self._bw * self._bh * self.count * self.dtype.itemsize < (1 << 31))
+
+    def _device_samples(self) -> bool:
+        """Sample types the device kernels take as they lie in the file: uint8, and uint16 in the host's (= the GPU's) byte order."""
+        return self.dtype == np.uint8 or (self.dtype.kind == "u" and self.dtype.itemsize == 2 and self.dtype.isnative)
 
     # One lane decodes one entropy-coded segment at ~1.1 MB/s (a 4096² raster in ONE block without restart markers: 4.0 s on the
     # device against 85 ms for the host reader; DESIGN.md §7): rasters with a larger segment stay with the host reader
@@ -409,8 +414,8 @@ class GeoTiff:
         """The whole raster decoded in HBM: the compressed blocks are read as they lie in the file (one pread of the span that
         holds them, into pinned memory), copied to the device once, decoded one wave per block (td_tiff_lzw_decode_dev /
         td_tiff_inflate_dev; JPEG: one lane per entropy-coded segment, td_tiff_jpeg_decode_dev, planned once by td_tiff_jpeg_plan) and
-        laid out as [height, width, bands] uint8 with predictor 2 undone (td_tiff_blocks_to_image_dev). → (image tensor,
-        check) where ``check()`` waits for the kernels and raises ValueError when a block did not decode to its size (the
+        laid out as [height, width, bands] uint8 — or torch.uint16 for 16-bit rasters — with predictor 2 undone
+        (td_tiff_blocks_to_image_dev / td_tiff_blocks_to_image_u16_dev). → (image tensor, check) where ``check()`` waits for the kernels and raises ValueError when a block did not decode to its size (the
         caller then falls back to the host reader). Everything is enqueued on ``stream`` (default: the current one). ``pinned``:
         a one-element list holding a pinned uint8 tensor to read the file into (grown and put back when too small — pinning
         hundreds of MB per image costs as much as reading them); ``pool``: threads the file read is spread over."""
@@ -454,8 +459,9 @@ class GeoTiff:
         finally:
             os.close(fd)
         buf[span:] = 0
-        block_cap = self._bw * self._bh * self.count
-        expect = np.array([self._block_rows(by) * self._bw * self.count for by in range(self._ny) for _ in range(self._nx)], dtype=np.int64)
+        item = self.dtype.itemsize                              # block sizes, capacities and what a block must decode to count BYTES
+        block_cap = self._bw * self._bh * self.count * item
+        expect = np.array([self._block_rows(by) * self._bw * self.count * item for by in range(self._ny) for _ in range(self._nx)], dtype=np.int64)
         ctx = torch.cuda.stream(stream) if stream is not None else _NullCtx()
         with torch.cuda.device(dev), ctx:
             st = _lib.stream_ptr()
@@ -471,9 +477,11 @@ class GeoTiff:
             fn, fname = (lib.td_tiff_lzw_decode_dev, "td_tiff_lzw_decode_dev") if self.compression == 5 else (lib.td_tiff_inflate_dev, "td_tiff_inflate_dev")
             _lib.check(fn(comp.data_ptr(), meta[0].data_ptr(), meta[1].data_ptr(), nb, blocks.data_ptr(), block_cap,
                           decoded.data_ptr(), status.data_ptr(), st), fname)
-            image = torch.empty((self.height, self.width, self.count), dtype=torch.uint8, device=dev)
-            _lib.check(lib.td_tiff_blocks_to_image_dev(blocks.data_ptr(), block_cap, self._bw, self._bh, self._nx, self._ny, self.count,
-                                                       self._predictor, image.data_ptr(), self.width, self.height, st), "td_tiff_blocks_to_image_dev")
+            image = torch.empty((self.height, self.width, self.count), dtype=torch.uint8 if item == 1 else torch.uint16, device=dev)
+            scatter, sname = ((lib.td_tiff_blocks_to_image_dev, "td_tiff_blocks_to_image_dev") if item == 1 else
+                              (lib.td_tiff_blocks_to_image_u16_dev, "td_tiff_blocks_to_image_u16_dev"))
+            _lib.check(scatter(blocks.data_ptr(), block_cap, self._bw, self._bh, self._nx, self._ny, self.count,
+                               self._predictor, image.data_ptr(), self.width, self.height, st), sname)
             k1.record()
             done = torch.cuda.Event()
             done.record()
@@ -547,27 +555,34 @@ class GeoTiff:
         return image, check
 
     def device_uploadable(self) -> bool:
-        """True when the raster's pixels lie in the file as ONE dense [rows, cols, bands] uint8 array (uncompressed contiguous
-        strips, pixel-interleaved): it can be copied to the GPU in large sequential pieces and its tile windows cut there."""
+        """True when the raster's pixels lie in the file as ONE dense [rows, cols, bands] array of uint8 or native-order uint16
+        samples (uncompressed contiguous strips, pixel-interleaved): it can be copied to the GPU in large sequential pieces and
+        its tile windows cut there. Big-endian, planar, int16 and float32 files keep the host reader."""
         self._setup_blocks()
-        return self._flat is not None and getattr(self, "_fd", None) is not None and self.dtype == np.uint8 and self._pil is None
+        if self._flat is None or self._pil is not None or not self._device_samples():
+            return False
+        if getattr(self, "_fd", None) is not None:
+            return True
+        # (the window reader keeps a descriptor for single-byte samples only: a 16-bit file is checked for its length here)
+        return self.dtype.itemsize == 2 and os.path.getsize(self.path) >= int(self._flat.offset) + self._flat.nbytes
 
     def upload_to_device(self, device, stream=None, staging=None, pool=None, piece: int = 4 << 20):
         """The whole uncompressed raster in HBM: the file's pixel bytes are read in large sequential pieces (pread of ``piece``
         bytes, several side by side on ``pool``) into pinned staging buffers and copied to the device as they arrive — per tile
         one memcpy of its bytes out of the page cache, no system call per window row and no per-batch H2D of windows later.
         ``staging``: list of >= 2 pinned uint8 tensors to rotate through (created here when None). → (image tensor [rows,
-        cols, bands] uint8, check) as :meth:`decode_to_device`."""
+        cols, bands] uint8 or torch.uint16, check) as :meth:`decode_to_device`."""
         import torch
         if not self.device_uploadable():
-            raise ValueError(f"{self.path}: not one dense uint8 array in the file")
+            raise ValueError(f"{self.path}: not one dense uint8 / uint16 array in the file")
         dev = torch.device(device)
-        total = self.height * self.width * self.count
+        total = self.height * self.width * self.count * self.dtype.itemsize        # bytes
         if staging is None:
             staging = [torch.empty((4 * piece,), dtype=torch.uint8, pin_memory=True) for _ in range(2)]
         cap = min(t.numel() for t in staging)
         ctx = torch.cuda.stream(stream) if stream is not None else _NullCtx()
-        fd, base = self._fd, self._flat_off
+        own_fd = getattr(self, "_fd", None) is None          # (the window reader keeps a descriptor for uint8 files only)
+        fd, base = os.open(self.path, os.O_RDONLY) if own_fd else self._fd, int(self._flat.offset)
 
         def read_into(view: memoryview, off: int) -> None:
             got = 0
@@ -577,32 +592,36 @@ class GeoTiff:
                     raise ValueError(f"{self.path}: file ends inside its pixel data")
                 got += n
 
-        with torch.cuda.device(dev), ctx:
-            image = torch.empty((self.height, self.width, self.count), dtype=torch.uint8, device=dev)
-            flat = image.view(-1)
-            events = [None] * len(staging)
-            k = 0
-            for o in range(0, total, cap):
-                n = min(cap, total - o)
-                buf = staging[k % len(staging)]
-                if events[k % len(staging)] is not None:
-                    events[k % len(staging)].synchronize()          # the copy that last used this staging buffer has finished
-                mv = memoryview(buf.numpy())
-                parts = [(p, min(piece, n - p)) for p in range(0, n, piece)]
+        try:
+            with torch.cuda.device(dev), ctx:
+                image = torch.empty((self.height, self.width, self.count), dtype=torch.uint8 if self.dtype.itemsize == 1 else torch.uint16, device=dev)
+                flat = image.view(-1).view(torch.uint8)
+                events = [None] * len(staging)
+                k = 0
+                for o in range(0, total, cap):
+                    n = min(cap, total - o)
+                    buf = staging[k % len(staging)]
+                    if events[k % len(staging)] is not None:
+                        events[k % len(staging)].synchronize()          # the copy that last used this staging buffer has finished
+                    mv = memoryview(buf.numpy())
+                    parts = [(p, min(piece, n - p)) for p in range(0, n, piece)]
 
-                def one(pr, mv=mv, o=o):
-                    read_into(mv[pr[0]:pr[0] + pr[1]], o + pr[0])
-                    return pr
-                # every piece goes to the device as soon as it (and the pieces before it) has been read: copies of a few MB keep
-                # the DMA queue short for the small result copies of the running forwards (64-MB copies delayed them by a millisecond)
-                for p0, pn in (pool.map(one, parts) if pool is not None and len(parts) > 1 else map(one, parts)):
-                    flat[o + p0:o + p0 + pn].copy_(buf[p0:p0 + pn], non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record()
-                events[k % len(staging)] = ev
-                k += 1
-            done = torch.cuda.Event(blocking=True)
-            done.record()
+                    def one(pr, mv=mv, o=o):
+                        read_into(mv[pr[0]:pr[0] + pr[1]], o + pr[0])
+                        return pr
+                    # every piece goes to the device as soon as it (and the pieces before it) has been read: copies of a few MB keep
+                    # the DMA queue short for the small result copies of the running forwards (64-MB copies delayed them by a millisecond)
+                    for p0, pn in (pool.map(one, parts) if pool is not None and len(parts) > 1 else map(one, parts)):
+                        flat[o + p0:o + p0 + pn].copy_(buf[p0:p0 + pn], non_blocking=True)
+                    ev = torch.cuda.Event()
+                    ev.record()
+                    events[k % len(staging)] = ev
+                    k += 1
+                done = torch.cuda.Event(blocking=True)
+                done.record()
+        finally:
+            if own_fd:
+                os.close(fd)
 
         def check():
             done.synchronize()

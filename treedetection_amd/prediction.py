@@ -380,8 +380,10 @@ class Predictor:
         """Starts, on a thread of its own, what the NEXT image needs before its first batch can be cut: an LZW, DEFLATE or JPEG raster's
         compressed blocks read into pinned memory, copied to the device and decoded there (GeoTiff.decode_to_device), or an uncompressed
         raster's bytes copied to the device in large sequential pieces (GeoTiff.upload_to_device) — while the current image
-        predicts. ``detection.walk_images`` calls it with the path after the one it submits. No-op for rasters the host reader
-        serves (PackBits, planar, 16-bit, JPEG blocks the device decoder does not take) and when ``device_decode`` is off."""
+        predicts. ``detection.walk_images`` calls it with the path after the one it submits. uint8 and little-endian uint16 rasters
+        qualify (a 16-bit raster stays in HBM as uint16 and its windows become the model's float input there:
+        Engine.preprocess_windows_u16). No-op for rasters the host reader serves (PackBits, planar and big-endian files, int16 and
+        float32 samples, JPEG blocks the device decoder does not take) and when ``device_decode`` is off."""
         if not self.device_decode or tifpath in self._rasters:
             return
         if self._raster_pool is None:
@@ -389,14 +391,14 @@ class Predictor:
         self._rasters[tifpath] = self._raster_pool.submit(self._decode_raster, tifpath)
 
     def _decode_raster(self, tifpath):
-        """→ the raster as a device tensor [rows, cols, bands] uint8, or None (not decodable on the device, or a block failed:
+        """→ the raster as a device tensor [rows, cols, bands] uint8 / uint16, or None (not decodable on the device, or a block failed:
         the host reader then serves the image and reports what is wrong with it, if anything)."""
         img = None
         try:
             img = GeoTiff(tifpath)
             decode = img.device_decodable()
             if not decode and not (self.device_upload and img.device_uploadable()
-                                   and img.height * img.width * img.count <= self.device_raster_max_bytes):
+                                   and img.height * img.width * img.count * img.dtype.itemsize <= self.device_raster_max_bytes):
                 return None
             if self._decode_stream is None:
                 # lowest priority: its own hardware queue, and the forwards' workgroups are served first (_lib.low_priority_stream)
@@ -420,7 +422,7 @@ class Predictor:
                 st["seconds"] += time.perf_counter() - t0
                 st["thread_cpu"] = st.get("thread_cpu", 0.0) + time.thread_time() - c0
                 st["compressed_bytes"] += check.compressed_bytes
-                st["decoded_bytes"] += image.numel()
+                st["decoded_bytes"] += image.numel() * image.element_size()
                 st["kernel_ms"] = st.get("kernel_ms", 0.0) + getattr(check, "kernel_ms", 0.0)
             return image
         except Exception as e:
@@ -474,7 +476,10 @@ class Predictor:
                     raise ValueError(f"tile has {img.count} bands, need >= 3")
                 info = {"orig_height": h, "orig_width": w, "height": h, "width": w,
                         "json_name": tile["json_name"], "tile_id": tile["tile_id"], "meta": tile["meta"]}
-                return {"devwin": (r0, c0, h, w, img.outside_mask(tile["bounds"], c0, r0, w, h))}, info
+                # uint8: the window is cut and resized as bytes; uint16: the rule of prediction.py:166-169 and the float resize read
+                # the raster in place (_to_model_input → Engine.preprocess_windows_u16)
+                kind = "devwin" if img.dtype == np.uint8 else "devwin16"
+                return {kind: (r0, c0, h, w, img.outside_mask(tile["bounds"], c0, r0, w, h))}, info
             if staging is not None and img.dtype == np.uint8:
                 hwc = img.read_bounds_hwc(tile["bounds"], out=staging, out_off=staging_off)
             else:
@@ -527,6 +532,11 @@ class Predictor:
                     tiles.append(d["u8"].to(self.device, non_blocking=True))
             images, hw_valid, hw_out = eng.preprocess_tiles_u8(tiles)
             return images, INPUT_U8_HWC, hw_valid, hw_out
+        if batch and all("devwin16" in b["data"] for b in batch):      # a 16-bit raster in HBM (one raster per batch: _start_single)
+            dev = batch[0]["raster"]
+            dev.record_stream(torch.cuda.current_stream())
+            x, shapes = eng.preprocess_windows_u16(dev, [b["data"]["devwin16"] for b in batch])
+            return x, INPUT_F32_CHW, shapes, [(b["orig_height"], b["orig_width"]) for b in batch]
         planes = []
         for b in batch:
             if "u8" in b["data"]:
@@ -628,7 +638,7 @@ class Predictor:
                     dropped.append(idx)
                 continue
             entry = {"data": data, **info}
-            if "devwin" in data:
+            if "devwin" in data or "devwin16" in data:
                 entry["raster"] = raster
             batch.append(entry)
         return batch
