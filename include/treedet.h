@@ -339,12 +339,34 @@ int64_t td_tiff_lzw_encode(const uint8_t* src, int64_t n, uint8_t* dst, int64_t 
 td_status td_tiff_lzw_decode_dev(const uint8_t* comp, const int64_t* block_off, const int64_t* block_nbytes, int nblocks,
                                  uint8_t* blocks_out, int64_t block_cap, int64_t* decoded, int32_t* status, void* stream);
 /* The same for DEFLATE blocks (TIFF compression 8 / 32946: zlib streams; inflate_core.h): status int32 [nblocks], decoded int64
- * [nblocks]; the Adler-32 trailer is not checked. */
+ * [nblocks]; the decoder stops at the end of the last DEFLATE block: the Adler-32 trailer is not checked (td_tiff_inflate_verified_dev
+ * checks it). */
 td_status td_tiff_inflate_dev(const uint8_t* comp, const int64_t* block_off, const int64_t* block_nbytes, int nblocks,
                               uint8_t* blocks_out, int64_t block_cap, int64_t* decoded, int32_t* status, void* stream);
+/* td_tiff_inflate_dev followed, on the same stream, by the check zlib ends with: every block that decoded with status 0 is summed
+ * (Adler-32 over its decoded[b] bytes in blocks_out, before any predictor is undone) and compared with the big-endian trailer that
+ * follows its last DEFLATE block in comp. status: 0 / 1 / 2 as above, 3 = the sums differ or the stream ends before its trailer. The
+ * decoder also applies zlib's rules where td_tiff_inflate_dev is laxer (window size in the header, incomplete code sets), so that a
+ * block has status 0 exactly when zlib accepts its stream and it fits block_cap. end_off: DEVICE int64 [nblocks] scratch — where each
+ * block's trailer begins, from the start of its stream (not block_nbytes - 4: a byte count may include padding). */
+td_status td_tiff_inflate_verified_dev(const uint8_t* comp, const int64_t* block_off, const int64_t* block_nbytes, int nblocks,
+                                       uint8_t* blocks_out, int64_t block_cap, int64_t* decoded, int32_t* status, int64_t* end_off,
+                                       void* stream);
+/* The second launch of td_tiff_inflate_verified_dev alone (measurements: tools/raster_decode_bench.py): one workgroup per block sums
+ * blocks[b * block_cap .. + decoded[b]) of the blocks whose status is 0 and writes status 3 where the trailer at
+ * comp[block_off[b] + end_off[b]] differs or would lie beyond block_nbytes[b]. */
+td_status td_tiff_adler32_blocks_dev(const uint8_t* blocks, int64_t block_cap, const int64_t* decoded, const uint8_t* comp,
+                                     const int64_t* block_off, const int64_t* block_nbytes, const int64_t* end_off, int nblocks,
+                                     int32_t* status, void* stream);
+/* The same kernel over one DEVICE buffer of n < 2^31 bytes: its Adler-32 (zlib.adler32's value) → out_dev[0]. Asynchronous on `stream`. */
+td_status td_adler32_dev(const uint8_t* data_dev, int64_t n, uint32_t* out_dev, void* stream);
 /* The decoder td_tiff_inflate_dev runs, instantiated for one lane on the host (parity tests against zlib without a GPU): one zlib
  * stream → dst; returns the bytes produced or a negative status (TD_ERR_INVALID corrupt stream, TD_ERR_CAPACITY). */
 int64_t td_tiff_inflate(const uint8_t* src, int64_t n, uint8_t* dst, int64_t cap);
+/* The decoder and the rules of td_tiff_inflate_verified_dev on the host: zlib's header and code-set rules, then the Adler-32 trailer
+ * after the last DEFLATE block (bytes behind it are ignored, as zlib leaves them unused). Accepts exactly the streams zlib's inflate
+ * accepts; TD_ERR_INVALID for a corrupt stream, a wrong checksum or a missing trailer, TD_ERR_CAPACITY. */
+int64_t td_tiff_inflate_verified(const uint8_t* src, int64_t n, uint8_t* dst, int64_t cap);
 /* Decoded blocks (strips: block_w = width; tiles: full padded tiles, row-major grid blocks_across x blocks_down) → the raster
  * image [height][width][spp] uint8 (DEVICE), predictor 2 undone per block row on the way (td_tiff_unpredict's arithmetic).
  * spp <= 4. Asynchronous on `stream`. */

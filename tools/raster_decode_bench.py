@@ -5,7 +5,9 @@ JPEG (three bands, predictor ignored): [quality=90] [subsampling=2 (4:2:0) | 1 (
 both give the same bytes.
 Raster side x side x 4 uint8 (default 9000: the 400 windows of 450 x 450 px the reference cuts from one image, twice over); prints per
 call file → pinned → device → decoded raster in HBM, and the kernels alone (HIP events). Under rocprofv3 --kernel-trace --stats the
-per-kernel durations land in profiles/r06_decode_kernel_stats.csv."""
+per-kernel durations land in profiles/r06_decode_kernel_stats.csv.
+DEFLATE: the blocks' Adler-32 check is a launch of its own behind the inflate kernel; "inflate_ms" and "checksum_ms" time the two
+separately (HIP events around td_tiff_inflate_dev and around td_tiff_adler32_blocks_dev, the raster's blocks already on the device)."""
 import json
 import os
 import sys
@@ -68,6 +70,42 @@ try:
             assert np.array_equal(got.cpu().numpy().transpose(2, 0, 1), img), "decoded raster differs from what was written"
         del image, got
     extra = {}
+    if codec == "deflate":
+        # the two launches of td_tiff_inflate_verified_dev apart: the decoder alone, then the checksum launch alone over its output
+        from treedetection_amd import _lib
+        lib = _lib.load()
+        offs, cnts = np.asarray(g._offs, dtype=np.int64), np.asarray(g._counts, dtype=np.int64)
+        lo, nb = int(offs.min()), g._nx * g._ny
+        span = int((offs + cnts).max()) - lo
+        cap = g._bw * g._bh * g.count * g.dtype.itemsize
+        comp = torch.zeros((span + 16,), dtype=torch.uint8)
+        comp[:span] = torch.from_numpy(np.fromfile(path, dtype=np.uint8, count=span, offset=lo))
+        comp = comp.cuda()
+        meta = torch.from_numpy(np.stack([offs - lo, cnts])).cuda()
+        blocks = torch.empty((nb, cap), dtype=torch.uint8, device="cuda")
+        dec = torch.empty((nb,), dtype=torch.int64, device="cuda")
+        ends = torch.empty((nb,), dtype=torch.int64, device="cuda")
+        status = torch.empty((nb,), dtype=torch.int32, device="cuda")
+        head = (comp.data_ptr(), meta[0].data_ptr(), meta[1].data_ptr(), nb, blocks.data_ptr(), cap, dec.data_ptr(), status.data_ptr())
+        sp = _lib.stream_ptr()
+        _lib.check(lib.td_tiff_inflate_verified_dev(*head, ends.data_ptr(), sp), "td_tiff_inflate_verified_dev")
+        assert int((status != 0).sum()) == 0, "a block failed its checksum"
+
+        def timed(fn):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            _lib.check(fn(), "launch")
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1)
+        inflate_ms = [timed(lambda: lib.td_tiff_inflate_dev(*head, sp)) for _ in range(5)]
+        verified_ms = [timed(lambda: lib.td_tiff_inflate_verified_dev(*head, ends.data_ptr(), sp)) for _ in range(5)]
+        checksum_ms = [timed(lambda: lib.td_tiff_adler32_blocks_dev(blocks.data_ptr(), cap, dec.data_ptr(), comp.data_ptr(), meta[0].data_ptr(),
+                                                                    meta[1].data_ptr(), ends.data_ptr(), nb, status.data_ptr(), sp)) for _ in range(5)]
+        assert int((status != 0).sum()) == 0
+        extra = {"inflate_ms": [round(t, 3) for t in inflate_ms], "inflate_verified_ms": [round(t, 3) for t in verified_ms],
+                 "checksum_ms": [round(t, 3) for t in checksum_ms], "checksum_share_of_inflate": min(checksum_ms) / min(inflate_ms)}
+        del comp, meta, blocks, dec, ends, status
     if codec == "jpeg":
         # the host reader on the same raster: every block through GeoTiff._decode_block (Pillow's libjpeg) on host_threads threads
         nth = int(args.get("host_threads", 16))

@@ -55,10 +55,13 @@ struct InflateScratchT {                 // LDS on the device (RING + 4.6 KB), a
 };
 using InflateScratch = InflateScratchT<INF_WINDOW>;
 
-// status: 0 ok, 1 corrupt stream, 2 more bytes than the block holds
+// status: 0 ok, 1 corrupt stream, 2 more bytes than the block holds. end: offset in the stream of the first byte after the final
+// DEFLATE block (the bit after its end-of-block symbol, rounded up to a byte) — where zlib reads the Adler-32 trailer; valid for
+// status 0 and 2, always <= n. (Not n - 4: a strip's byte count may include padding.)
 struct InflateResult {
     uint32_t produced;
     int status;
+    uint32_t end;
 };
 
 namespace inflate_detail {
@@ -123,16 +126,20 @@ TD_INF_HD uint32_t reverse_bits(uint32_t v, int n) {
 }
 
 // canonical Huffman tables from code lengths lens[0..n): counts per length, symbols in canonical order, the fast lookup.
-// Returns false for an over-subscribed set (an incomplete one is allowed only for a single distance code, as zlib allows).
-TD_INF_HD bool build(const uint8_t* lens, int n, uint16_t* count, uint16_t* sym, uint16_t* fast, int fast_bits) {
+// Returns false for an over-subscribed set. complete: 0 = an incomplete set is accepted (its unused codes fail when they are met);
+// 1 / 2 = zlib's rule (inftrees.c) for the literal / length and distance sets / for the code-length code: an incomplete set is refused,
+// except a set of no codes at all (it fails at the first symbol) and, for 1, a single code of one bit.
+TD_INF_HD bool build(const uint8_t* lens, int n, uint16_t* count, uint16_t* sym, uint16_t* fast, int fast_bits, int complete = 0) {
     for (int l = 0; l < 16; ++l) count[l] = 0;
     for (int s = 0; s < n; ++s) ++count[lens[s]];
-    int left = 1;
+    int left = 1, longest = 0;
     for (int l = 1; l < 16; ++l) {
         left <<= 1;
         left -= count[l];
         if (left < 0) return false;
+        if (count[l]) longest = l;
     }
+    if (complete && left > 0 && longest != 0 && (complete == 2 || longest != 1)) return false;
     uint16_t offs[16];
     offs[1] = 0;
     for (int l = 1; l < 15; ++l) offs[l + 1] = (uint16_t)(offs[l] + count[l]);
@@ -184,8 +191,10 @@ TD_INF_HD int decode_sym(Scratch& S, Reader& r, const uint16_t* fast, int fast_b
 }  // namespace inflate_detail
 
 // src: the zlib stream (n bytes); dst: the block's output (cap bytes); every lane of the wave calls this with its lane id
-// (host: NL = 1, lane = 0). The result is the same on every lane.
-template <int NL, int RING>
+// (host: NL = 1, lane = 0). The result is the same on every lane. ZLIB_RULES: refuse what zlib's inflate refuses before the trailer and
+// this decoder otherwise lets pass — a window size beyond 32 KB in the header (CINFO > 7), incomplete code sets — so that a caller
+// which then checks the Adler-32 trailer at `end` (inflate_trailer_ok) accepts exactly the streams zlib accepts.
+template <int NL, int RING, bool ZLIB_RULES = false>
 TD_INF_HD TD_INF_INLINE InflateResult inflate_block(InflateScratchT<RING>& S, const uint8_t* src, int64_t n, uint8_t* dst, uint32_t cap, int lane) {
     using namespace inflate_detail;
     // length / distance codes: base value | extra bits << 16 (dwords: a scalar load on the device; byte tables would be per-lane loads)
@@ -197,7 +206,8 @@ TD_INF_HD TD_INF_INLINE InflateResult inflate_block(InflateScratchT<RING>& S, co
                                         1025 | 9 << 16, 1537 | 9 << 16, 2049 | 10 << 16, 3073 | 10 << 16, 4097 | 11 << 16, 6145 | 11 << 16, 8193 | 12 << 16,
                                         12289 | 12 << 16, 16385 | 13 << 16, 24577 | 13 << 16};
     constexpr uint8_t ORDER[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-    InflateResult res{0, 1};
+    InflateResult res{0, 1, 0};
+    constexpr int CODES = ZLIB_RULES ? 2 : 0, LENS = ZLIB_RULES ? 1 : 0;
     if (n < 6) return res;                                  // header + at least an empty block + trailer
     const uintptr_t a0 = reinterpret_cast<uintptr_t>(src);
     const uint32_t skip = (uint32_t)(a0 & 3);
@@ -209,6 +219,7 @@ TD_INF_HD TD_INF_INLINE InflateResult inflate_block(InflateScratchT<RING>& S, co
     ensure<NL>(S, r, 16, lane);
     const uint32_t cmf = take(r, 8), flg = take(r, 8);
     if ((cmf & 15) != 8 || ((cmf << 8) | flg) % 31 != 0 || (flg & 32)) return res;      // not deflate / bad check / preset dictionary
+    if (ZLIB_RULES && (cmf >> 4) > 7) return res;           // a window of more than 32 KB
     uint32_t op = 0;
     for (;;) {
         ensure<NL>(S, r, 3, lane);
@@ -238,7 +249,7 @@ TD_INF_HD TD_INF_INLINE InflateResult inflate_block(InflateScratchT<RING>& S, co
             if (type == 1) {                                // fixed codes
                 if (lane == 0) {
                     for (int s = 0; s < 288; ++s) S.lens[s] = s < 144 ? 8 : (s < 256 ? 9 : (s < 280 ? 7 : 8));
-                    ok = build(S.lens, 288, S.lit_count, S.lit_sym, S.lit_fast, INF_LIT_FAST);
+                    ok = build(S.lens, 288, S.lit_count, S.lit_sym, S.lit_fast, INF_LIT_FAST);            // (complete)
                     for (int s = 0; s < 30; ++s) S.lens[s] = 5;
                     ok = ok && build(S.lens, 30, S.dist_count, S.dist_sym, S.dist_fast, INF_DIST_FAST);
                 }
@@ -255,7 +266,7 @@ TD_INF_HD TD_INF_INLINE InflateResult inflate_block(InflateScratchT<RING>& S, co
                 TD_INF_SYNC();
                 if (lane == 0) {
                     for (int i = 0; i < 19; ++i) S.lens[i] = cl[i];
-                    ok = build(S.lens, 19, S.lit_count, S.lit_sym, S.lit_fast, 7);       // (the code-length code uses the literal table's arrays for a moment)
+                    ok = build(S.lens, 19, S.lit_count, S.lit_sym, S.lit_fast, 7, CODES);       // (the code-length code uses the literal table's arrays for a moment)
                 }
                 TD_INF_SYNC();
 #ifdef __HIP_DEVICE_COMPILE__
@@ -294,8 +305,8 @@ TD_INF_HD TD_INF_INLINE InflateResult inflate_block(InflateScratchT<RING>& S, co
                 TD_INF_SYNC();
                 if (lane == 0) {
                     ok = L[256] != 0;                        // no end-of-block code
-                    ok = ok && build(L, hlit, S.lit_count, S.lit_sym, S.lit_fast, INF_LIT_FAST);
-                    ok = ok && build(L + hlit, hdist, S.dist_count, S.dist_sym, S.dist_fast, INF_DIST_FAST);
+                    ok = ok && build(L, hlit, S.lit_count, S.lit_sym, S.lit_fast, INF_LIT_FAST, LENS);
+                    ok = ok && build(L + hlit, hdist, S.dist_count, S.dist_sym, S.dist_fast, INF_DIST_FAST, LENS);
                 }
             }
             TD_INF_SYNC();
@@ -426,7 +437,16 @@ TD_INF_HD TD_INF_INLINE InflateResult inflate_block(InflateScratchT<RING>& S, co
         }
         if (last) break;
     }
+    if (bitpos(r) > r.end_bit) return res;                  // (the final block's last bits lie inside the stream)
     res.produced = op;
     res.status = op > cap ? 2 : 0;
+    res.end = ((bitpos(r) + 7u) >> 3) - skip;
     return res;
+}
+
+// zlib's last step: the four bytes at `end` are the Adler-32 of the output, big-endian; a stream that ends before them is incomplete
+TD_INF_HD bool inflate_trailer_ok(const uint8_t* src, int64_t n, uint32_t end, uint32_t adler) {
+    if ((int64_t)end + 4 > n) return false;
+    const uint8_t* t = src + end;
+    return (((uint32_t)t[0] << 24) | ((uint32_t)t[1] << 16) | ((uint32_t)t[2] << 8) | (uint32_t)t[3]) == adler;
 }

@@ -5,6 +5,7 @@
 // Pure host code; called from the reader's decode threads with the GIL released.
 #include "common.h"
 
+#include <algorithm>
 #include <cstring>
 
 // TIFF LZW: MSB-first variable-width codes (9..12 bits), ClearCode 256, EndOfInformation 257, first free code 258,
@@ -166,11 +167,16 @@ extern "C" int64_t td_tiff_lzw_encode(const uint8_t* src, int64_t n, uint8_t* ds
 
 // DEFLATE in a zlib wrapper (TIFF compression 8 / 32946): the decoder the GPU runs (inflate_core.h, one wave per block), instantiated
 // for ONE lane — the same source on the host, so its parity with zlib is tested without a GPU (tests/test_geotiff_formats.py). The
-// tile reader itself keeps Python's zlib for DEFLATE blocks (it also checks the Adler-32 trailer, which this decoder skips).
+// tile reader itself keeps Python's zlib for DEFLATE blocks. td_tiff_inflate stops at the end of the last DEFLATE block, as
+// td_tiff_inflate_dev does; td_tiff_inflate_verified goes on as zlib does: zlib's rules for the header and the code sets, then the
+// Adler-32 trailer that follows the last block (td_tiff_inflate_verified_dev: the same on the GPU).
 #include "inflate_core.h"
-extern "C" int64_t td_tiff_inflate(const uint8_t* src, int64_t n, uint8_t* dst, int64_t cap) {
+namespace {
+// → bytes produced or a negative status; `end` = where the trailer begins
+template <bool ZLIB_RULES>
+int64_t inflate_host(const char* what, const uint8_t* src, int64_t n, uint8_t* dst, int64_t cap, uint32_t* end) {
     if (!src || !dst || n < 0 || cap < 0 || cap >= ((int64_t)1 << 31) || n >= ((int64_t)1 << 28)) {
-        td_set_error("td_tiff_inflate: bad argument");
+        td_set_error("%s: bad argument", what);
         return TD_ERR_INVALID;
     }
     static thread_local InflateScratchT<8192> scratch;       // (the ring the device uses on large rasters: its far-match path runs here too)
@@ -178,16 +184,43 @@ extern "C" int64_t td_tiff_inflate(const uint8_t* src, int64_t n, uint8_t* dst, 
     // the stream into a padded, aligned buffer so that a caller's tight buffer is never over-read
     std::vector<uint32_t> padded((size_t)(n + 8) / 4 + 2, 0u);
     std::memcpy(padded.data(), src, (size_t)n);
-    const InflateResult r = inflate_block<1>(scratch, reinterpret_cast<const uint8_t*>(padded.data()), n, dst, (uint32_t)cap, 0);
+    const InflateResult r = inflate_block<1, 8192, ZLIB_RULES>(scratch, reinterpret_cast<const uint8_t*>(padded.data()), n, dst, (uint32_t)cap, 0);
     if (r.status == 1) {
-        td_set_error("td_tiff_inflate: corrupt stream");
+        td_set_error("%s: corrupt stream", what);
         return TD_ERR_INVALID;
     }
     if (r.status == 2) {
-        td_set_error("td_tiff_inflate: %lld bytes decoded, capacity %lld", (long long)r.produced, (long long)cap);
+        td_set_error("%s: %lld bytes decoded, capacity %lld", what, (long long)r.produced, (long long)cap);
         return TD_ERR_CAPACITY;
     }
+    *end = r.end;
     return (int64_t)r.produced;
+}
+}  // namespace
+extern "C" int64_t td_tiff_inflate(const uint8_t* src, int64_t n, uint8_t* dst, int64_t cap) {
+    uint32_t end = 0;
+    return inflate_host<false>("td_tiff_inflate", src, n, dst, cap, &end);
+}
+
+extern "C" int64_t td_tiff_inflate_verified(const uint8_t* src, int64_t n, uint8_t* dst, int64_t cap) {
+    uint32_t end = 0;
+    const int64_t produced = inflate_host<true>("td_tiff_inflate_verified", src, n, dst, cap, &end);
+    if (produced < 0) return produced;
+    uint32_t a = 1, b = 0;                                  // Adler-32 (RFC 1950), reduced every 5552 bytes: the most before b can overflow
+    for (int64_t i = 0; i < produced;) {
+        const int64_t stop = std::min<int64_t>(produced, i + 5552);
+        for (; i < stop; ++i) {
+            a += dst[i];
+            b += a;
+        }
+        a %= 65521u;
+        b %= 65521u;
+    }
+    if (!inflate_trailer_ok(src, n, end, (b << 16) | a)) {
+        td_set_error("td_tiff_inflate_verified: Adler-32 mismatch or no trailer");
+        return TD_ERR_INVALID;
+    }
+    return produced;
 }
 
 // PackBits (TIFF 6.0 section 9): header byte h: 0..127 → copy h+1 literal bytes; -127..-1 → repeat the next byte

@@ -344,21 +344,119 @@ __global__ __launch_bounds__(64 * WPB) void tiff_lzw_blocks_kernel(const uint8_t
 // vector registers and 12 KB of LDS for the whole 60 ms, and one such wave per SIMD is enough to keep the model's large tiles
 // (256 registers x 2 waves per SIMD, > 100 KB of LDS) off that CU — spread one per workgroup they stalled the forward of the
 // image that predicts meanwhile on every CU of the chip.
-template <int RING, int WPB>
+// VERIFY (td_tiff_inflate_verified_dev): zlib's rules for the header and the code sets, and the offset of the stream's Adler-32
+// trailer goes to end_off[b] for tiff_adler32_blocks_kernel below.
+template <int RING, int WPB, bool VERIFY = false>
 __global__ __launch_bounds__(64 * WPB) void tiff_inflate_blocks_kernel(const uint8_t* __restrict__ comp, const int64_t* __restrict__ block_off,
                                                                        const int64_t* __restrict__ block_nbytes, uint8_t* __restrict__ out,
                                                                        int64_t block_cap, int64_t* __restrict__ decoded,
-                                                                       int32_t* __restrict__ status, int nblocks, int* __restrict__ ticket) {
+                                                                       int32_t* __restrict__ status, int nblocks, int* __restrict__ ticket,
+                                                                       int64_t* __restrict__ end_off) {
     __shared__ InflateScratchT<RING> S[WPB];
     const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), lane = (int)threadIdx.x & 63;      // the wave's number as a scalar: its LDS base stays one
     for (int b = take_block(ticket, lane); b < nblocks; b = take_block(ticket, lane)) {      // whole waves leave; nothing in here meets a workgroup barrier
-        const InflateResult r = inflate_block<64>(S[wave], comp + block_off[b], block_nbytes[b], out + (int64_t)b * block_cap, (uint32_t)block_cap, lane);
+        const InflateResult r = inflate_block<64, RING, VERIFY>(S[wave], comp + block_off[b], block_nbytes[b], out + (int64_t)b * block_cap,
+                                                                (uint32_t)block_cap, lane);
         if (lane == 0) {
             decoded[b] = (int64_t)r.produced;
             status[b] = r.status;
+            if (VERIFY) end_off[b] = (int64_t)r.end;
         }
         TD_INF_SYNC();                                     // the next block's set-up writes follow this block's last LDS reads
     }
+}
+
+// Adler-32 (RFC 1950) of one buffer per workgroup, position-parallel: with n bytes x_0 .. x_{n-1}, A = 1 + sum x_i and
+// B = n + sum (n - i) x_i = n + n sum x_i - sum i x_i, both modulo 65521 — so the bytes may be summed in any order as long as
+// each carries its index. Thread t takes the 16-byte vectors t, t + 256, t + 512, ... of the 16-byte-aligned middle of the buffer
+// (threads 0 .. 15 also one byte each of the unaligned head and tail), and keeps of its q-th vector (bytes v .. v + 15, v = head
+// + 16 (256 q + t)) three exact sums: S = sum x, T = sum k x_{v + k} and q S; its sum of i x is then (head + 16 t) sum S +
+// 4096 sum q S + sum T. Nothing is reduced inside the loop because nothing can overflow: n < 2^31 gives q < 2^19, S <= 4080
+// and T <= 30600 (all bytes 0xFF), so sum S < 2^31, sum T < 2^34 and sum q S < 2^49 in 64-bit accumulators. Each thread reduces
+// its two sums modulo 65521 once, the wave adds them by lane shifts (64 values < 2^16), the four waves meet in LDS.
+// Buffer b begins at data + b * stride; lengths: the buffers' sizes (low 32 bits: `decoded` of the block decoders), or nullptr = n_all.
+// verify (the blocks of td_tiff_inflate_verified_dev): only blocks of status 0 are summed; a block whose big-endian trailer at
+// comp[block_off[b] + end_off[b]] differs, or would lie beyond block_nbytes[b] (zlib: stream incomplete), gets status 3. Otherwise
+// the checksum goes to out[b]. The decoder's kernel has ended before this one starts (same stream): plain loads see its bytes.
+constexpr uint32_t ADLER_MOD = 65521u;
+constexpr int ADLER_THREADS = 256;
+__global__ __launch_bounds__(ADLER_THREADS) void tiff_adler32_blocks_kernel(const uint8_t* __restrict__ data, int64_t stride, int64_t n_all,
+                                                                            const int64_t* __restrict__ lengths, uint32_t* __restrict__ out,
+                                                                            const uint8_t* __restrict__ comp, const int64_t* __restrict__ block_off,
+                                                                            const int64_t* __restrict__ block_nbytes,
+                                                                            const int64_t* __restrict__ end_off, int32_t* __restrict__ status) {
+    __shared__ uint32_t part[2][ADLER_THREADS / 64];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const bool verify = status != nullptr;
+    if (verify && status[b] != 0) return;                  // (the same answer for the whole workgroup: nobody waits at the barrier below)
+    const uint8_t* p = data + (int64_t)b * stride;
+    const uint32_t n = lengths ? (uint32_t)(lengths[b] & 0xffffffff) : (uint32_t)n_all;      // < 2^31
+    const uint32_t mis = (uint32_t)((16u - (uint32_t)(reinterpret_cast<uintptr_t>(p) & 15u)) & 15u);
+    const uint32_t head = mis < n ? mis : n;
+    const uint32_t nvec = (n - head) >> 4;
+    const uint32_t tail0 = head + (nvec << 4);             // the bytes [tail0, n): fewer than 16
+    uint64_t sum_s = 0, sum_t = 0, sum_qs = 0;
+    const uint4* v = reinterpret_cast<const uint4*>(p + head);
+    uint32_t q = 0;
+#pragma unroll 4
+    for (uint32_t j = tid; j < nvec; j += ADLER_THREADS, ++q) {
+        const uint4 w = v[j];
+        // bytes of a dword in memory order = from its low end; weights k = 0 .. 15 over the four dwords
+        auto bytes = [](uint32_t d) { return (d & 255u) + ((d >> 8) & 255u) + ((d >> 16) & 255u) + (d >> 24); };
+        auto ramp = [](uint32_t d) { return ((d >> 8) & 255u) + 2u * ((d >> 16) & 255u) + 3u * (d >> 24); };
+        const uint32_t s0 = bytes(w.x), s1 = bytes(w.y), s2 = bytes(w.z), s3 = bytes(w.w);
+        const uint32_t S = s0 + s1 + s2 + s3;
+        const uint32_t T = ramp(w.x) + ramp(w.y) + ramp(w.z) + ramp(w.w) + 4u * s1 + 8u * s2 + 12u * s3;
+        sum_s += S;
+        sum_t += T;
+        sum_qs += (uint64_t)q * S;
+    }
+    uint64_t sx = sum_s % ADLER_MOD;
+    uint64_t six = ((uint64_t)(head + 16u * (uint32_t)tid) * sx + 4096u * (sum_qs % ADLER_MOD) + sum_t % ADLER_MOD) % ADLER_MOD;
+    if ((uint32_t)tid < head) {                            // the unaligned head: byte tid
+        const uint32_t x = p[tid];
+        sx += x;
+        six += (uint64_t)tid * x;
+    }
+    if (tail0 + (uint32_t)tid < n) {                       // the tail: byte tail0 + tid
+        const uint32_t x = p[tail0 + tid];
+        sx += x;
+        six += (uint64_t)((tail0 + (uint32_t)tid) % ADLER_MOD) * x;
+    }
+    uint32_t a = (uint32_t)(sx % ADLER_MOD), c = (uint32_t)(six % ADLER_MOD);
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {                    // 64 values < 2^16: no overflow
+        a += (uint32_t)__shfl_down((int)a, d);
+        c += (uint32_t)__shfl_down((int)c, d);
+    }
+    if ((tid & 63) == 0) {
+        part[0][tid >> 6] = a;
+        part[1][tid >> 6] = c;
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    uint64_t sum_x = 0, sum_ix = 0;
+    for (int w = 0; w < ADLER_THREADS / 64; ++w) {
+        sum_x += part[0][w];
+        sum_ix += part[1][w];
+    }
+    sum_x %= ADLER_MOD;
+    sum_ix %= ADLER_MOD;
+    const uint64_t nm = n % ADLER_MOD;
+    const uint32_t A = (uint32_t)((1u + sum_x) % ADLER_MOD);
+    const uint32_t B = (uint32_t)((nm + nm * sum_x + ADLER_MOD - sum_ix) % ADLER_MOD);
+    const uint32_t adler = (B << 16) | A;
+    if (!verify) {
+        out[b] = adler;
+        return;
+    }
+    const int64_t e = end_off[b];
+    bool ok = e >= 0 && e + 4 <= block_nbytes[b];
+    if (ok) {
+        const uint8_t* t = comp + block_off[b] + e;
+        ok = (((uint32_t)t[0] << 24) | ((uint32_t)t[1] << 16) | ((uint32_t)t[2] << 8) | (uint32_t)t[3]) == adler;
+    }
+    if (!ok) status[b] = 3;
 }
 
 // Decoded blocks → the raster [height][width][spp] (pixel-interleaved samples of type T: uint8, or uint16 in the GPU's own
@@ -526,10 +624,13 @@ extern "C" td_status td_tiff_lzw_decode_dev(const uint8_t* comp, const int64_t* 
     return TD_OK;
 }
 
-extern "C" td_status td_tiff_inflate_dev(const uint8_t* comp, const int64_t* block_off, const int64_t* block_nbytes, int nblocks,
-                                         uint8_t* blocks_out, int64_t block_cap, int64_t* decoded, int32_t* status, void* stream) {
-    TD_REQUIRE(comp && block_off && block_nbytes && blocks_out && decoded && status, "td_tiff_inflate_dev: null pointer");
-    TD_REQUIRE(nblocks >= 0 && block_cap >= 1 && block_cap < ((int64_t)1 << 31), "td_tiff_inflate_dev: %d blocks of %lld bytes", nblocks,
+namespace {
+
+// both DEFLATE entry points: end_off == nullptr is td_tiff_inflate_dev, otherwise the verifying decoder (zlib's rules, trailer offsets)
+td_status launch_inflate(const char* what, const uint8_t* comp, const int64_t* block_off, const int64_t* block_nbytes, int nblocks,
+                         uint8_t* blocks_out, int64_t block_cap, int64_t* decoded, int32_t* status, int64_t* end_off, void* stream) {
+    TD_REQUIRE(comp && block_off && block_nbytes && blocks_out && decoded && status, "%s: null pointer", what);
+    TD_REQUIRE(nblocks >= 0 && block_cap >= 1 && block_cap < ((int64_t)1 << 31), "%s: %d blocks of %lld bytes", what, nblocks,
                (long long)block_cap);
     if (nblocks == 0) return TD_OK;
     constexpr int WPB_SMALL = 12, WPB_WINDOW = 4;          // 148 KB of LDS per workgroup either way
@@ -540,19 +641,62 @@ extern "C" td_status td_tiff_inflate_dev(const uint8_t* comp, const int64_t* blo
     const td_status tst = next_ticket(static_cast<hipStream_t>(stream), &ticket, &cus);
     if (tst < 0) return tst;
     // one workgroup per CU at most (WPB = 1: as many single waves as CUs hold: twelve each)
-#define TD_INFLATE(RING, WPB) hipLaunchKernelGGL((tiff_inflate_blocks_kernel<RING, WPB>), \
+#define TD_INFLATE(RING, WPB, VERIFY) hipLaunchKernelGGL((tiff_inflate_blocks_kernel<RING, WPB, VERIFY>), \
                                                  dim3((nblocks + WPB - 1) / WPB < cus * (WPB == 1 ? 12 : 1) ? (nblocks + WPB - 1) / WPB : cus * (WPB == 1 ? 12 : 1)), \
                                                  dim3(64 * WPB), 0, static_cast<hipStream_t>(stream), comp, block_off, block_nbytes, blocks_out, block_cap, \
-                                                 decoded, status, nblocks, ticket)
-    if (inflate_ring_choice(nblocks)) {
-        if (wpb == 1) TD_INFLATE(8192, 1);
-        else if (wpb == 8) TD_INFLATE(8192, 8);
-        else TD_INFLATE(8192, WPB_SMALL);
+                                                 decoded, status, nblocks, ticket, end_off)
+    if (end_off) {                                         // (the measurement layouts of TD_INFLATE_WPB exist for the plain decoder only)
+        if (inflate_ring_choice(nblocks)) TD_INFLATE(8192, WPB_SMALL, true);
+        else TD_INFLATE(INF_WINDOW, WPB_WINDOW, true);
+    } else if (inflate_ring_choice(nblocks)) {
+        if (wpb == 1) TD_INFLATE(8192, 1, false);
+        else if (wpb == 8) TD_INFLATE(8192, 8, false);
+        else TD_INFLATE(8192, WPB_SMALL, false);
     } else {
-        if (wpb == 1) TD_INFLATE(INF_WINDOW, 1);
-        else TD_INFLATE(INF_WINDOW, WPB_WINDOW);
+        if (wpb == 1) TD_INFLATE(INF_WINDOW, 1, false);
+        else TD_INFLATE(INF_WINDOW, WPB_WINDOW, false);
     }
 #undef TD_INFLATE
+    TD_KERNEL_CHECK();
+    return TD_OK;
+}
+
+}  // namespace
+
+extern "C" td_status td_tiff_inflate_dev(const uint8_t* comp, const int64_t* block_off, const int64_t* block_nbytes, int nblocks,
+                                         uint8_t* blocks_out, int64_t block_cap, int64_t* decoded, int32_t* status, void* stream) {
+    return launch_inflate("td_tiff_inflate_dev", comp, block_off, block_nbytes, nblocks, blocks_out, block_cap, decoded, status, nullptr, stream);
+}
+
+extern "C" td_status td_tiff_adler32_blocks_dev(const uint8_t* blocks, int64_t block_cap, const int64_t* decoded, const uint8_t* comp,
+                                                const int64_t* block_off, const int64_t* block_nbytes, const int64_t* end_off, int nblocks,
+                                                int32_t* status, void* stream) {
+    TD_REQUIRE(blocks && decoded && comp && block_off && block_nbytes && end_off && status, "td_tiff_adler32_blocks_dev: null pointer");
+    TD_REQUIRE(nblocks >= 0 && block_cap >= 1 && block_cap < ((int64_t)1 << 31), "td_tiff_adler32_blocks_dev: %d blocks of %lld bytes", nblocks,
+               (long long)block_cap);
+    if (nblocks == 0) return TD_OK;
+    hipLaunchKernelGGL(tiff_adler32_blocks_kernel, dim3(nblocks), dim3(ADLER_THREADS), 0, static_cast<hipStream_t>(stream), blocks, block_cap,
+                       (int64_t)0, decoded, static_cast<uint32_t*>(nullptr), comp, block_off, block_nbytes, end_off, status);
+    TD_KERNEL_CHECK();
+    return TD_OK;
+}
+
+extern "C" td_status td_tiff_inflate_verified_dev(const uint8_t* comp, const int64_t* block_off, const int64_t* block_nbytes, int nblocks,
+                                                  uint8_t* blocks_out, int64_t block_cap, int64_t* decoded, int32_t* status, int64_t* end_off,
+                                                  void* stream) {
+    TD_REQUIRE(end_off, "td_tiff_inflate_verified_dev: null pointer");
+    const td_status st = launch_inflate("td_tiff_inflate_verified_dev", comp, block_off, block_nbytes, nblocks, blocks_out, block_cap, decoded,
+                                        status, end_off, stream);
+    if (st < 0) return st;
+    return td_tiff_adler32_blocks_dev(blocks_out, block_cap, decoded, comp, block_off, block_nbytes, end_off, nblocks, status, stream);
+}
+
+extern "C" td_status td_adler32_dev(const uint8_t* data_dev, int64_t n, uint32_t* out_dev, void* stream) {
+    TD_REQUIRE(out_dev && (data_dev || n == 0), "td_adler32_dev: null pointer");
+    TD_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), "td_adler32_dev: %lld bytes", (long long)n);
+    hipLaunchKernelGGL(tiff_adler32_blocks_kernel, dim3(1), dim3(ADLER_THREADS), 0, static_cast<hipStream_t>(stream), data_dev, (int64_t)0, n,
+                       static_cast<const int64_t*>(nullptr), out_dev, static_cast<const uint8_t*>(nullptr), static_cast<const int64_t*>(nullptr),
+                       static_cast<const int64_t*>(nullptr), static_cast<const int64_t*>(nullptr), static_cast<int32_t*>(nullptr));
     TD_KERNEL_CHECK();
     return TD_OK;
 }

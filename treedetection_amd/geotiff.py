@@ -413,10 +413,12 @@ class GeoTiff:
     def decode_to_device(self, device, stream=None, pinned=None, pool=None):
         """The whole raster decoded in HBM: the compressed blocks are read as they lie in the file (one pread of the span that
         holds them, into pinned memory), copied to the device once, decoded one wave per block (td_tiff_lzw_decode_dev /
-        td_tiff_inflate_dev; JPEG: one lane per entropy-coded segment, td_tiff_jpeg_decode_dev, planned once by td_tiff_jpeg_plan) and
+        td_tiff_inflate_verified_dev, which also checks every DEFLATE block's Adler-32 trailer as zlib does; JPEG: one lane per
+        entropy-coded segment, td_tiff_jpeg_decode_dev, planned once by td_tiff_jpeg_plan) and
         laid out as [height, width, bands] uint8 — or torch.uint16 for 16-bit rasters — with predictor 2 undone
-        (td_tiff_blocks_to_image_dev / td_tiff_blocks_to_image_u16_dev). → (image tensor, check) where ``check()`` waits for the kernels and raises ValueError when a block did not decode to its size (the
-        caller then falls back to the host reader). Everything is enqueued on ``stream`` (default: the current one). ``pinned``:
+        (td_tiff_blocks_to_image_dev / td_tiff_blocks_to_image_u16_dev). → (image tensor, check) where ``check()`` waits for the kernels and raises ValueError when a block did not decode to its size
+        or, DEFLATE, its bytes do not sum to the stream's checksum ("Adler-32 mismatch": the host reader's zlib raises on the same block) — the
+        caller then falls back to the host reader. Everything is enqueued on ``stream`` (default: the current one). ``pinned``:
         a one-element list holding a pinned uint8 tensor to read the file into (grown and put back when too small — pinning
         hundreds of MB per image costs as much as reading them); ``pool``: threads the file read is spread over."""
         import torch
@@ -473,10 +475,14 @@ class GeoTiff:
             blocks = torch.empty((nb, block_cap), dtype=torch.uint8, device=dev)
             decoded = torch.empty((nb,), dtype=torch.int64, device=dev)
             status = torch.empty((2 * nb + 1,), dtype=torch.int32, device=dev)      # [nb] status + scratch of the wide-table pass
+            ends = torch.empty((nb,), dtype=torch.int64, device=dev) if self.compression != 5 else None      # DEFLATE: where each trailer begins
             k0.record()
-            fn, fname = (lib.td_tiff_lzw_decode_dev, "td_tiff_lzw_decode_dev") if self.compression == 5 else (lib.td_tiff_inflate_dev, "td_tiff_inflate_dev")
-            _lib.check(fn(comp.data_ptr(), meta[0].data_ptr(), meta[1].data_ptr(), nb, blocks.data_ptr(), block_cap,
-                          decoded.data_ptr(), status.data_ptr(), st), fname)
+            if self.compression == 5:
+                _lib.check(lib.td_tiff_lzw_decode_dev(comp.data_ptr(), meta[0].data_ptr(), meta[1].data_ptr(), nb, blocks.data_ptr(), block_cap,
+                                                      decoded.data_ptr(), status.data_ptr(), st), "td_tiff_lzw_decode_dev")
+            else:
+                _lib.check(lib.td_tiff_inflate_verified_dev(comp.data_ptr(), meta[0].data_ptr(), meta[1].data_ptr(), nb, blocks.data_ptr(), block_cap,
+                                                            decoded.data_ptr(), status.data_ptr(), ends.data_ptr(), st), "td_tiff_inflate_verified_dev")
             image = torch.empty((self.height, self.width, self.count), dtype=torch.uint8 if item == 1 else torch.uint16, device=dev)
             scatter, sname = ((lib.td_tiff_blocks_to_image_dev, "td_tiff_blocks_to_image_dev") if item == 1 else
                               (lib.td_tiff_blocks_to_image_u16_dev, "td_tiff_blocks_to_image_u16_dev"))
@@ -491,17 +497,19 @@ class GeoTiff:
             st_h.copy_(status[:nb], non_blocking=True)
             copied = torch.cuda.Event(blocking=True)
             copied.record()
-        keep = [pin, comp, meta, blocks, decoded, status]     # alive until check() has run: the kernels read them
+        keep = [pin, comp, meta, blocks, decoded, status, ends]     # alive until check() has run: the kernels read them
 
         def check():
             copied.synchronize()
-            check.kernel_ms = k0.elapsed_time(k1)          # the two decode launches + the scatter / predictor kernel
+            check.kernel_ms = k0.elapsed_time(k1)          # the decode launches (DEFLATE: + the checksum launch) + the scatter / predictor kernel
             keep.clear()
             produced = dec_h.numpy() & 0xffffffff
             check.slow_codes = int((dec_h.numpy() >> 32).sum())     # LZW: strings copied through memory (sources older than the LDS ring)
             bad = np.nonzero((st_h.numpy() != 0) | (produced != expect))[0]
             if bad.size:
                 b = int(bad[0])
+                if self.compression != 5 and int(st_h[b]) == 3:
+                    raise ValueError(f"{self.path}: block {b}: Adler-32 mismatch (status 3): its {int(produced[b])} decoded bytes do not sum to the stream's trailer")
                 raise ValueError(f"{self.path}: block {b} decodes to {int(produced[b])} bytes (status {int(st_h[b])}), expected {int(expect[b])}")
             return image
         check.event = done
