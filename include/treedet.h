@@ -376,6 +376,12 @@ td_status td_tiff_blocks_to_image_dev(const uint8_t* blocks, int64_t block_cap, 
  * uint16 (DEVICE), and predictor 2 is undone per whole sample modulo 65536 (TIFF 6.0 section 14). spp <= 4. Asynchronous on `stream`. */
 td_status td_tiff_blocks_to_image_u16_dev(const uint8_t* blocks, int64_t block_cap, int block_w, int block_h, int blocks_across,
                                           int blocks_down, int spp, int predictor, uint16_t* image, int width, int height, void* stream);
+/* The same for float32 samples (height rasters): blocks hold the bytes as the block decoders left them, image is [height][width][spp]
+ * float (DEVICE). predictor 1: little-endian floats, copied; 2: horizontal differencing of the samples viewed as uint32, modulo 2^32;
+ * 3: the floating-point predictor (TIFF Technical Note 3, td_tiff_unpredict_float's rule), undone per block row. spp <= 4.
+ * Asynchronous on `stream`. */
+td_status td_tiff_blocks_to_image_f32_dev(const uint8_t* blocks, int64_t block_cap, int block_w, int block_h, int blocks_across,
+                                          int blocks_down, int spp, int predictor, float* image, int width, int height, void* stream);
 /* ---- JPEG-in-TIFF (compression 7; jpeg_core.h, jpegcodec.cpp, jpegdecode.hip): sequential Huffman, 8-bit, grey or three components
  * (Y 1x1 / 2x1 / 2x2, chroma 1x1), restart intervals; the output equals the host reader's (Pillow's libjpeg: accurate integer IDCT, fancy
  * upsampling, its YCbCr → RGB) byte for byte. Everything else is unsupported and stays with the host reader. */
@@ -418,6 +424,12 @@ int64_t td_read_windows(int fd, int n, const int64_t* file_off, int64_t row_stri
 /* Undo TIFF predictor 2 (horizontal differencing) in place on one decoded block of rows x cols pixels with
  * `samples` interleaved samples of 1, 2 or 4 bytes (host byte order). */
 int td_tiff_unpredict(void* data, int64_t rows, int64_t cols, int samples, int bytes_per_sample);
+/* Undo TIFF predictor 3 (floating-point predictor, TIFF Technical Note 3; libtiff's fpAcc) in place on one decoded block of
+ * rows x cols pixels with `samples` interleaved samples of bytes_per_sample == 4 bytes. A row of n = cols * samples floats is
+ * stored as 4n bytes: a byte-wise running sum modulo 256 with stride `samples` runs over ALL of them (across the plane
+ * boundaries), then the bytes are four planes of n, most significant first — in every file, whatever its byte order. The
+ * result is floats in host byte order. TD_ERR_INVALID for a null pointer or another sample size. */
+int td_tiff_unpredict_float(void* data, int64_t rows, int64_t cols, int samples, int bytes_per_sample);
 
 /* The same file text from contours traced on the device: points / det_info / contour_info are ONE image's slices of the
  * td_trace_contours_dev outputs, copied to the host. Detections the device left to the host (status != 0) are traced

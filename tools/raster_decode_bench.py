@@ -7,7 +7,13 @@ Raster side x side x 4 uint8 (default 9000: the 400 windows of 450 x 450 px the 
 call file → pinned → device → decoded raster in HBM, and the kernels alone (HIP events). Under rocprofv3 --kernel-trace --stats the
 per-kernel durations land in profiles/r06_decode_kernel_stats.csv.
 DEFLATE: the blocks' Adler-32 check is a launch of its own behind the inflate kernel; "inflate_ms" and "checksum_ms" time the two
-separately (HIP events around td_tiff_inflate_dev and around td_tiff_adler32_blocks_dev, the raster's blocks already on the device)."""
+separately (HIP events around td_tiff_inflate_dev and around td_tiff_adler32_blocks_dev, the raster's blocks already on the device).
+samples=f32 [codec=deflate|lzw] [side=9000] [tile=256|strip=N] [predictors=1,2,3]: the float32 height raster of the post-processing
+stage (a synthetic nDSM, one band) — per predictor one JSON line with the compressed size, the block decoder's launch and the scatter /
+predictor kernel apart (HIP events on the stream they ran on, median of 7 warm runs; the scatter's GB/s counts one read and one
+write of the raster), the wall time from the file to a raster td_crown_stats can read for the device path (decode_to_device +
+check()) and for the host paths: the block reader (read()) + the copy to the device, and — predictor 3 — the whole image through Pillow
++ the copy, which is how the reader served such files before it undid the floating-point predictor itself."""
 import json
 import os
 import sys
@@ -23,6 +29,117 @@ from treedetection_amd.geotiff import GeoTiff, write_geotiff      # noqa: E402
 from treedetection_amd.synth import make_tile                      # noqa: E402
 
 args = dict(a.split("=", 1) for a in sys.argv[1:] if "=" in a)
+
+
+def f32_main():
+    from concurrent.futures import ThreadPoolExecutor
+    from statistics import median
+    from treedetection_amd import _lib
+    lib = _lib.load()
+    side, codec = int(args.get("side", 9000)), args.get("codec", "deflate")
+    kw = {"rows_per_strip": int(args["strip"])} if "strip" in args else {"tile": (int(args.get("tile", 256)),) * 2}
+    n = -(-side // 1000)
+    tiles = [make_tile(i, 1000)[1] for i in range(min(16, n * n))]
+    img = np.ascontiguousarray(np.block([[tiles[(r * n + c) % len(tiles)] for c in range(n)] for r in range(n)])[None, :side, :side])
+    base = "/dev/shm" if os.path.isdir("/dev/shm") else tempfile.gettempdir()
+    path = os.path.join(base, f"td_f32bench_{os.getpid()}.tif")
+    pinned, pool = [None], ThreadPoolExecutor(max_workers=8)
+    sp = _lib.stream_ptr()
+
+    def timed(fn, reps=7):
+        out = []
+        for _ in range(reps + 1):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            _lib.check(fn(), "launch")
+            e1.record()
+            torch.cuda.synchronize()
+            out.append(e0.elapsed_time(e1))
+        return out[1:]                                      # (the first run is the warm-up)
+
+    def wall(fn, reps=5):
+        out = []
+        for _ in range(reps + 1):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            out.append((time.perf_counter() - t0) * 1e3)
+        return out[1:]
+
+    for pred in [int(v) for v in args.get("predictors", "1,2,3").split(",")]:
+        try:
+            write_geotiff(path, img, (1.0, 0, 412000.0, 0, -1.0, 5318000.0 + side), 25832, compression=codec, predictor=pred, **kw)
+            g = GeoTiff(path)
+            assert g.device_decodable(float_samples=True)
+
+            def device_path():
+                image, check = g.decode_to_device("cuda:0", None, pinned, pool)
+                return check()
+            got = device_path()
+            assert np.array_equal(got.cpu().numpy()[:, :, 0].view(np.uint32), img[0].view(np.uint32)), "decoded raster differs from what was written"
+            del got
+            device_ms = wall(device_path)
+
+            def host_blocks():
+                h = GeoTiff(path)
+                torch.from_numpy(np.ascontiguousarray(h.read()[0], dtype=np.float32)).to("cuda:0")
+                h.close()
+
+            def host_pillow():
+                from PIL import Image
+                Image.MAX_IMAGE_PIXELS = None
+                torch.from_numpy(np.ascontiguousarray(np.asarray(Image.open(path)), dtype=np.float32)).to("cuda:0")
+            host_ms = wall(host_blocks, 3)
+            pillow_ms = wall(host_pillow, 3) if pred == 3 else None
+            # the two launches apart, the raster's compressed blocks already on the device
+            offs, cnts = np.asarray(g._offs, dtype=np.int64), np.asarray(g._counts, dtype=np.int64)
+            lo, nb = int(offs.min()), g._nx * g._ny
+            span = int((offs + cnts).max()) - lo
+            cap = g._bw * g._bh * 4
+            comp = torch.zeros((span + 16,), dtype=torch.uint8)
+            comp[:span] = torch.from_numpy(np.fromfile(path, dtype=np.uint8, count=span, offset=lo))
+            comp = comp.cuda()
+            meta = torch.from_numpy(np.stack([offs - lo, cnts])).cuda()
+            blocks = torch.empty((nb, cap), dtype=torch.uint8, device="cuda")
+            dec = torch.empty((nb,), dtype=torch.int64, device="cuda")
+            ends = torch.empty((nb,), dtype=torch.int64, device="cuda")
+            status = torch.empty((2 * nb + 1,), dtype=torch.int32, device="cuda")
+            image = torch.empty((side, side), dtype=torch.float32, device="cuda")
+            head = (comp.data_ptr(), meta[0].data_ptr(), meta[1].data_ptr(), nb, blocks.data_ptr(), cap, dec.data_ptr(), status.data_ptr())
+            if codec == "lzw":
+                decode_ms = timed(lambda: lib.td_tiff_lzw_decode_dev(*head, sp))
+                plain_ms = None
+            else:
+                plain_ms = timed(lambda: lib.td_tiff_inflate_dev(*head, sp))
+                decode_ms = timed(lambda: lib.td_tiff_inflate_verified_dev(*head, ends.data_ptr(), sp))
+            assert int((status[:nb] != 0).sum()) == 0
+            scatter_ms = timed(lambda: lib.td_tiff_blocks_to_image_f32_dev(blocks.data_ptr(), cap, g._bw, g._bh, g._nx, g._ny, 1, pred, image.data_ptr(),
+                                                                          side, side, sp))
+            assert np.array_equal(image.cpu().numpy().view(np.uint32), img[0].view(np.uint32))
+            raw = img.nbytes
+            r3 = lambda v: None if v is None else [round(t, 3) for t in v]
+            print(json.dumps({"samples": "f32", "codec": codec, "raster": f"{side}x{side}x1", "layout": kw, "predictor": pred, "blocks": nb,
+                              "raw_mb": raw / 1e6, "file_mb": os.path.getsize(path) / 1e6,
+                              "inflate_ms" if codec != "lzw" else "lzw_ms": r3(plain_ms if codec != "lzw" else decode_ms),
+                              "inflate_verified_ms": r3(decode_ms) if codec != "lzw" else None,
+                              "scatter_ms": r3(scatter_ms), "scatter_median_ms": round(median(scatter_ms), 3),
+                              "scatter_gb_per_s_read_plus_write": 2 * raw / (median(scatter_ms) * 1e-3) / 1e9,
+                              "decoder_median_ms": round(median(plain_ms if codec != "lzw" else decode_ms), 3),
+                              "device_path_wall_ms": r3(device_ms), "device_path_median_ms": round(median(device_ms), 1),
+                              "host_block_reader_plus_h2d_ms": r3(host_ms), "host_block_reader_median_ms": round(median(host_ms), 1),
+                              "host_pillow_whole_image_plus_h2d_ms": r3(pillow_ms),
+                              "host_pillow_median_ms": None if pillow_ms is None else round(median(pillow_ms), 1)}), flush=True)
+            g.close()
+            del comp, meta, blocks, dec, ends, status, image
+        finally:
+            if os.path.exists(path):
+                os.unlink(path)
+
+
+if args.get("samples") == "f32":
+    f32_main()
+    sys.exit(0)
 side, pred, data, codec = int(args.get("side", 9000)), int(args.get("predictor", 2)), args.get("data", "tiles"), args.get("codec", "lzw")
 kw = {"rows_per_strip": int(args["strip"])} if "strip" in args else {"tile": (int(args.get("tile", 256)),) * 2}
 base = "/dev/shm" if os.path.isdir("/dev/shm") else tempfile.gettempdir()

@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <vector>
 
 // TIFF LZW: MSB-first variable-width codes (9..12 bits), ClearCode 256, EndOfInformation 257, first free code 258,
 // code width grows one code EARLY (when the next free code reaches 2^width - 1).
@@ -278,6 +279,30 @@ extern "C" int td_tiff_unpredict(void* data, int64_t rows, int64_t cols, int sam
         } else {
             uint32_t* p = static_cast<uint32_t*>(data) + r * row_elems;
             for (int64_t i = samples; i < row_elems; ++i) p[i] = p[i] + p[i - samples];
+        }
+    }
+    return TD_OK;
+}
+
+// Predictor 3 (TIFF Technical Note 3, the floating-point predictor; libtiff's fpAcc): a row of n = cols * samples floats lies
+// in the block as 4n bytes — the samples' bytes sorted into four planes of n, most significant byte first whatever the file's
+// byte order, then differenced byte-wise with stride `samples` over the whole 4n bytes (the differences do not restart at a
+// plane's beginning). Undo both in place, row by row: the running sum, then one pass that puts each sample's bytes together.
+extern "C" int td_tiff_unpredict_float(void* data, int64_t rows, int64_t cols, int samples, int bytes_per_sample) {
+    if (!data || rows < 0 || cols < 0 || samples < 1 || bytes_per_sample != 4) {
+        td_set_error("td_tiff_unpredict_float: bad argument (4-byte samples only)");
+        return TD_ERR_INVALID;
+    }
+    const int64_t n = cols * samples;
+    std::vector<uint8_t> planes((size_t)(4 * n));
+    for (int64_t r = 0; r < rows; ++r) {
+        uint8_t* p = static_cast<uint8_t*>(data) + r * 4 * n;
+        for (int64_t i = samples; i < 4 * n; ++i) p[i] = (uint8_t)(p[i] + p[i - samples]);
+        std::memcpy(planes.data(), p, (size_t)(4 * n));
+        for (int64_t k = 0; k < n; ++k) {
+            const uint32_t v = ((uint32_t)planes[k] << 24) | ((uint32_t)planes[n + k] << 16) | ((uint32_t)planes[2 * n + k] << 8) |
+                               (uint32_t)planes[3 * n + k];
+            std::memcpy(p + 4 * k, &v, 4);
         }
     }
     return TD_OK;

@@ -459,9 +459,10 @@ __global__ __launch_bounds__(ADLER_THREADS) void tiff_adler32_blocks_kernel(cons
     if (!ok) status[b] = 3;
 }
 
-// Decoded blocks → the raster [height][width][spp] (pixel-interleaved samples of type T: uint8, or uint16 in the GPU's own
-// little-endian order), undoing predictor 2 (TIFF 6.0 section 14: each SAMPLE is the difference to the same sample of the
-// pixel on its left, within the row of its block — modulo 256 or 65536, which is T's own arithmetic) on the way. One
+// Decoded blocks → the raster [height][width][spp] (pixel-interleaved samples of type T: uint8, uint16 in the GPU's own
+// little-endian order, or uint32 = the bit patterns of little-endian float32 samples), undoing predictor 2 (TIFF 6.0 section
+// 14: each SAMPLE is the difference to the same sample of the pixel on its left, within the row of its block — modulo 256,
+// 65536 or 2^32, which is T's own arithmetic) on the way. One
 // workgroup per (image row, block column): a block row of bw pixels is a prefix sum per sample — per-thread runs, a scan of
 // the 256 run totals in LDS, then the stores. block_cap counts BYTES (a multiple of sizeof(T)). HBM-bound: one read and one
 // write of the raster (2 x spp x sizeof(T) bytes per pixel).
@@ -539,6 +540,117 @@ __global__ __launch_bounds__(256) void tiff_blocks_to_image_rgbi_kernel(const ui
             carry = (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
         }
         if (p < valid) dst[p] = v;
+    }
+}
+
+// Predictor 3 (TIFF Technical Note 3, the floating-point predictor; td_tiff_unpredict_float's rule) for float32 rasters. A block
+// row of n = bw * spp floats lies in the block as four byte planes of n bytes, most significant first, differenced byte-wise with
+// stride spp over all 4n bytes. n is a multiple of spp, so a byte's channel is its position in its plane modulo spp in every
+// plane, and the stride-spp running sum over the 4n bytes is, per plane, a running sum per channel that starts from the channel
+// totals of the planes before it. One workgroup per (image row, block column), one WAVE per plane, two passes over the row in
+// steps of 256 positions (any block width: a strip row of a wide raster is walked with carries, nothing of it is kept in LDS):
+//   pass 1  every wave sums its plane per channel; the four totals meet in LDS, wave p starts from those of the planes 0 .. p - 1
+//   pass 2  a lane takes four consecutive bytes of its plane as ONE dword (the planes begin at any byte: two aligned dwords,
+//           shifted): the stride-spp sums inside the dword and the scan of the lanes' channel totals across the wave are packed
+//           byte adds (add_bytes, one byte per channel). The four waves then exchange their dwords through LDS, so that thread t
+//           puts the four bytes of sample t together and the workgroup stores 256 consecutive little-endian floats.
+// Traffic: one write of the raster, and one read of it from HBM where the second pass finds in L2 what the first brought in — rows
+// of tiles (spp KB per workgroup). Rows of strips are 4 x width x spp bytes per workgroup (36 KB at 9 000 px, 280 KB at 70 000):
+// with every CU holding several of them they outgrow an XCD's 4 MB of L2, and the second pass is then served by the Infinity
+// Cache or by HBM — the bound for strips is TWO reads and one write (12 x spp bytes per pixel against 8 x spp for tiles).
+// Only samples inside the raster are stored (edge tiles).
+constexpr int FP_THREADS = 256;
+// bytes k0 .. k0 + 3 of plane `plane` of the row (n dwords at `row`), byte k0 lowest; positions from n on read as 0
+__device__ __forceinline__ uint32_t fp_plane_dword(const uint32_t* __restrict__ row, int n, int plane, int k0) {
+    const int off = plane * n + k0;                        // byte offset in the row; the row is 4n < 2^31 bytes
+    const int d = off >> 2;
+    const uint32_t lo = d < n ? row[d] : 0u, hi = d + 1 < n ? row[d + 1] : 0u;      // (whole dwords of the row: never past its end)
+    const uint32_t v = (uint32_t)((((uint64_t)hi << 32) | lo) >> ((off & 3) * 8));
+    const int left = n - k0;
+    return left >= 4 ? v : (left <= 0 ? 0u : v & ((1u << (8 * left)) - 1u));
+}
+// the stride-spp running sum inside a lane's four bytes
+template <int spp>
+__device__ __forceinline__ uint32_t fp_lane_scan(uint32_t v) {
+    if constexpr (spp == 1) {
+        v = add_bytes(v, v << 8);
+        v = add_bytes(v, v << 16);
+    } else if constexpr (spp < 4) {
+        v = add_bytes(v, v << (8 * spp));
+    }
+    return v;
+}
+// → byte c = the lane's last running sum of channel c; ph = k0 % spp, the channel of the lane's first byte (0 unless spp == 3:
+// k0 is a multiple of 4). The last spp bytes of the dword hold every channel once.
+template <int spp>
+__device__ __forceinline__ uint32_t fp_lane_totals(uint32_t v, int ph) {
+    if constexpr (spp == 4) return v;
+    if constexpr (spp == 2) return v >> 16;
+    if constexpr (spp == 1) return v >> 24;
+    const uint32_t w = v >> 8;                             // bytes 1, 2, 3: channels ph + 1, ph + 2, ph (mod 3) → rotate left by (ph + 1) % 3 bytes
+    const int r = 8 * ((ph + 1) % 3);
+    return r ? ((w << r) | (w >> (24 - r))) & 0xffffffu : w;
+}
+// per-channel sums (byte c = channel c) → what each of the lane's four bytes adds: byte j = channel (ph + j) % spp
+template <int spp>
+__device__ __forceinline__ uint32_t fp_spread(uint32_t e, int ph) {
+    if constexpr (spp == 4) return e;
+    if constexpr (spp == 2) return e | (e << 16);
+    if constexpr (spp == 1) return e * 0x01010101u;
+    const uint64_t twice = (uint64_t)e | ((uint64_t)e << 24);
+    return (uint32_t)(twice >> (8 * ph));
+}
+template <int spp>
+__global__ __launch_bounds__(FP_THREADS) void tiff_fp_blocks_to_image_kernel(const uint8_t* __restrict__ blocks, int64_t block_cap, int bw, int bh,
+                                                                             int blocks_across, uint32_t* __restrict__ image, int width,
+                                                                             int height) {
+    __shared__ uint32_t plane_tot[4];
+    __shared__ uint32_t xch[2][4][64];                     // two steps' dwords of the four planes (one barrier per step)
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int plane = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int y = blockIdx.x, bx = blockIdx.y;
+    const int by = y / bh;
+    const int n = bw * spp;
+    const uint32_t* row = reinterpret_cast<const uint32_t*>(blocks + ((int64_t)by * blocks_across + bx) * block_cap) + (int64_t)(y - by * bh) * n;
+    const int x0 = bx * bw;
+    const int nvalid = min(bw, width - x0) * spp;          // samples of this block row that lie inside the raster
+    uint32_t* dst = image + ((int64_t)y * width + x0) * spp;
+    // pass 1: this plane's total per channel
+    uint32_t acc = 0;
+    for (int base = 0; base < n; base += FP_THREADS) {
+        const int k0 = base + 4 * lane;
+        acc = add_bytes(acc, fp_lane_totals<spp>(fp_lane_scan<spp>(fp_plane_dword(row, n, plane, k0)), spp == 3 ? k0 % 3 : 0));
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) acc = add_bytes(acc, (uint32_t)__shfl_xor((int)acc, d));
+    if (lane == 0) plane_tot[plane] = acc;
+    __syncthreads();
+    uint32_t carry = 0;                                    // per channel: everything before this step's first byte (a scalar)
+    for (int q = 0; q < plane; ++q) carry = add_bytes(carry, plane_tot[q]);
+    carry = (uint32_t)__builtin_amdgcn_readfirstlane((int)carry);
+    // pass 2
+    int buf = 0;
+    for (int base = 0; base < n; base += FP_THREADS, buf ^= 1) {
+        const int k0 = base + 4 * lane;
+        const int ph = spp == 3 ? k0 % 3 : 0;
+        uint32_t v = fp_lane_scan<spp>(fp_plane_dword(row, n, plane, k0));
+        uint32_t incl = fp_lane_totals<spp>(v, ph);
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t up = (uint32_t)__shfl_up((int)incl, d);
+            if (lane >= d) incl = add_bytes(incl, up);
+        }
+        uint32_t excl = (uint32_t)__shfl_up((int)incl, 1);
+        excl = add_bytes(lane ? excl : 0u, carry);
+        carry = add_bytes(carry, (uint32_t)__builtin_amdgcn_readlane((int)incl, 63));
+        xch[buf][plane][lane] = add_bytes(v, fp_spread<spp>(excl, ph));
+        __syncthreads();                                   // (the buffer written two steps ago was read before the barrier of the step between)
+        const int k = base + tid;
+        if (k < nvalid) {
+            const int sh = 8 * (tid & 3);
+            dst[k] = (((xch[buf][0][tid >> 2] >> sh) & 255u) << 24) | (((xch[buf][1][tid >> 2] >> sh) & 255u) << 16) |
+                     (((xch[buf][2][tid >> 2] >> sh) & 255u) << 8) | ((xch[buf][3][tid >> 2] >> sh) & 255u);
+        }
     }
 }
 
@@ -703,13 +815,14 @@ extern "C" td_status td_adler32_dev(const uint8_t* data_dev, int64_t n, uint32_t
 
 namespace {
 
-// the checks and the launch of both sample widths; `what` names the entry point in messages
+// the checks and the launch of every sample width (four bytes: float32, which alone has predictor 3); `what` names the entry point in messages
 template <typename T>
 td_status blocks_to_image(const char* what, const uint8_t* blocks, int64_t block_cap, int block_w, int block_h, int blocks_across, int blocks_down,
                           int spp, int predictor, T* image, int width, int height, void* stream) {
     TD_REQUIRE(blocks && image, "%s: null pointer", what);
     TD_REQUIRE(block_w >= 1 && block_h >= 1 && blocks_across >= 1 && blocks_down >= 1 && width >= 1 && height >= 1, "%s: bad geometry", what);
-    TD_REQUIRE(spp >= 1 && spp <= SC_MAX_SPP && (predictor == 1 || predictor == 2), "%s: %d samples per pixel, predictor %d", what, spp, predictor);
+    TD_REQUIRE(spp >= 1 && spp <= SC_MAX_SPP && (predictor == 1 || predictor == 2 || (sizeof(T) == 4 && predictor == 3)),
+               "%s: %d samples per pixel, predictor %d", what, spp, predictor);
     TD_REQUIRE((int64_t)block_w * block_h * spp * (int64_t)sizeof(T) <= block_cap, "%s: a %d x %d x %d block does not fit %lld bytes", what, block_w,
                block_h, spp, (long long)block_cap);
     TD_REQUIRE((int64_t)blocks_across * block_w >= width && (int64_t)blocks_down * block_h >= height && (int64_t)(blocks_across - 1) * block_w < width &&
@@ -724,6 +837,21 @@ td_status blocks_to_image(const char* what, const uint8_t* blocks, int64_t block
         if (spp == 4 && block_cap % 4 == 0 && reinterpret_cast<uintptr_t>(blocks) % 4 == 0 && reinterpret_cast<uintptr_t>(image) % 4 == 0) {
             hipLaunchKernelGGL(tiff_blocks_to_image_rgbi_kernel, dim3((height + 3) / 4, blocks_across), dim3(256), 0, s, blocks, block_cap, block_w,
                                block_h, blocks_across, predictor, image, width, height);
+            TD_KERNEL_CHECK();
+            return TD_OK;
+        }
+    }
+    if constexpr (sizeof(T) == 4) {
+        if (predictor == 3) {
+#define TD_FP_SCATTER(N) hipLaunchKernelGGL((tiff_fp_blocks_to_image_kernel<N>), grid, dim3(FP_THREADS), 0, s, blocks, block_cap, block_w, block_h, \
+                                            blocks_across, image, width, height)
+            switch (spp) {
+                case 1: TD_FP_SCATTER(1); break;
+                case 2: TD_FP_SCATTER(2); break;
+                case 3: TD_FP_SCATTER(3); break;
+                default: TD_FP_SCATTER(4); break;
+            }
+#undef TD_FP_SCATTER
             TD_KERNEL_CHECK();
             return TD_OK;
         }
@@ -755,4 +883,12 @@ extern "C" td_status td_tiff_blocks_to_image_u16_dev(const uint8_t* blocks, int6
                                                      void* stream) {
     return blocks_to_image<uint16_t>("td_tiff_blocks_to_image_u16_dev", blocks, block_cap, block_w, block_h, blocks_across, blocks_down, spp,
                                      predictor, image, width, height, stream);
+}
+
+extern "C" td_status td_tiff_blocks_to_image_f32_dev(const uint8_t* blocks, int64_t block_cap, int block_w, int block_h, int blocks_across,
+                                                     int blocks_down, int spp, int predictor, float* image, int width, int height,
+                                                     void* stream) {
+    // predictors 1 and 2 move and add the samples as uint32 (TIFF's 32-bit horizontal differencing is modulo 2^32 on the bit patterns)
+    return blocks_to_image<uint32_t>("td_tiff_blocks_to_image_f32_dev", blocks, block_cap, block_w, block_h, blocks_across, blocks_down, spp,
+                                     predictor, reinterpret_cast<uint32_t*>(image), width, height, stream);
 }

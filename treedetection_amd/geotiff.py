@@ -6,9 +6,11 @@ BigTIFF rasters — strips or tiles, pixel-interleaved or planar, 8/16/32-bit in
 DEFLATE (zlib) / LZW / PackBits (td_tiff_*_decode in libtreedet_hip.so), horizontal-differencing predictor — plus the
 three geo tags (ModelPixelScale / ModelTiepoint / GeoKeyDirectory). JPEG-in-TIFF (compression 7, 8-bit, one or three bands)
 is windowed too: a block's abbreviated stream + the JPEGTables tag form one JPEG stream, decoded by Pillow's libjpeg block by
-block (GDAL does the same through libtiff). Other codecs (old-style JPEG, floating-point predictor, ...): whole image through Pillow.
+block (GDAL does the same through libtiff). The floating-point predictor (predictor 3, TIFF Technical Note 3) of float32 rasters
+is undone block by block (td_tiff_unpredict_float). Other codecs (old-style JPEG, predictor 3 on float64, ...): whole image through Pillow.
 Whole rasters can instead be decoded on the GPU and kept in HBM (``decode_to_device``): LZW and DEFLATE (tiffdecode.hip; uint8 and
-native-order uint16 samples) and sequential-Huffman JPEG (jpegdecode.hip, byte-identical to the Pillow path) — see ``device_decodable``.
+native-order uint16 samples; native-order float32 height rasters, predictors 1 - 3, for callers that ask for them) and sequential-Huffman
+JPEG (jpegdecode.hip, byte-identical to the Pillow path) — see ``device_decodable``.
 """
 from __future__ import annotations
 
@@ -159,7 +161,7 @@ class GeoTiff:
         self._flat = None
         self._fd = None
         item = self.dtype.itemsize
-        if self.compression == 1 and self.planar == 1 and self._strips:
+        if self.compression == 1 and self.planar == 1 and self._strips and self._predictor != 3:
             row_bytes = W * self.count * item
             offs = self._offs
             if all(offs[i + 1] - offs[i] == self._bh * row_bytes for i in range(len(offs) - 1)):
@@ -171,9 +173,13 @@ class GeoTiff:
         if self.compression == 7 and self._jpeg_blocks_ok():
             tb = bytes(bytearray(int(v) for v in t.get(347, [])))
             self._jpeg_tables = tb if len(tb) >= 4 and tb[:2] == b"\xff\xd8" and tb[-2:] == b"\xff\xd9" else b""
-        elif self.compression not in (1, 5, 8, 32946, 32773) or self._predictor not in (1, 2):
+        elif self.compression not in (1, 5, 8, 32946, 32773) or not (self._predictor in (1, 2) or self._float_predictor()):
             self._pil_fallback()
         self._blocks_ready = True
+
+    def _float_predictor(self) -> bool:
+        """Predictor 3 on float32 samples (either byte order): undone per block by td_tiff_unpredict_float."""
+        return self._predictor == 3 and self.dtype.kind == "f" and self.dtype.itemsize == 4
 
     def _jpeg_blocks_ok(self) -> bool:
         """New-style JPEG blocks this reader decodes one by one: 8-bit chunky samples, grey or three bands (RGB or YCbCr)."""
@@ -206,7 +212,7 @@ class GeoTiff:
         return arr[:rows]
 
     def _pil_fallback(self) -> None:
-        """Codecs this reader does not implement (JPEG, floating-point predictor, ...): whole image through Pillow."""
+        """Codecs this reader does not implement (old-style JPEG, floating-point predictor on float64, ...): whole image through Pillow."""
         from PIL import Image
         Image.MAX_IMAGE_PIXELS = None
         arr = np.asarray(Image.open(self.path))
@@ -281,6 +287,11 @@ class GeoTiff:
             buf = buf[:n]
         if buf.size < nbytes:
             raise ValueError(f"{self.path}: block ({plane},{by},{bx}) decodes to {buf.size} bytes, expected {nbytes}")
+        if self._predictor == 3:                      # defined on the block's BYTES (planes, most significant first, in every file): undone
+            from . import _lib                        # before anything reads them as samples; the result is native floats
+            raw4 = np.array(buf[:nbytes], dtype=np.uint8)
+            _lib.check(_lib.load().td_tiff_unpredict_float(raw4.ctypes.data, rows, self._bw, cb, self.dtype.itemsize), "td_tiff_unpredict_float")
+            return raw4.view(np.float32).reshape(rows, self._bw, cb)
         blk = np.frombuffer(buf[:nbytes], dtype=self.dtype).reshape(rows, self._bw, cb)
         if self.dtype.byteorder not in ("=", "|"):     # file byte order differs from the host's
             blk = blk.astype(self.dtype.newbyteorder("="))
@@ -354,20 +365,22 @@ class GeoTiff:
         return out
 
     # -- compressed raster → HBM (tiffdecode.hip) --------------------------------------------------------------------------
-    def device_decodable(self) -> bool:
+    def device_decodable(self, float_samples: bool = False) -> bool:
         """True when the raster's blocks can be decoded on the GPU: LZW or DEFLATE (zlib) strips or tiles of pixel-interleaved
         uint8 or native-order (little-endian) uint16 samples (<= 4 per pixel), predictor 1 or 2; JPEG (compression 7) grey or
         three-band blocks when the host plan (td_tiff_jpeg_plan: sequential Huffman, 8-bit, 4:4:4 / 4:2:2 / 4:2:0) accepts every
-        one of them. Everything else keeps the host reader: big-endian and planar files, PackBits, int16 and float32 samples,
-        12-bit JPEG."""
+        one of them. ``float_samples=True`` (the height raster of the post-processing stage; the tile loop never asks) also admits
+        native-order float32 samples in the same LZW / DEFLATE layouts, predictor 1, 2 or 3 (floating-point predictor). Everything
+        else keeps the host reader: big-endian and planar files, PackBits, int16 / int32 and float64 samples, 12-bit JPEG."""
         self._setup_blocks()
         if self.compression == 7:
             if not (hasattr(self, "_jpeg_tables") and self._counts is not None and self._pil is None and self._flat is None):
                 return False
             plan = self._jpeg_plan()
             return plan is not None and int(plan[1][:, 1].max()) <= self.JPEG_DEVICE_MAX_SEGMENT
-        return (self.compression in (5, 8, 32946) and self.planar == 1 and self._device_samples() and 1 <= self.count <= 4
-                and self._predictor in (1, 2) and self._counts is not None and self._pil is None
+        f32 = float_samples and self.dtype.kind == "f" and self.dtype.itemsize == 4 and self.dtype.isnative
+        return (self.compression in (5, 8, 32946) and self.planar == 1 and (self._device_samples() or f32) and 1 <= self.count <= 4
+                and self._predictor in ((1, 2, 3) if f32 else (1, 2)) and self._counts is not None and self._pil is None
                 and self._bw * self._bh * self.count * self.dtype.itemsize < (1 << 31))
 
     def _device_samples(self) -> bool:
@@ -415,15 +428,15 @@ class GeoTiff:
         holds them, into pinned memory), copied to the device once, decoded one wave per block (td_tiff_lzw_decode_dev /
         td_tiff_inflate_verified_dev, which also checks every DEFLATE block's Adler-32 trailer as zlib does; JPEG: one lane per
         entropy-coded segment, td_tiff_jpeg_decode_dev, planned once by td_tiff_jpeg_plan) and
-        laid out as [height, width, bands] uint8 — or torch.uint16 for 16-bit rasters — with predictor 2 undone
-        (td_tiff_blocks_to_image_dev / td_tiff_blocks_to_image_u16_dev). → (image tensor, check) where ``check()`` waits for the kernels and raises ValueError when a block did not decode to its size
+        laid out as [height, width, bands] uint8 — or torch.uint16 for 16-bit rasters, torch.float32 for float32 rasters — with
+        predictor 2 (float32: or 3) undone (td_tiff_blocks_to_image_dev / td_tiff_blocks_to_image_u16_dev / td_tiff_blocks_to_image_f32_dev). → (image tensor, check) where ``check()`` waits for the kernels and raises ValueError when a block did not decode to its size
         or, DEFLATE, its bytes do not sum to the stream's checksum ("Adler-32 mismatch": the host reader's zlib raises on the same block) — the
         caller then falls back to the host reader. Everything is enqueued on ``stream`` (default: the current one). ``pinned``:
         a one-element list holding a pinned uint8 tensor to read the file into (grown and put back when too small — pinning
         hundreds of MB per image costs as much as reading them); ``pool``: threads the file read is spread over."""
         import torch
         from . import _lib
-        if not self.device_decodable():
+        if not self.device_decodable(float_samples=True):
             raise ValueError(f"{self.path}: not decodable on the device (compression {self.compression}, {self.dtype}, {self.count} bands)")
         lib = _lib.load()
         dev = torch.device(device)
@@ -483,9 +496,9 @@ class GeoTiff:
             else:
                 _lib.check(lib.td_tiff_inflate_verified_dev(comp.data_ptr(), meta[0].data_ptr(), meta[1].data_ptr(), nb, blocks.data_ptr(), block_cap,
                                                             decoded.data_ptr(), status.data_ptr(), ends.data_ptr(), st), "td_tiff_inflate_verified_dev")
-            image = torch.empty((self.height, self.width, self.count), dtype=torch.uint8 if item == 1 else torch.uint16, device=dev)
-            scatter, sname = ((lib.td_tiff_blocks_to_image_dev, "td_tiff_blocks_to_image_dev") if item == 1 else
-                              (lib.td_tiff_blocks_to_image_u16_dev, "td_tiff_blocks_to_image_u16_dev"))
+            image = torch.empty((self.height, self.width, self.count), dtype={1: torch.uint8, 2: torch.uint16, 4: torch.float32}[item], device=dev)
+            sname = {1: "td_tiff_blocks_to_image_dev", 2: "td_tiff_blocks_to_image_u16_dev", 4: "td_tiff_blocks_to_image_f32_dev"}[item]
+            scatter = getattr(lib, sname)
             _lib.check(scatter(blocks.data_ptr(), block_cap, self._bw, self._bh, self._nx, self._ny, self.count,
                                self._predictor, image.data_ptr(), self.width, self.height, st), sname)
             k1.record()
@@ -732,6 +745,17 @@ class GeoTiff:
         return np.ascontiguousarray(self.read_bounds_hwc(bounds).transpose(2, 0, 1))
 
 
+def device_decode_setting(value="auto"):
+    """The ``device_decode`` config key as both stages read it (the Predictor's tile loop, the post-processing stage's height raster):
+    true / false / "auto" / "all" → (use the device decoders, upload uncompressed rasters too). TD_DEVICE_DECODE (diagnostics: 0 |
+    false | all) overrides the default "auto"; anything else is refused."""
+    if value == "auto" and os.environ.get("TD_DEVICE_DECODE"):
+        value = {"0": False, "false": False, "all": "all"}.get(os.environ["TD_DEVICE_DECODE"], "auto")
+    if value not in (True, False, "auto", "true", "false", "all"):
+        raise ValueError(f"device_decode must be true, false, 'auto' or 'all', got {value!r}")
+    return value in (True, "auto", "true", "all"), value == "all"
+
+
 class _NullCtx:
     def __enter__(self):
         return self
@@ -782,8 +806,8 @@ def write_geotiff(path: str, data: np.ndarray, transform: Sequence[float], epsg:
     [rows, cols]; uint8 / uint16 / float32. Defaults: one uncompressed pixel-interleaved strip (what the tile reader
     maps without copying). Options: ``tile=(tile_rows, tile_cols)`` (multiples of 16) or ``rows_per_strip``,
     ``compression`` None / "deflate" / "lzw" (td_tiff_lzw_encode, blocks encoded on host threads) / "jpeg" (lossy; Pillow's encoder per
-    block), ``predictor`` 1 / 2
-    (horizontal differencing, integer samples), ``planar`` (one block grid per band). JPEG: ``jpeg_tables`` writes the GDAL / libtiff
+    block), ``predictor`` 1 / 2 (horizontal differencing; float32 samples are differenced as uint32, modulo 2^32, which is what libtiff's
+    32-bit accumulator undoes) / 3 (floating-point predictor, TIFF Technical Note 3: float32 only), ``planar`` (one block grid per band). JPEG: ``jpeg_tables`` writes the GDAL / libtiff
     layout (the quantisation and Huffman tables once, in the JPEGTables tag; abbreviated blocks without JFIF) instead of complete
     streams; ``jpeg_restart`` > 0 puts a restart marker every that many MCUs; ``jpeg_quality``, ``jpeg_subsampling`` (2 = 4:2:0,
     1 = 4:2:2, 0 = 4:4:4 for three bands)."""
@@ -794,8 +818,10 @@ def write_geotiff(path: str, data: np.ndarray, transform: Sequence[float], epsg:
     fmt = {np.dtype(np.uint8): (1, 8), np.dtype(np.uint16): (1, 16), np.dtype(np.float32): (3, 32)}[arr.dtype]
     if compression not in (None, "deflate", "lzw", "jpeg"):
         raise ValueError("compression must be None, 'deflate', 'lzw' or 'jpeg'")
-    if predictor not in (1, 2) or (predictor == 2 and fmt[0] != 1):
-        raise ValueError("predictor 2 needs integer samples")
+    if predictor not in (1, 2, 3):
+        raise ValueError("predictor must be 1, 2 or 3")
+    if predictor == 3 and fmt != (3, 32):
+        raise ValueError("predictor 3 (floating-point predictor) needs float32 samples")
     hwc = np.ascontiguousarray(arr.transpose(1, 2, 0)).astype(arr.dtype.newbyteorder("<"), copy=False)
     if tile:
         bh, bw = int(tile[0]), int(tile[1])
@@ -816,7 +842,15 @@ def write_geotiff(path: str, data: np.ndarray, transform: Sequence[float], epsg:
                 piece = src[by * bh:by * bh + rows, bx * bw:(bx + 1) * bw]
                 blk[:piece.shape[0], :piece.shape[1]] = piece
                 if predictor == 2:
-                    blk[:, 1:] = blk[:, 1:] - blk[:, :-1]          # modulo the sample width
+                    ints = blk.view("<u4") if fmt[0] == 3 else blk          # float32: the bit patterns, modulo 2^32
+                    ints[:, 1:] = ints[:, 1:] - ints[:, :-1]       # modulo the sample width
+                elif predictor == 3:
+                    # the samples' bytes in four planes per row, most significant first, then byte differences with the pixel stride
+                    # over the whole row of planes (libtiff's fpDiff)
+                    u = blk.view("<u4").reshape(rows, -1)
+                    row = np.concatenate([(u >> s & 255).astype(np.uint8) for s in (24, 16, 8, 0)], axis=1)
+                    row[:, src.shape[2]:] = row[:, src.shape[2]:] - row[:, :-src.shape[2]]
+                    blk = row
                 if compression == "jpeg":
                     blocks.append(_jpeg_block(blk, jpeg_quality, jpeg_subsampling, jpeg_restart))
                     continue
@@ -859,8 +893,8 @@ def write_geotiff(path: str, data: np.ndarray, transform: Sequence[float], epsg:
     add(262, 3, [(6 if compression == "jpeg" else 2) if C >= 3 else 1])
     add(277, 3, [C])
     add(284, 3, [2 if planar else 1])
-    if predictor == 2:
-        add(317, 3, [2])
+    if predictor != 1:
+        add(317, 3, [predictor])
     if tile:
         add(322, 4, [bw])
         add(323, 4, [bh])

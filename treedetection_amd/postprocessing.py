@@ -26,7 +26,7 @@ import torch
 import yaml
 
 from . import _lib
-from .geotiff import GeoTiff
+from .geotiff import GeoTiff, device_decode_setting
 from .gpkg import polygon_blob, read_layer, write_blobs
 from .stitching import simplify_ring
 
@@ -134,27 +134,34 @@ def crown_circles(rings: Sequence[np.ndarray]) -> np.ndarray:
     return out
 
 
-def crown_stats(raster: np.ndarray, transform, bounds, circles: np.ndarray, mode: int, radius_scale: float = 1.0,
+def crown_stats(raster, transform, bounds, circles: np.ndarray, mode: int, radius_scale: float = 1.0,
                 device: int = 0, clamp_shape: Optional[Tuple[int, int]] = None) -> np.ndarray:
-    """td_crown_stats over one raster → [n,3] (mode 0: max height, x, y) or [n,4] (mode 1: NDVI min, max, mean, var)."""
+    """td_crown_stats over one raster → [n,3] (mode 0: max height, x, y) or [n,4] (mode 1: NDVI min, max, mean, var).
+    ``raster``: a numpy array [rows, cols] (copied to ``device``), or a contiguous float32 CUDA tensor [rows, cols] (a raster
+    decoded in HBM, GeoTiff.decode_to_device), which the kernel reads where it lies."""
     n = circles.shape[0]
     cols_out = 3 if mode == 0 else 4
     if n == 0:
         return np.zeros((0, cols_out), np.float32)
+    on_device = isinstance(raster, torch.Tensor)
+    if on_device and not (raster.is_cuda and raster.dtype == torch.float32 and raster.dim() == 2 and raster.is_contiguous()):
+        raise ValueError(f"crown_stats: a raster tensor must be a contiguous float32 CUDA tensor [rows, cols], got {raster.dtype} "
+                         f"{tuple(raster.shape)} on {raster.device}")
     rows, cols = raster.shape
     cr, cc = clamp_shape if clamp_shape else (rows, cols)
     r_lo, c_lo, r_hi, c_hi = _window(transform, cr, cc, bounds)
     r_hi, c_hi = min(r_hi, rows - 1), min(c_hi, cols - 1)
     lib = _lib.load()
     import ctypes as C
-    dev = torch.device("cuda", device)
-    d_r = torch.from_numpy(np.ascontiguousarray(raster, dtype=np.float32)).to(dev)
+    dev = raster.device if on_device else torch.device("cuda", device)
+    d_r = raster if on_device else torch.from_numpy(np.ascontiguousarray(raster, dtype=np.float32)).to(dev)
     d_c = torch.from_numpy(np.ascontiguousarray(circles, dtype=np.float32)).to(dev)
     d_o = torch.empty((n, cols_out), dtype=torch.float32, device=dev)
     tr = (C.c_double * 6)(*[float(v) for v in transform[:6]])
     win = (C.c_int32 * 4)(r_lo, c_lo, r_hi, c_hi)
-    _lib.check(lib.td_crown_stats(d_r.data_ptr(), rows, cols, tr, win, d_c.data_ptr(), n, mode, float(radius_scale),
-                                  d_o.data_ptr(), _lib.stream_ptr()), "td_crown_stats")
+    with torch.cuda.device(dev):
+        _lib.check(lib.td_crown_stats(d_r.data_ptr(), rows, cols, tr, win, d_c.data_ptr(), n, mode, float(radius_scale),
+                                      d_o.data_ptr(), _lib.stream_ptr()), "td_crown_stats")
     return d_o.cpu().numpy()
 
 
@@ -220,6 +227,27 @@ def _round_ring(ring: np.ndarray) -> np.ndarray:
     return np.array([[round(float(c) * 1000) / 1000 for c in pt] for pt in ring], dtype=np.float64)
 
 
+def _height_on_device(hg: GeoTiff, h_scale: float, config, device: int):
+    """The height raster decoded in HBM (GeoTiff.decode_to_device → float32 CUDA tensor [rows, cols], which td_crown_stats reads
+    where it lies: no inflate on the host, no copy of the array), or None when the host reader has to serve it: ``device_decode``
+    is not explicitly true / "all" (the default "auto" keeps the host reader for this raster until both paths have been timed), the raster is not a single-band native float32 LZW / DEFLATE raster (``device_decodable(float_samples=True)``), the
+    scaling factor resamples it (resampling is host numpy), or a block turns out corrupt (printed, like the prediction stage)."""
+    value = config.get("device_decode", "auto")
+    device_decode_setting("auto" if value is None else value)       # (refuses what the Predictor refuses)
+    if value not in (True, "true", "all"):                          # opt-in: "auto" keeps the host reader, the two paths are untimed (DESIGN.md §7)
+        return None
+    if hg.count != 1 or (int(hg.height * h_scale), int(hg.width * h_scale)) != (hg.height, hg.width):
+        return None
+    if not hg.device_decodable(float_samples=True):
+        return None
+    try:
+        _, check = hg.decode_to_device(torch.device("cuda", device))
+        return check().view(hg.height, hg.width)
+    except ValueError as e:
+        print(f"device decode of {hg.path} failed ({e}): using the host reader")
+        return None
+
+
 # ---- one layer -----------------------------------------------------------------------------------------
 def process_layer(rings: List[np.ndarray], scores: Sequence[Optional[float]], config, height_path: str, rgbi_path: str,
                   device: int = 0) -> List[dict]:
@@ -242,8 +270,10 @@ def process_layer(rings: List[np.ndarray], scores: Sequence[Optional[float]], co
     feats = [f for f in feats if area_thr <= f["area"] <= 1000]
     # rasters, decimated by the scaling factors (postprocessing.py:780-797): transform scaled by src / out size
     hg = GeoTiff(height_path)
-    hraw = hg.read()[:1]
-    height = resample_bilinear_gdal(hraw, int(hg.height * h_scale), int(hg.width * h_scale))[0].astype(np.float32)
+    height = _height_on_device(hg, h_scale, config, device)
+    if height is None:
+        hraw = hg.read()[:1]
+        height = resample_bilinear_gdal(hraw, int(hg.height * h_scale), int(hg.width * h_scale))[0].astype(np.float32)
     h_t = (hg.transform[0] * (hg.width / height.shape[1]), hg.transform[1], hg.transform[2],
            hg.transform[3], hg.transform[4] * (hg.height / height.shape[0]), hg.transform[5])
     h_b = hg.bounds                                       # bounds: left, bottom, right, top

@@ -24,7 +24,7 @@ from . import _lib
 from . import distributed as D
 from .contours import batch_prediction_files, find_contours, tile_polygons_json, tile_polygons_json_dev, tile_prediction_file, xy
 from .engine import Engine, INPUT_F32_CHW, INPUT_U8_HWC
-from .geotiff import GeoTiff
+from .geotiff import GeoTiff, device_decode_setting
 from .weights import load_checkpoint
 
 
@@ -202,16 +202,12 @@ class Predictor:
         self.cfg = cfg
         # LZW, DEFLATE and JPEG rasters are decoded on the GPU, whole, and their tile windows are cut in HBM (GeoTiff.decode_to_device;
         # images this process predicts alone: submit). "auto" / True: every raster that qualifies; False: the host reader for everything
-        if device_decode == "auto" and os.environ.get("TD_DEVICE_DECODE"):       # diagnostics: override the default
-            device_decode = {"0": False, "false": False, "all": "all"}.get(os.environ["TD_DEVICE_DECODE"], "auto")
-        if device_decode not in (True, False, "auto", "true", "false", "all"):
-            raise ValueError(f"device_decode must be true, false, 'auto' or 'all', got {device_decode!r}")
-        self.device_decode = device_decode in (True, "auto", "true", "all")
+        # (TD_DEVICE_DECODE overrides the default; the post-processing stage reads the same key the same way)
         # "all": uncompressed uint8 rasters are kept whole in HBM too (uploaded in 4-MB pieces). Measured both ways (round 6,
         # tools/host_cost.py, profiles/r06_host_cost.txt): on a 256-thread host with slow page-cache reads +10 % tiles/s and -30 % host CPU
         # per tile; on a 16-core host -20 % (the upload's reader threads compete with the epilogue workers, and an image that was not
         # prefetched waits for its whole raster before its first batch) — so the default keeps the per-window host reader for them
-        self.device_upload = device_decode == "all"
+        self.device_decode, self.device_upload = device_decode_setting(device_decode)
         self._rasters: Dict[str, "object"] = {}
         self._raster_pool = None
         self._decode_stream = None
@@ -383,7 +379,8 @@ class Predictor:
         predicts. ``detection.walk_images`` calls it with the path after the one it submits. uint8 and little-endian uint16 rasters
         qualify (a 16-bit raster stays in HBM as uint16 and its windows become the model's float input there:
         Engine.preprocess_windows_u16). No-op for rasters the host reader serves (PackBits, planar and big-endian files, int16 and
-        float32 samples, JPEG blocks the device decoder does not take) and when ``device_decode`` is off."""
+        float32 samples — ``device_decodable()`` is asked without ``float_samples``: float32 rasters are decoded on the device only
+        for the post-processing stage — JPEG blocks the device decoder does not take) and when ``device_decode`` is off."""
         if not self.device_decode or tifpath in self._rasters:
             return
         if self._raster_pool is None:
