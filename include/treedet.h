@@ -495,6 +495,28 @@ int td_region_relate(const double* ring_xy, const int64_t* ring_start, const int
 td_status td_crown_stats(const float* raster, int rows, int cols, const double* transform, const int32_t* window,
                          const float* circles, int n, int mode, float radius_scale, float* out, void* stream);
 
+/* GDAL's separable triangle-filter resampling (src.read(out_shape=..., resampling=bilinear), reference postprocessing.py:781-797)
+ * of a raster that lies in device memory, with the NDVI rule of helpers.ndvi_array_from_rgbi (880-895) fused into the second pass.
+ * src: DEVICE uint8 [height][width][c] pixel-interleaved (TD_SAMPLE_U8, c <= 4) or DEVICE float32 [height][width] (TD_SAMPLE_F32,
+ * c = 1). bands: HOST list of n_bands <= 4 band indices < c — only these are computed. The filter taps are the caller's, one table
+ * per axis in DEVICE memory: output j of the axis is the sum over k < count[j] of sample[start[j] + k] * weights[offset[j] + k],
+ * accumulated in float32 in ascending k, multiply and add rounded separately; start / count / offset int32 [n_dst] (n_dst = out_w
+ * for the x tables, out_h for the y tables), weights float32 [n_weights]. The caller guarantees start >= 0, count >= 1,
+ * start + count <= the source size of the axis and offset + count <= n_weights (device memory is not read by the checks of this
+ * call; the kernels ignore what lies outside). tmp: DEVICE float32 [n_bands][height][out_w], the first pass's result.
+ * dst by mode: TD_RESAMPLE_F32 float32 [n_bands][out_h][out_w]; TD_RESAMPLE_U8 uint8 [n_bands][out_h][out_w] =
+ * clip(floor(v + 0.5), 0, 255); TD_RESAMPLE_NDVI (exactly two bands: red, near-infrared) float32 [out_h][out_w] = both rounded to
+ * uint8 as in mode u8, then (nir / 255 - red / 255) / (nir / 255 + red / 255 + 1e-10) in float64, rounded once. Modes u8 and ndvi
+ * take uint8 sources only. Returns TD_ERR_INVALID (with a message, before any launch) for a null pointer, a bad shape, sample type
+ * or mode, a band index >= c, or a mode / band count / sample type combination outside the above. Asynchronous on `stream`. */
+enum { TD_SAMPLE_U8 = 0, TD_SAMPLE_F32 = 1 };
+enum { TD_RESAMPLE_F32 = 0, TD_RESAMPLE_U8 = 1, TD_RESAMPLE_NDVI = 2 };
+td_status td_resample_gdal_dev(const void* src, int sample_type, int height, int width, int c, const int32_t* bands, int n_bands,
+                               const int32_t* x_start, const int32_t* x_count, const int32_t* x_offset, const float* x_weights,
+                               int out_w, int64_t x_n_weights, const int32_t* y_start, const int32_t* y_count,
+                               const int32_t* y_offset, const float* y_weights, int out_h, int64_t y_n_weights, float* tmp,
+                               void* dst, int mode, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

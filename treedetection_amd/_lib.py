@@ -20,6 +20,8 @@ ERR_CAPACITY = -4   # TD_ERR_CAPACITY
 ERR_STATE = -5      # TD_ERR_STATE
 ERR_UNSUPPORTED = -6  # TD_ERR_UNSUPPORTED
 JPEG_TABSET_BYTES = 8928  # TD_JPEG_TABSET_BYTES: one table set of td_tiff_jpeg_plan
+SAMPLE_U8, SAMPLE_F32 = 0, 1                          # TD_SAMPLE_*: source of td_resample_gdal_dev
+RESAMPLE_MODES = {"f32": 0, "u8": 1, "ndvi": 2}       # TD_RESAMPLE_*: its output modes
 
 
 class TdError(RuntimeError):
@@ -86,6 +88,9 @@ SIGNATURES = {
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "td_crown_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_void_p, C.c_int,
                                  C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    "td_resample_gdal_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int]
+                             + [C.c_void_p] * 4 + [C.c_int, C.c_int64] + [C.c_void_p] * 4 + [C.c_int, C.c_int64]
+                             + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "td_trace_contours_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                         C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "td_find_contours": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),

@@ -8,7 +8,8 @@ are one launch of ``td_crown_stats`` per raster (libtreedet_hip.so; a workgroup 
 box, same membership arithmetic); the N x N box filters and the selection rules are small host numpy, written to follow
 the reference line by line *including* its quirks, which are listed in DESIGN.md §7 and marked ``# ref:`` below.
 GDAL's bilinear decimation of the rasters (``ndvi_scaling_factor`` 0.2 in the example config) is restated from its
-published algorithm (:func:`resample_bilinear_gdal`, both directions). Not reproduced: fiona's
+published algorithm (:func:`resample_bilinear_gdal`, both directions); with ``device_decode: true`` the rasters are decoded in
+HBM and the same taps are applied there, NDVI included (:func:`resample_on_device`, ``td_resample_gdal_dev``). Not reproduced: fiona's
 schema handling (the layer is written by
 :mod:`treedetection_amd.gpkg`), and cupy's float32 reduction order for mean / variance / centroid (accumulated in
 float64, rounded once). The reference holds no fixture for this stage: parity is unpinned (oracle/postprocess_ref.py).
@@ -121,6 +122,79 @@ def ndvi_from_rgbi(rgbi: np.ndarray) -> np.ndarray:
     return (nir - red) / (nir + red + 1e-10)
 
 
+def tap_tables(n_src: int, n_dst: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """:func:`_decimation_weights` of one axis flattened for td_resample_gdal_dev: (start[n_dst], count[n_dst], offset[n_dst]) int32
+    and one float32 weight array — output j sums ``src[start[j] + k] * weights[offset[j] + k]`` over ``k < count[j]``. The weights
+    are ``wgt.astype(np.float32)``, what :func:`resample_bilinear_gdal` multiplies by; the taps of an output are consecutive source
+    indices."""
+    rows = _decimation_weights(n_src, n_dst)
+    start = np.array([int(idx[0]) for idx, _ in rows], dtype=np.int32)
+    count = np.array([len(idx) for idx, _ in rows], dtype=np.int32)
+    offset = (np.cumsum(count, dtype=np.int64) - count).astype(np.int32)
+    weights = np.concatenate([wgt.astype(np.float32) for _, wgt in rows])
+    return start, count, offset, weights
+
+
+def check_tap_tables(table, n_src: int, n_dst: int, axis: str = "") -> None:
+    """Refuses (ValueError) a tap table that td_resample_gdal_dev must not see: wrong lengths or types, ``count < 1``, ``start < 0``,
+    ``start + count > n_src`` (a tap outside the source) or ``offset + count`` outside the weight array. Host numpy only."""
+    start, count, offset, weights = table
+    for name, a in (("start", start), ("count", count), ("offset", offset)):
+        if not (isinstance(a, np.ndarray) and a.dtype == np.int32 and a.shape == (n_dst,)):
+            raise ValueError(f"{axis} tap table: {name} must be an int32 array of {n_dst} entries")
+    if not (isinstance(weights, np.ndarray) and weights.dtype == np.float32 and weights.ndim == 1 and weights.size >= 1):
+        raise ValueError(f"{axis} tap table: the weights must be a float32 vector")
+    s, c, o = start.astype(np.int64), count.astype(np.int64), offset.astype(np.int64)
+    if n_dst < 1 or (c < 1).any() or (s < 0).any() or (s + c > n_src).any():
+        raise ValueError(f"{axis} tap table reaches outside the {n_src} source samples (start >= 0, count >= 1, start + count <= {n_src})")
+    if (o < 0).any() or (o + c > weights.size).any():
+        raise ValueError(f"{axis} tap table reaches outside its {weights.size} weights")
+
+
+def resample_on_device(tensor: torch.Tensor, out_h: int, out_w: int, bands: Sequence[int], mode: str, tables=None) -> torch.Tensor:
+    """:func:`resample_bilinear_gdal` of a raster that lies in HBM (td_resample_gdal_dev, resample.hip: the same taps, float32
+    accumulation in ascending tap order). ``tensor``: a contiguous CUDA tensor, uint8 [rows, cols, bands] (what
+    GeoTiff.decode_to_device returns) or float32 [rows, cols]; ``bands``: the band indices to compute (at most four). ``mode``:
+    "f32" → float32 [len(bands), out_h, out_w]; "u8" → uint8, rounded half up and clamped (the host rule for integer rasters);
+    "ndvi" (two bands: red, near-infrared) → float32 [out_h, out_w] = ``ndvi_from_rgbi`` of the two rounded bands, rounded once.
+    The same size runs the same kernels with :func:`_decimation_weights`'s identity taps (weights 1, 0). ``tables``: (x table, y
+    table) as :func:`tap_tables` returns them, instead of the GDAL taps; they are validated on the host before anything is uploaded."""
+    if mode not in _lib.RESAMPLE_MODES:
+        raise ValueError(f"resample_on_device: mode must be one of {sorted(_lib.RESAMPLE_MODES)}, got {mode!r}")
+    what = "resample_on_device: the raster must be a contiguous CUDA tensor, uint8 [rows, cols, bands] or float32 [rows, cols]"
+    if not (isinstance(tensor, torch.Tensor) and tensor.is_contiguous()
+            and ((tensor.dtype == torch.uint8 and tensor.dim() == 3) or (tensor.dtype == torch.float32 and tensor.dim() == 2))):
+        raise ValueError(what)
+    h, w = int(tensor.shape[0]), int(tensor.shape[1])
+    c = int(tensor.shape[2]) if tensor.dim() == 3 else 1
+    out_h, out_w = int(out_h), int(out_w)
+    if out_h < 1 or out_w < 1:
+        raise ValueError(f"cannot resample a {h} x {w} raster to {out_h} x {out_w}")
+    xt, yt = tables if tables is not None else (tap_tables(w, out_w), tap_tables(h, out_h))
+    check_tap_tables(xt, w, out_w, "x")
+    check_tap_tables(yt, h, out_h, "y")
+    if not tensor.is_cuda:                                  # (after the tables: their validation needs no device)
+        raise ValueError(what)
+    import ctypes as C
+    lib = _lib.load()
+    dev = tensor.device
+    nb = len(bands)
+    band_list = (C.c_int32 * max(nb, 1))(*[int(b) for b in bands])
+    with torch.cuda.device(dev):
+        d_x = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in xt]
+        d_y = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in yt]
+        tmp = torch.empty((max(nb, 1), h, out_w), dtype=torch.float32, device=dev)
+        if mode == "ndvi":
+            dst = torch.empty((out_h, out_w), dtype=torch.float32, device=dev)
+        else:
+            dst = torch.empty((max(nb, 1), out_h, out_w), dtype=torch.float32 if mode == "f32" else torch.uint8, device=dev)
+        _lib.check(lib.td_resample_gdal_dev(tensor.data_ptr(), _lib.SAMPLE_U8 if tensor.dtype == torch.uint8 else _lib.SAMPLE_F32, h, w, c,
+                                            band_list, nb, *[a.data_ptr() for a in d_x], out_w, xt[3].size,
+                                            *[a.data_ptr() for a in d_y], out_h, yt[3].size, tmp.data_ptr(), dst.data_ptr(),
+                                            _lib.RESAMPLE_MODES[mode], _lib.stream_ptr()), "td_resample_gdal_dev")
+    return dst      # (tmp and the tables go back to torch's allocator on the stream the kernels run on: reuse is ordered after them)
+
+
 def crown_circles(rings: Sequence[np.ndarray]) -> np.ndarray:
     """[n,3] float32 (cx, cy, r): centre of the bounding box of the float32 vertex coordinates and the largest vertex
     distance from it (postprocessing.py:79-95)."""
@@ -229,23 +303,54 @@ def _round_ring(ring: np.ndarray) -> np.ndarray:
 
 def _height_on_device(hg: GeoTiff, h_scale: float, config, device: int):
     """The height raster decoded in HBM (GeoTiff.decode_to_device → float32 CUDA tensor [rows, cols], which td_crown_stats reads
-    where it lies: no inflate on the host, no copy of the array), or None when the host reader has to serve it: ``device_decode``
-    is not explicitly true / "all" (the default "auto" keeps the host reader for this raster until both paths have been timed), the raster is not a single-band native float32 LZW / DEFLATE raster (``device_decodable(float_samples=True)``), the
-    scaling factor resamples it (resampling is host numpy), or a block turns out corrupt (printed, like the prediction stage)."""
-    value = config.get("device_decode", "auto")
-    device_decode_setting("auto" if value is None else value)       # (refuses what the Predictor refuses)
-    if value not in (True, "true", "all"):                          # opt-in: "auto" keeps the host reader, the two paths are untimed (DESIGN.md §7)
+    where it lies: no inflate on the host, no copy of the array) and, when ``height_scaling_factor`` shrinks it, decimated there
+    (:func:`resample_on_device`, mode "f32"); or None when the host reader has to serve it: ``device_decode``
+    is not explicitly true / "all" (the default "auto" keeps the host reader for this raster: DESIGN.md §7), the raster is not a single-band native float32 LZW / DEFLATE raster (``device_decodable(float_samples=True)``), the
+    scaling factor enlarges it (a factor above 1 stays host numpy), or a block turns out corrupt (printed, like the prediction stage)."""
+    if not _device_decode_on(config):
         return None
-    if hg.count != 1 or (int(hg.height * h_scale), int(hg.width * h_scale)) != (hg.height, hg.width):
+    out_h, out_w = int(hg.height * h_scale), int(hg.width * h_scale)
+    if hg.count != 1 or not (1 <= out_h <= hg.height and 1 <= out_w <= hg.width):
         return None
     if not hg.device_decodable(float_samples=True):
         return None
     try:
         _, check = hg.decode_to_device(torch.device("cuda", device))
-        return check().view(hg.height, hg.width)
+        height = check().view(hg.height, hg.width)
     except ValueError as e:
         print(f"device decode of {hg.path} failed ({e}): using the host reader")
         return None
+    if (out_h, out_w) == (hg.height, hg.width):             # same shape = the raster itself, as resample_bilinear_gdal returns it
+        return height
+    return resample_on_device(height, out_h, out_w, [0], "f32")[0]
+
+
+def _device_decode_on(config) -> bool:
+    """``device_decode`` explicitly true / "all": the crown stage's rasters take the device path. "auto", the default, keeps the
+    host reader for them (nothing has decided otherwise: DESIGN.md §7). Refuses what the Predictor refuses."""
+    value = config.get("device_decode", "auto")
+    device_decode_setting("auto" if value is None else value)
+    return value in (True, "true", "all")
+
+
+def _ndvi_on_device(rg: GeoTiff, n_scale: float, config, device: int):
+    """The NDVI raster of the crown statistics computed in HBM: the RGBI raster decoded there (GeoTiff.decode_to_device), bands 0 and
+    3 resampled to [int(rows * n_scale), int(cols * n_scale)] and turned into NDVI by one call of td_resample_gdal_dev (mode "ndvi";
+    with ``n_scale`` 1 the same kernels run with identity taps) → float32 CUDA tensor for :func:`crown_stats`. None when the host
+    reader has to serve it, by the gating of :func:`_height_on_device`: ``device_decode`` not explicitly true / "all", a raster that
+    is not uint8 with four bands in a layout the device decoders take (LZW / DEFLATE, pixel-interleaved), or a corrupt block (printed)."""
+    if not _device_decode_on(config):
+        return None
+    out_h, out_w = int(rg.height * n_scale), int(rg.width * n_scale)
+    if rg.dtype != np.uint8 or rg.count < 4 or out_h < 1 or out_w < 1 or not rg.device_decodable():
+        return None
+    try:
+        _, check = rg.decode_to_device(torch.device("cuda", device))
+        rgbi = check()
+    except ValueError as e:
+        print(f"device decode of {rg.path} failed ({e}): using the host reader")
+        return None
+    return resample_on_device(rgbi, out_h, out_w, [0, 3], "ndvi")
 
 
 # ---- one layer -----------------------------------------------------------------------------------------
@@ -278,9 +383,11 @@ def process_layer(rings: List[np.ndarray], scores: Sequence[Optional[float]], co
            hg.transform[3], hg.transform[4] * (hg.height / height.shape[0]), hg.transform[5])
     h_b = hg.bounds                                       # bounds: left, bottom, right, top
     rg = GeoTiff(rgbi_path)
-    rraw = rg.read()
-    rgbi = resample_bilinear_gdal(rraw, int(rg.height * n_scale), int(rg.width * n_scale))
-    ndvi = ndvi_from_rgbi(rgbi).astype(np.float32)
+    ndvi = _ndvi_on_device(rg, n_scale, config, device)
+    if ndvi is None:
+        rraw = rg.read()
+        rgbi = resample_bilinear_gdal(rraw, int(rg.height * n_scale), int(rg.width * n_scale))
+        ndvi = ndvi_from_rgbi(rgbi).astype(np.float32)
     orig_t = rg.transform
     n_t = (orig_t[0] * (rg.width / ndvi.shape[1]), orig_t[1], orig_t[2], orig_t[3], orig_t[4] * (rg.height / ndvi.shape[0]), orig_t[5])
     n_b = rg.bounds
