@@ -517,6 +517,38 @@ td_status td_resample_gdal_dev(const void* src, int sample_type, int height, int
                                const int32_t* y_offset, const float* y_weights, int out_h, int64_t y_n_weights, float* tmp,
                                void* dst, int mode, void* stream);
 
+/* ---- the crown stage's box-pair filters (reference postprocessing.py:349-476) without their N x N matrices ----
+ * boxes: DEVICE float32 [n][4] (x1, y1, x2, y2), 16-byte aligned; areas_f16: DEVICE float16 [n], the polygon areas. All arithmetic is
+ * the reference's, each operation rounded on its own: connected(i, j) = iou > iou_threshold in float32 (inter / ((area_i + area_j) -
+ * inter), IEEE division) AND |a_i - a_j| / max(a_i, a_j) < area_threshold_f16 on the float16 areas, rounded to half after every
+ * operation as numpy does (thresholds: a float32 and a float16 bit pattern); containment ratio[i][j] = inter / area_j in float32,
+ * compared >= containment_threshold. Pairs of disjoint boxes are skipped, which changes nothing when every coordinate is finite,
+ * every float32 box area finite and positive, iou_threshold >= 0 and containment_threshold > 0 — the CALLER's preconditions, not
+ * checked here (device memory is not read by the checks of these calls).
+ * td_crown_pairs_count: counts int32 [n] = connected j != i per row (NULL: containment only; needs areas_f16 otherwise);
+ * num_contained int32 [n] = j != i with ratio[i][j] >= threshold and is_contained int32 [n] = 0 / 1, any i' != i with
+ * ratio[i'][i] >= threshold (both NULL: de-duplication only). The outputs are zeroed on `stream` by the call.
+ * td_crown_pairs_fill: row_start DEVICE int64 [n + 1] = exclusive prefix sum of counts; cols int32 [row_start[n]] receives the
+ * connected column indices of row i in [row_start[i], row_start[i + 1]), in no particular order; cursor: int32 [n] of scratch.
+ * Same boxes, areas and thresholds as the count pass, which ran the same pair test.
+ * Both return TD_ERR_INVALID (with a message, before any launch) for a null pointer, a misaligned boxes pointer, n < 1 or
+ * n > 67 107 840 (65 535 column chunks of 1 024 crowns, the launch grid's second dimension).
+ * Asynchronous on `stream`. */
+td_status td_crown_pairs_count(const float* boxes, const uint16_t* areas_f16, int n, float iou_threshold, uint16_t area_threshold_f16,
+                               int32_t* counts, float containment_threshold, int32_t* num_contained, int32_t* is_contained,
+                               void* stream);
+td_status td_crown_pairs_fill(const float* boxes, const uint16_t* areas_f16, int n, float iou_threshold, uint16_t area_threshold_f16,
+                              const int64_t* row_start, int32_t* cursor, int32_t* cols, void* stream);
+/* The greedy pass of the de-duplication over those rows (HOST memory throughout, host code, O(n + edges)): rows in index order; a
+ * removed row is skipped; of a row's members and the row itself the one with the highest float16 confidence (conf_f16: bit
+ * patterns, no NaN) stays and every other one is marked in removed uint8 [n] (removed members still vote in later groups). Ties
+ * go as the reference's argmax over "ascending members, then the row itself" does: the smallest index among the members; the row
+ * itself takes part at its own index when the mask's diagonal holds for it (self_connected uint8 [n]; NULL = it holds for every
+ * row; a row that lists itself in cols says the same) and otherwise wins only when strictly higher. The order inside a row does
+ * not matter. TD_ERR_INVALID for a null pointer, n < 0, a decreasing row_start or a column outside [0, n). */
+int td_crown_pairs_greedy(const int64_t* row_start, const int32_t* cols, const uint16_t* conf_f16, const uint8_t* self_connected,
+                          int n, uint8_t* removed);
+
 #ifdef __cplusplus
 }
 #endif

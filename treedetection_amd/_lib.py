@@ -91,6 +91,10 @@ SIGNATURES = {
     "td_resample_gdal_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int]
                              + [C.c_void_p] * 4 + [C.c_int, C.c_int64] + [C.c_void_p] * 4 + [C.c_int, C.c_int64]
                              + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "td_crown_pairs_count": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_uint16, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
+    "td_crown_pairs_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_uint16, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "td_crown_pairs_greedy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "td_trace_contours_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                         C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "td_find_contours": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),

@@ -6,7 +6,9 @@ layers — the only consumer of the nDSM side band.
 What runs where: the per-crown raster statistics — in the reference a cupy test of every crown against EVERY pixel —
 are one launch of ``td_crown_stats`` per raster (libtreedet_hip.so; a workgroup per crown over its circle's bounding
 box, same membership arithmetic); the N x N box filters and the selection rules are small host numpy, written to follow
-the reference line by line *including* its quirks, which are listed in DESIGN.md §7 and marked ``# ref:`` below.
+the reference line by line *including* its quirks, which are listed in DESIGN.md §7 and marked ``# ref:`` below; with
+``device_filters: true`` the pair tests of the two box filters run on the GPU and only the sparse result comes back
+(``td_crown_pairs_count`` / ``td_crown_pairs_fill``, crownpairs.hip; same arithmetic, same results).
 GDAL's bilinear decimation of the rasters (``ndvi_scaling_factor`` 0.2 in the example config) is restated from its
 published algorithm (:func:`resample_bilinear_gdal`, both directions); with ``device_decode: true`` the rasters are decoded in
 HBM and the same taps are applied there, NDVI included (:func:`resample_on_device`, ``td_resample_gdal_dev``). Not reproduced: fiona's
@@ -291,6 +293,152 @@ def containment(bounds, threshold):
     return ([float(ratios[:, j].max()) for j in range(n)], [bool(is_c[:, j].any()) for j in range(n)], [int(v) for v in num])
 
 
+# ---- the same two filters with the pair tests on the GPU (crownpairs.hip; opt-in: ``device_filters: true``) ------------------
+MAX_DEVICE_PAIRS = 1 << 27      # connected pairs the device path stores (512 MB of int32 indices); beyond it the host function serves
+
+
+def _decline(who: str, why: str) -> None:
+    print(f"{who}: {why}: using the host function")
+
+
+def _boxes_declined(bb: np.ndarray) -> Optional[str]:
+    """Why the pair kernels must not see these float32 boxes (they skip disjoint pairs, which is only the reference's answer for
+    finite boxes of finite positive area), or None."""
+    if not np.isfinite(bb).all():
+        return "a box coordinate is not finite"
+    with np.errstate(over="ignore", invalid="ignore"):
+        area = (bb[:, 2] - bb[:, 0]) * (bb[:, 3] - bb[:, 1])
+    if not (np.isfinite(area) & (area > 0)).all():
+        return "a box has no finite positive float32 area"
+    return None
+
+
+def _weak_threshold(threshold, dtype):
+    """``threshold`` in the type numpy compares an array of ``dtype`` with it in — ``dtype`` itself for a Python number (and for a
+    numpy scalar that does not widen it) — or None when the comparison would run in a wider type than the kernels compute in."""
+    if np.result_type(dtype, threshold) != dtype:
+        return None
+    with np.errstate(over="ignore"):
+        return dtype(threshold)
+
+
+def connected_pairs_device(bb: np.ndarray, ar: np.ndarray, iou_thr: np.float32, area_thr: np.float16, device: int = 0):
+    """The de-duplication mask of :func:`filter_polygons_by_iou_and_area` as sparse rows: (row_start int64 [n + 1], cols int32
+    [row_start[n]]) — the j != i with ``mask[i][j]``, row i in ``cols[row_start[i]:row_start[i + 1]]`` in no particular order — or
+    None when there are more than MAX_DEVICE_PAIRS of them. td_crown_pairs_count, a prefix sum, td_crown_pairs_fill. ``bb``: float32
+    [n, 4], n >= 1; ``ar``: float16 [n]. The preconditions are the caller's (:func:`filter_polygons_by_iou_and_area_device`)."""
+    n = bb.shape[0]
+    lib = _lib.load()
+    dev = torch.device("cuda", device)
+    with torch.cuda.device(dev):
+        d_b = torch.from_numpy(np.ascontiguousarray(bb, dtype=np.float32)).to(dev)
+        d_a = torch.from_numpy(np.ascontiguousarray(ar, dtype=np.float16)).to(dev)
+        counts = torch.empty(n, dtype=torch.int32, device=dev)
+        thr_bits = int(np.float16(area_thr).view(np.uint16))
+        _lib.check(lib.td_crown_pairs_count(d_b.data_ptr(), d_a.data_ptr(), n, float(np.float32(iou_thr)), thr_bits, counts.data_ptr(),
+                                            0.0, None, None, _lib.stream_ptr()), "td_crown_pairs_count")
+        row_start = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(counts, 0, dtype=torch.int64, out=row_start[1:])
+        total = int(row_start[-1].item())
+        if total > MAX_DEVICE_PAIRS:
+            return None
+        cols = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
+        if total:
+            cursor = torch.empty(n, dtype=torch.int32, device=dev)
+            _lib.check(lib.td_crown_pairs_fill(d_b.data_ptr(), d_a.data_ptr(), n, float(np.float32(iou_thr)), thr_bits, row_start.data_ptr(),
+                                               cursor.data_ptr(), cols.data_ptr(), _lib.stream_ptr()), "td_crown_pairs_fill")
+        return row_start.cpu().numpy(), cols[:total].cpu().numpy()
+
+
+def greedy_removal(row_start: np.ndarray, cols: np.ndarray, conf: np.ndarray, self_connected: Optional[np.ndarray] = None) -> np.ndarray:
+    """td_crown_pairs_greedy: the group loop of :func:`filter_polygons_by_iou_and_area` over sparse rows → removed bool [n].
+    ``conf``: float16 [n] without NaN; ``self_connected``: the mask's diagonal (None = set everywhere). Host code."""
+    n = len(conf)
+    rs = np.ascontiguousarray(row_start, dtype=np.int64)
+    cl = np.ascontiguousarray(cols, dtype=np.int32)
+    cf = np.ascontiguousarray(conf, dtype=np.float16)
+    sc = None if self_connected is None else np.ascontiguousarray(self_connected, dtype=np.uint8)
+    if rs.shape != (n + 1,) or (sc is not None and sc.shape != (n,)) or (n and cl.shape != (int(rs[-1]),)):
+        raise ValueError("greedy_removal: row_start needs n + 1 entries, cols row_start[n], self_connected n")
+    removed = np.zeros(n, np.uint8)
+    _lib.check(_lib.load().td_crown_pairs_greedy(rs.ctypes.data, cl.ctypes.data, cf.ctypes.data, None if sc is None else sc.ctypes.data, n,
+                                                 removed.ctypes.data), "td_crown_pairs_greedy")
+    return removed.astype(bool)
+
+
+def filter_polygons_by_iou_and_area_device(bounds, areas, confidences, iou_threshold, area_threshold, device=0) -> Optional[List[int]]:
+    """:func:`filter_polygons_by_iou_and_area` with the N x N mask replaced by td_crown_pairs_count / td_crown_pairs_fill (sparse
+    rows of connected pairs, the same float32 / float16 arithmetic) and the group loop by td_crown_pairs_greedy → the same kept
+    indices. None (one printed line) = use the host function: an input outside what the kernels were argued for — a non-finite
+    coordinate, a box without a finite positive float32 area, a NaN confidence, ``iou_threshold`` < 0, a threshold numpy would
+    compare in a wider type — or more than MAX_DEVICE_PAIRS connected pairs."""
+    who = "filter_polygons_by_iou_and_area_device"
+    n = len(areas)
+    if n == 0:
+        return []
+    bb = np.array([[np.float32(v) for v in b] for b in bounds], dtype=np.float32).reshape(-1, 4)
+    conf = np.array(confidences, dtype=np.float16)
+    ar = np.array(areas, dtype=np.float16)
+    iou_thr, area_thr = _weak_threshold(iou_threshold, np.float32), _weak_threshold(area_threshold, np.float16)
+    why = _boxes_declined(bb)
+    if why is None and np.isnan(conf).any():
+        why = "a confidence is NaN"
+    if why is None and (iou_thr is None or area_thr is None):
+        why = "a threshold is not compared in float32 / float16"
+    if why is None and iou_thr < 0:
+        why = f"iou_threshold {iou_threshold} is negative"
+    if why is not None:
+        return _decline(who, why)
+    pairs = connected_pairs_device(bb, ar, iou_thr, area_thr, device)
+    if pairs is None:
+        return _decline(who, f"more than {MAX_DEVICE_PAIRS} connected pairs")
+    # the mask's diagonal, which the sparse rows leave out: it decides how a row's own confidence ties (td_crown_pairs_greedy)
+    box_area = (bb[:, 2] - bb[:, 0]) * (bb[:, 3] - bb[:, 1])
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        diagonal = (box_area / (box_area + box_area - box_area) > iou_thr) & (np.abs(ar - ar) / np.maximum(ar, ar) < area_thr)
+    removed = greedy_removal(pairs[0], pairs[1], conf, diagonal)
+    return [int(i) for i in np.flatnonzero(~removed)]
+
+
+def containment_device(bounds, threshold, device=0):
+    """:func:`containment` with the pair tests in td_crown_pairs_count → the same triple, or None (one printed line) = use the host
+    function: a non-finite coordinate, a box without a finite positive float32 area, ``threshold`` <= 0 or compared in a wider type
+    than float32. The ratio returned is 1.0 for every box: the diagonal of the ratio matrix is exactly 1 for a finite positive area
+    and no entry exceeds it (float subtraction and multiplication are monotone, so iw * ih <= the inner box's area)."""
+    who = "containment_device"
+    b = np.array(bounds, dtype=np.float32).reshape(-1, 4)
+    n = b.shape[0]
+    if n == 0:
+        return [], [], []
+    thr = _weak_threshold(threshold, np.float32)
+    why = _boxes_declined(b)
+    if why is None and thr is None:
+        why = "the threshold is not compared in float32"
+    if why is None and thr <= 0:
+        why = f"containment_threshold {threshold} is not positive"
+    if why is not None:
+        return _decline(who, why)
+    lib = _lib.load()
+    dev = torch.device("cuda", device)
+    with torch.cuda.device(dev):
+        d_b = torch.from_numpy(np.ascontiguousarray(b)).to(dev)
+        out = torch.empty((2, n), dtype=torch.int32, device=dev)
+        _lib.check(lib.td_crown_pairs_count(d_b.data_ptr(), None, n, 0.0, 0, None, float(thr), out[0].data_ptr(), out[1].data_ptr(),
+                                            _lib.stream_ptr()), "td_crown_pairs_count")
+        num, is_c = out.cpu().numpy()
+    return [1.0] * n, [bool(v) for v in is_c], [int(v) for v in num]
+
+
+def _device_filters_on(config) -> bool:
+    """``device_filters`` explicitly true: both box-pair filters take the device path. "auto", the default, and false keep the host
+    functions (nothing has decided otherwise: DESIGN.md §7). Anything else is refused."""
+    value = config.get("device_filters", "auto")
+    value = "auto" if value is None else value
+    if not any(value is v for v in (True, False)) and value not in ("auto", "true", "false"):
+        raise ValueError(f"device_filters must be true, false or 'auto', got {value!r}")
+    return value is True or value == "true"
+
+
 def _near_border(pb, rb, eps) -> bool:
     """helpers.element_is_near_border; rb = (left, bottom, right, top)."""
     return pb[0] < rb[0] + eps or pb[2] > rb[2] - eps or pb[1] < rb[1] + eps or pb[3] > rb[3] - eps
@@ -358,6 +506,7 @@ def process_layer(rings: List[np.ndarray], scores: Sequence[Optional[float]], co
                   device: int = 0) -> List[dict]:
     """process_geojson + process_features (postprocessing.py:722-808, 478-720) for the crowns of one image → the list
     of output features ``{"ring": [m,2], "properties": {...}}`` in the reference's order (duplicates included)."""
+    device_filters = _device_filters_on(config)
     conf_thr, iou_thr, area_thr = _cfg(config, "confidence_threshold"), _cfg(config, "iou_threshold"), _cfg(config, "area_threshold")
     h_scale, n_scale = float(_cfg(config, "height_scaling_factor")), float(_cfg(config, "ndvi_scaling_factor"))
     # 1-2: confidence filter, ids, areas of the simplify(2) polygons
@@ -397,8 +546,10 @@ def process_layer(rings: List[np.ndarray], scores: Sequence[Optional[float]], co
     def bounds_of(f):
         r = f["ring"]
         return (r[:, 0].min(), r[:, 1].min(), r[:, 0].max(), r[:, 1].max())
-    kept = filter_polygons_by_iou_and_area([bounds_of(f) for f in feats], [id_to_area[f["poly_id"]] for f in feats],
-                                           [f["score"] for f in feats], iou_thr, area_thr)
+    dedup_args = ([bounds_of(f) for f in feats], [id_to_area[f["poly_id"]] for f in feats], [f["score"] for f in feats], iou_thr, area_thr)
+    kept = filter_polygons_by_iou_and_area_device(*dedup_args, device=device) if device_filters else None
+    if kept is None:                                      # the host function: device_filters off, or the device path declined
+        kept = filter_polygons_by_iou_and_area(*dedup_args)
     features = [feats[i] for i in kept]
     if not features:
         return []
@@ -439,7 +590,9 @@ def process_layer(rings: List[np.ndarray], scores: Sequence[Optional[float]], co
             continue
         preselected.append(f)
     # containment over ALL features of step 3
-    ratios, is_cont, num_cont = containment([bounds_of(f) for f in features], _cfg(config, "containment_threshold"))
+    contain_args = ([bounds_of(f) for f in features], _cfg(config, "containment_threshold"))
+    contained = containment_device(*contain_args, device=device) if device_filters else None
+    ratios, is_cont, num_cont = contained if contained is not None else containment(*contain_args)
     info = {f["poly_id"]: {"is_contained": is_cont[j], "num_contained": num_cont[j], "containment_ratio": ratios[j]}
             for j, f in enumerate(features)}
     index_of = {f["poly_id"]: j for j, f in enumerate(features)}
