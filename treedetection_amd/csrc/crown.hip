@@ -14,6 +14,18 @@
 //                   result = min, max, mean, population variance (mean / variance accumulated in float64 and rounded
 //                   once — cupy's own float32 reduction order is not reproducible).
 // A crown whose circle holds no pixel gets -1 in every field. HBM-bound gather; no matrix work.
+//
+// The box. Height mode tests float64 positions, so the circle's box plus a pixel holds every pixel that passes. NDVI mode tests
+// positions ROUNDED to float32, and the rounding moves a pixel by up to half a float32 step of its coordinate: at a northing of
+// 5.3e6 a step is 0.5 m, so whole rows up to 0.25 m outside the circle pass the reference's test. The NDVI box is therefore wider by
+// that displacement — at most |coordinate| * 2^-24, taken at the largest |x| and |y| the subset reaches — converted to pixels (at
+// 0.2 m pixels and a northing of 5.3e6: 0.32 m, at most two rows more per side; nothing at small coordinates). It stays a box of
+// the circle's size; only a rotated transform scans the whole subset.
+//
+// NaN. max, argmax and min are numpy's (oracle/postprocess_ref.py is the definition; parity with cupy itself is unpinned here as in
+// the rest of this stage): a NaN inside the circle makes max and min NaN, and the position reported is that of the FIRST NaN in
+// row-major order; among numbers the first occurrence of the maximum wins (+0.0 and -0.0 are equal). Mean and variance propagate
+// NaN through their sums. The NaN's payload is not defined.
 #include "common.h"
 
 namespace {
@@ -47,6 +59,18 @@ __device__ __forceinline__ bool inside_f32(const CrownArgs& A, int row_sub, int 
     return __fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)) <= r2;
 }
 
+// numpy's argmax order: does (v, lin) displace the running (vmax, imax)? A NaN beats every number; among NaNs, and among equal
+// numbers, the lower row-major position wins. Used by the per-thread loop and by the LDS reduction alike.
+__device__ __forceinline__ bool max_takes(float v, long long lin, float vmax, long long imax) {
+    if (imax < 0) return true;
+    const bool v_nan = v != v, m_nan = vmax != vmax;
+    if (v_nan || m_nan) return v_nan && (!m_nan || lin < imax);
+    return v > vmax || (v == vmax && lin < imax);
+}
+
+// numpy's min: a NaN, once met, stays
+__device__ __forceinline__ float min_nan(float m, float v) { return (v < m || v != v) ? v : m; }
+
 __global__ __launch_bounds__(256) void crown_stats_kernel(const CrownArgs A) {
     const int k = blockIdx.x;
     const int tid = threadIdx.x;
@@ -56,9 +80,15 @@ __global__ __launch_bounds__(256) void crown_stats_kernel(const CrownArgs A) {
     // bounding box of the circle in subset indices (whole subset when the transform is rotated)
     int c0 = 0, c1 = A.sub_cols - 1, r0 = 0, r1 = A.sub_rows - 1;
     if (A.b == 0.0 && A.d == 0.0 && A.a != 0.0 && A.e != 0.0) {
-        const double m = (double)r * 1.0001 + 1e-3;
-        double u0 = ((double)cx - m - A.c) / A.a, u1 = ((double)cx + m - A.c) / A.a;     // col' range
-        double v0 = ((double)cy - m - A.f) / A.e, v1 = ((double)cy + m - A.f) / A.e;     // row' range
+        double mx = (double)r * 1.0001 + 1e-3, my = mx;
+        if (A.mode == 1) {       // float32 rounding of the pixel positions: half a step at the largest |x|, |y| of the subset
+            const double xa = fabs(A.a * (double)A.r_lo + A.c), xb = fabs(A.a * (double)(A.r_lo + A.sub_cols - 1) + A.c);
+            const double ya = fabs(A.e * (double)A.c_lo + A.f), yb = fabs(A.e * (double)(A.c_lo + A.sub_rows - 1) + A.f);
+            mx += (xa > xb ? xa : xb) * 0x1p-24;
+            my += (ya > yb ? ya : yb) * 0x1p-24;
+        }
+        double u0 = ((double)cx - mx - A.c) / A.a, u1 = ((double)cx + mx - A.c) / A.a;   // col' range
+        double v0 = ((double)cy - my - A.f) / A.e, v1 = ((double)cy + my - A.f) / A.e;   // row' range
         if (u0 > u1) { const double t = u0; u0 = u1; u1 = t; }
         if (v0 > v1) { const double t = v0; v0 = v1; v1 = t; }
         const double lo_c = floor(u0) - 1.0 - A.r_lo, hi_c = ceil(u1) + 1.0 - A.r_lo;
@@ -85,11 +115,11 @@ __global__ __launch_bounds__(256) void crown_stats_kernel(const CrownArgs A) {
         if (!in) continue;
         const float v = A.raster[(size_t)(rs + A.r_lo) * A.cols + (cs + A.c_lo)];
         const long long lin = (long long)rs * A.sub_cols + cs;       // position in the flattened subset
-        if (imax < 0 || v > vmax || (v == vmax && lin < imax)) {
+        if (max_takes(v, lin, vmax, imax)) {
             vmax = v;
             imax = lin;
         }
-        vmin = v < vmin ? v : vmin;
+        vmin = min_nan(vmin, v);
         sum += (double)v;
         ++cnt;
     }
@@ -100,12 +130,12 @@ __global__ __launch_bounds__(256) void crown_stats_kernel(const CrownArgs A) {
             const long long oi = s_idx[tid + s];
             if (oi >= 0) {
                 const float ov = s_max[tid + s];
-                if (s_idx[tid] < 0 || ov > s_max[tid] || (ov == s_max[tid] && oi < s_idx[tid])) {
+                if (max_takes(ov, oi, s_max[tid], s_idx[tid])) {
                     s_max[tid] = ov;
                     s_idx[tid] = oi;
                 }
             }
-            s_min[tid] = s_min[tid + s] < s_min[tid] ? s_min[tid + s] : s_min[tid];
+            s_min[tid] = min_nan(s_min[tid], s_min[tid + s]);
             s_sum[tid] += s_sum[tid + s];
             s_cnt[tid] += s_cnt[tid + s];
         }
