@@ -382,19 +382,21 @@ td_status td_tiff_blocks_to_image_u16_dev(const uint8_t* blocks, int64_t block_c
  * Asynchronous on `stream`. */
 td_status td_tiff_blocks_to_image_f32_dev(const uint8_t* blocks, int64_t block_cap, int block_w, int block_h, int blocks_across,
                                           int blocks_down, int spp, int predictor, float* image, int width, int height, void* stream);
-/* ---- JPEG-in-TIFF (compression 7; jpeg_core.h, jpegcodec.cpp, jpegdecode.hip): sequential Huffman, 8-bit, grey or three components
- * (Y 1x1 / 2x1 / 2x2, chroma 1x1), restart intervals; the output equals the host reader's (Pillow's libjpeg: accurate integer IDCT, fancy
+/* ---- JPEG-in-TIFF (compression 7; jpeg_core.h, jpegcodec.cpp, jpegdecode.hip): sequential Huffman, 8-bit, grey, three components
+ * (Y 1x1 / 2x1 / 2x2, chroma 1x1) or four (all 1x1, stored as they decode: RGB + an extra sample, separated), restart intervals; the
+ * output equals the host reader's (Pillow's libjpeg: accurate integer IDCT, fancy
  * upsampling, its YCbCr → RGB) byte for byte. Everything else is unsupported and stays with the host reader. */
 /* Host plan of a raster, once per image: the JPEGTables tag (tables, tables_len; 0 = none) is parsed once, then every block's headers
  * (data + block_off[b], block_nbytes[b] bytes; host memory) as the host reader's stream sees them (an Adobe segment saying
- * photometric == 6 first when bands == 3 and the block has no JFIF). block_rows[b]: the rows the block must hold; its SOF width must be
+ * photometric == 6 first when bands == 3 and the block has no JFIF; nothing is added for bands == 4, whose blocks must hold four
+ * components sampled 1x1 and no Adobe segment naming a transform — YCCK is unsupported). bands: 1, 3 or 4. block_rows[b]: the rows the block must hold; its SOF width must be
  * block_w. Per block, block_info int64 [nblocks][8] = {0 decodable / 1 unsupported, table set, sampling mode (0 grey, 1 4:4:4, 2 4:2:2,
- * 3 4:2:0), 1 = YCbCr → RGB, SOF width, SOF height, first coefficient (int16 elements), restart interval}. segs int64 [seg_cap][4]: one
+ * 3 4:2:0, 4 four components as stored), 1 = YCbCr → RGB (never in mode 4), SOF width, SOF height, first coefficient (int16 elements), restart interval}. segs int64 [seg_cap][4]: one
  * entropy-coded segment per block, or one per restart interval = {offset in data, bytes, block, first MCU | MCU count << 32}.
  * tabsets: [tabset_cap] deduplicated table sets of TD_JPEG_TABSET_BYTES each (quantisation tables in natural order, Huffman lookup
  * tables). totals int64 [4] = {segments, table sets, coefficients, unsupported blocks}. Returns TD_OK, TD_ERR_CAPACITY (totals say how
  * much is needed) or TD_ERR_INVALID. Host code, thread-safe. */
-#define TD_JPEG_TABSET_BYTES 8928
+#define TD_JPEG_TABSET_BYTES 11904
 td_status td_tiff_jpeg_plan(const uint8_t* tables, int64_t tables_len, const uint8_t* data, const int64_t* block_off,
                             const int64_t* block_nbytes, int nblocks, int photometric, int bands, int block_w, const int32_t* block_rows,
                             int64_t* block_info, int64_t* segs, int64_t seg_cap, void* tabsets, int64_t tabset_cap, int64_t* totals);
@@ -402,7 +404,8 @@ td_status td_tiff_jpeg_plan(const uint8_t* tables, int64_t tables_len, const uin
  * plan's arrays (nseg segments); coef: DEVICE int16 [totals[2]] scratch (zeroed here), planes: DEVICE uint8 [totals[2]] scratch;
  * image: DEVICE [height][width][bands] uint8, blocks block_w x block_h (strips: block_w = width) in a grid blocks_across wide, each
  * cropped to the raster. status: DEVICE int32 [nblocks], 0 = ok, 1 = corrupt entropy-coded data. One lane decodes one segment, the
- * waves take 64 segments at a time from a per-launch counter; then the IDCT and the upsampling / colour kernels. Asynchronous on
+ * waves take 64 segments at a time from a per-launch counter; then the IDCT and the upsampling / colour kernels. bands == 4 (every block
+ * of mode 4, as the plan for four bands gives them): image must be 4-byte aligned, each pixel is written as one dword. Asynchronous on
  * `stream`, whose device must be the calling thread's current one. */
 td_status td_tiff_jpeg_decode_dev(const uint8_t* comp, const int64_t* block_info, int nblocks, const int64_t* segs, int nseg,
                                   const void* tabsets, int16_t* coef, uint8_t* planes, int64_t coef_count, int32_t* status, uint8_t* image,

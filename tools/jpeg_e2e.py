@@ -1,7 +1,8 @@
 """Files-to-files Predictor rate on a JPEG-in-TIFF raster, device decoder on ("auto" / true) against the host reader (false):
 python tools/jpeg_e2e.py [side=9000] [tile=256] [quality=90] [subsampling=2] [layout=complete|gdal] [restart=0] [precision=fp16]
-[batch=16] [images=3] [modes=true,false]
-The raster (side x side x 3 uint8, synthetic orthophoto tiles) is cut into the reference's 450 x 450 px tiles; every mode predicts
+[batch=16] [images=3] [modes=true,false] [bands=3|4]
+The raster (side x side x bands uint8, synthetic orthophoto tiles; bands=4 adds the green band again as a near-infrared band: RGBI,
+of which the tile loop reads bands 0 - 2) is cut into the reference's 450 x 450 px tiles; every mode predicts
 one warm-up image, then `images` images back to back as detection.predict_on_model walks them (the next one prefetched while the
 current one predicts). Prints one JSON line: tiles/s per mode, the decode stats, and whether the Prediction_*.json files are identical."""
 import json
@@ -22,7 +23,7 @@ from treedetection_amd.synth import make_tile                      # noqa: E402
 from treedetection_amd.weights import make_synthetic_state_dict   # noqa: E402
 
 args = dict(a.split("=", 1) for a in sys.argv[1:] if "=" in a)
-side, tile, nimg = int(args.get("side", 9000)), int(args.get("tile", 256)), int(args.get("images", 3))
+side, tile, nimg, bands = int(args.get("side", 9000)), int(args.get("tile", 256)), int(args.get("images", 3)), int(args.get("bands", 3))
 modes = [m if m in ("auto", "all") else m == "true" for m in args.get("modes", "true,false").split(",")]
 base = "/dev/shm" if os.path.isdir("/dev/shm") and os.access("/dev/shm", os.W_OK) else None
 root = tempfile.mkdtemp(prefix="td_jpeg_e2e_", dir=base)
@@ -31,10 +32,11 @@ try:
     S = 1000
     n = -(-side // S)
     tiles = [make_tile(i, S)[0] for i in range(min(16, n * n))]
-    img = np.zeros((3, n * S, n * S), np.uint8)
+    img = np.zeros((bands, n * S, n * S), np.uint8)
     for r in range(n):
         for c in range(n):
-            img[:, r * S:(r + 1) * S, c * S:(c + 1) * S] = tiles[(r * n + c) % len(tiles)].transpose(2, 0, 1)
+            t = tiles[(r * n + c) % len(tiles)].transpose(2, 0, 1)
+            img[:, r * S:(r + 1) * S, c * S:(c + 1) * S] = t if bands == 3 else np.concatenate([t, t[1:2]])
     img = np.ascontiguousarray(img[:, :side, :side])
     tif = f"{root}/rgb/324125000.tif"
     write_geotiff(tif, img, (0.2, 0.0, 412000.0, 0.0, -0.2, 5318000.0 + side * 0.2), 25832, compression="jpeg", tile=(tile, tile),
@@ -50,7 +52,7 @@ try:
         os.link(tjson, f"{root}/tiles/{nm}.json")
     sd = make_synthetic_state_dict(int(args.get("depth", 50)), seed=0)
     cfg = T.setup_model_cfg(update_model="synthetic", device="0")
-    res = {"raster": f"{side}x{side}x3 uint8 JPEG, {tile}x{tile} tiles", "tiles_per_image": ntiles, "file_bytes": os.path.getsize(tif),
+    res = {"raster": f"{side}x{side}x{bands} uint8 JPEG, {tile}x{tile} tiles", "tiles_per_image": ntiles, "file_bytes": os.path.getsize(tif),
            "precision": args.get("precision", "fp16")}
     outs = {}
     for dd in modes:

@@ -19,7 +19,7 @@ ERR_INVALID = -1    # TD_ERR_INVALID
 ERR_CAPACITY = -4   # TD_ERR_CAPACITY
 ERR_STATE = -5      # TD_ERR_STATE
 ERR_UNSUPPORTED = -6  # TD_ERR_UNSUPPORTED
-JPEG_TABSET_BYTES = 8928  # TD_JPEG_TABSET_BYTES: one table set of td_tiff_jpeg_plan
+JPEG_TABSET_BYTES = 11904  # TD_JPEG_TABSET_BYTES: one table set of td_tiff_jpeg_plan
 SAMPLE_U8, SAMPLE_F32 = 0, 1                          # TD_SAMPLE_*: source of td_resample_gdal_dev
 RESAMPLE_MODES = {"f32": 0, "u8": 1, "ndvi": 2}       # TD_RESAMPLE_*: its output modes
 

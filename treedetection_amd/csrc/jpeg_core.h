@@ -7,8 +7,9 @@
 //   - "fancy" upsampling of chroma (triangular filter, 3/4 - 1/4 weights, edge samples replicated at the component's real size
 //     ceil(W * h / hmax) x ceil(H * v / vmax); components at most 2 samples wide are replicated instead, as libjpeg does);
 //   - YCbCr → RGB in 16-bit fixed point.
-// What this core decodes: baseline / extended sequential Huffman, 8-bit samples, one component or three with Y sampled 1x1, 2x1 or
-// 2x2 and chroma 1x1, one interleaved scan, restart intervals. The host plan (jpegcodec.cpp) parses the headers, builds the Huffman
+// What this core decodes: baseline / extended sequential Huffman, 8-bit samples, one component, three with Y sampled 1x1, 2x1 or
+// 2x2 and chroma 1x1, or four that are all sampled 1x1 and come out as stored (libjpeg's JCS_CMYK / JCS_UNKNOWN: what libtiff writes for
+// a four-band RGB + extra sample or separated raster), one interleaved scan, restart intervals. The host plan (jpegcodec.cpp) parses the headers, builds the Huffman
 // lookup tables and cuts a block's entropy-coded data into segments (one per restart interval); everything else is unsupported.
 #pragma once
 #include <cstdint>
@@ -31,30 +32,32 @@ struct JpegHuff {
     uint8_t vals[256];                   // symbols in code order (HUFFVAL)
 };
 
-// The tables a block's components use, resolved per component (Y, Cb, Cr). Blocks that use the same tables share one set.
+// The tables a block's components use, resolved per component (Y, Cb, Cr; or the four bands). Blocks that use the same tables share
+// one set.
+constexpr int JPG_MAXC = 4;
 struct JpegTables {
-    uint16_t q[3][64];                   // quantisation tables in natural (row-major) order
-    JpegHuff dc[3], ac[3];
+    uint16_t q[JPG_MAXC][64];            // quantisation tables in natural (row-major) order
+    JpegHuff dc[JPG_MAXC], ac[JPG_MAXC];
 };
 
-// Sampling modes: 0 grey, 1 4:4:4, 2 4:2:2 (Y 2x1), 3 4:2:0 (Y 2x2); chroma is always 1x1.
+// Sampling modes: 0 grey, 1 4:4:4, 2 4:2:2 (Y 2x1), 3 4:2:0 (Y 2x2), chroma always 1x1; 4 four components, all 1x1, no colour step.
 struct JpegGeom {
     int ncomp, hmax, vmax, mcus_x, mcus_y;
-    int bw[3], bh[3];                    // 8x8 blocks across / down per component (the MCU grid's, padding included)
-    int cw[3], ch[3];                    // real size of each component in samples
-    int64_t off[3];                      // where the component's coefficients / samples start, in elements from the block's base
+    int bw[JPG_MAXC], bh[JPG_MAXC];      // 8x8 blocks across / down per component (the MCU grid's, padding included)
+    int cw[JPG_MAXC], ch[JPG_MAXC];      // real size of each component in samples
+    int64_t off[JPG_MAXC];               // where the component's coefficients / samples start, in elements from the block's base
     int64_t total;                       // elements of one block (coefficients, or samples of the component planes)
 };
 
 TD_JPG_HD JpegGeom jpeg_geom(int mode, int w, int h) {
     JpegGeom g;
-    g.ncomp = mode == 0 ? 1 : 3;
-    g.hmax = mode >= 2 ? 2 : 1;
+    g.ncomp = mode == 0 ? 1 : (mode == 4 ? 4 : 3);
+    g.hmax = mode == 2 || mode == 3 ? 2 : 1;
     g.vmax = mode == 3 ? 2 : 1;
     g.mcus_x = (w + 8 * g.hmax - 1) / (8 * g.hmax);
     g.mcus_y = (h + 8 * g.vmax - 1) / (8 * g.vmax);
     int64_t o = 0;
-    for (int c = 0; c < 3; ++c) {
+    for (int c = 0; c < JPG_MAXC; ++c) {
         const bool y = c == 0;
         g.bw[c] = c < g.ncomp ? g.mcus_x * (y ? g.hmax : 1) : 0;
         g.bh[c] = c < g.ncomp ? g.mcus_y * (y ? g.vmax : 1) : 0;
@@ -178,7 +181,10 @@ TD_JPG_HD TD_JPG_INLINE int jpeg_block(const JpegHuff& dc, const JpegHuff& ac, c
 }
 
 // MCUs [mcu0, mcu0 + nmcu) of one block from its segment [src, src + nbytes) (one restart interval, or the whole scan) into the
-// block's zeroed coefficient area coef (layout: JpegGeom::off / bw). → 0 ok, 1 corrupt.
+// block's zeroed coefficient area coef (layout: JpegGeom::off / bw). → 0 ok, 1 corrupt. FOUR: the block is of mode 4 (four DC
+// predictors, an MCU of four blocks) — a parameter of the instantiation, so that the one- and three-component decoder carries nothing
+// of it (the entropy kernel is bound by its registers).
+template <bool FOUR = false>
 TD_JPG_HD TD_JPG_INLINE int jpeg_decode_segment(const JpegTables& T, const JpegGeom& g, const uint8_t* src, uint32_t nbytes, uint32_t mcu0,
                                                 uint32_t nmcu, int16_t* coef) {
     JpegBits b;
@@ -188,10 +194,14 @@ TD_JPG_HD TD_JPG_INLINE int jpeg_decode_segment(const JpegTables& T, const JpegG
     b.acc = 0;
     b.have = 0;
     b.pad = 0;
-    int32_t pred[3] = {0, 0, 0};
+    int32_t pred[FOUR ? 4 : 3] = {};
     for (uint32_t m = mcu0; m < mcu0 + nmcu; ++m) {
         const int mx = (int)(m % (uint32_t)g.mcus_x), my = (int)(m / (uint32_t)g.mcus_x);
-        if (g.ncomp == 1) {
+        if constexpr (FOUR) {
+            const int64_t at = ((int64_t)my * g.mcus_x + mx) * 64, plane = (int64_t)g.mcus_x * g.mcus_y * 64;
+            for (int c = 0; c < 4; ++c)
+                if (jpeg_block(T.dc[c], T.ac[c], T.q[c], b, pred[c], coef + c * plane + at)) return 1;
+        } else if (g.ncomp == 1) {
             if (jpeg_block(T.dc[0], T.ac[0], T.q[0], b, pred[0], coef + ((int64_t)my * g.bw[0] + mx) * 64)) return 1;
         } else {
             for (int v = 0; v < g.vmax; ++v)
@@ -348,9 +358,16 @@ TD_JPG_HD int jpeg_chroma(const uint8_t* planes, const JpegGeom& g, int c, int x
     return (t * 3 + o + 7) >> 4;
 }
 
+// Mode 4: the pixel's four samples as stored, packed in memory order (sample 0 in the low byte) — one dword of an [h][w][4] raster.
+TD_JPG_HD uint32_t jpeg_pixel4(const uint8_t* planes, int mcus_x, int mcus_y, int x, int y) {
+    const int64_t plane = (int64_t)mcus_x * mcus_y * 64, at = (int64_t)y * (mcus_x * 8) + x;
+    return (uint32_t)planes[at] | (uint32_t)planes[plane + at] << 8 | (uint32_t)planes[2 * plane + at] << 16 |
+           (uint32_t)planes[3 * plane + at] << 24;
+}
+
 TD_JPG_HD uint8_t jpeg_clamp255(int v) { return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
 
-// → the pixel's samples in px[0 .. ncomp)
+// → the pixel's samples in px[0 .. ncomp), one or three components (four: jpeg_pixel4)
 TD_JPG_HD TD_JPG_INLINE void jpeg_pixel(const uint8_t* planes, const JpegGeom& g, int ycc, int x, int y, uint8_t* px) {
     const int Y = jpeg_plane_at(planes, g, 0, x, y);
     if (g.ncomp == 1) {

@@ -6,7 +6,8 @@
 // SOI, an Adobe APP14 segment (three bands and no JFIF in the block's first 32 bytes: transform 1 for PhotometricInterpretation 6,
 // 0 otherwise), the JPEGTables tag without its SOI / EOI, the block without its SOI. The plan walks those pieces in that order, so a
 // table the block redefines wins and the colour transform follows libjpeg's rule (JFIF → YCbCr, else the Adobe transform, else the
-// component ids).
+// component ids). Four bands get no Adobe segment: libjpeg takes four components as they are stored (CMYK) unless an Adobe segment of
+// the stream itself names a transform (YCCK), and such a block is unsupported.
 #include "common.h"
 #include "jpeg_core.h"
 
@@ -138,7 +139,7 @@ void walk_markers(JpegHeader& h, const uint8_t* p, int64_t n, int64_t pos, bool 
                 h.why = "not 8-bit";
                 return;
             }
-            if ((h.ncomp != 1 && h.ncomp != 3) || sl < 6 + 3 * h.ncomp) {
+            if ((h.ncomp != 1 && h.ncomp != 3 && h.ncomp != 4) || sl < 6 + 3 * h.ncomp) {
                 h.why = "component count";
                 return;
             }
@@ -232,7 +233,8 @@ bool build_huff(const HuffSpec& s, bool dc, JpegHuff& H) {
     return true;
 }
 
-// A parsed block → mode (0 grey, 1 4:4:4, 2 4:2:2, 3 4:2:0), colour transform, resolved tables. → false + why: unsupported.
+// A parsed block → mode (0 grey, 1 4:4:4, 2 4:2:2, 3 4:2:0, 4 four components as stored), colour transform, resolved tables.
+// → false + why: unsupported.
 bool resolve(JpegHeader& h, int& mode, int& ycc, JpegTables& T) {
     if (!h.sos) {
         if (!h.why) h.why = "no scan";
@@ -240,6 +242,17 @@ bool resolve(JpegHeader& h, int& mode, int& ycc, JpegTables& T) {
     }
     if (h.ncomp == 1) {
         mode = 0;
+    } else if (h.ncomp == 4) {                               // libjpeg: CMYK as stored, unless an Adobe segment says YCCK (any transform but 0)
+        for (int c = 0; c < 4; ++c)
+            if (h.hs[c] != 1 || h.vs[c] != 1) {
+                h.why = "sampling of a four-component frame";
+                return false;
+            }
+        if (h.adobe && h.adobe_transform != 0) {
+            h.why = "YCCK";
+            return false;
+        }
+        mode = 4;
     } else {
         for (int c = 1; c < 3; ++c)
             if (h.hs[c] != 1 || h.vs[c] != 1) {
@@ -322,7 +335,7 @@ extern "C" td_status td_tiff_jpeg_plan(const uint8_t* tables, int64_t tables_len
                                        const int32_t* block_rows, int64_t* block_info, int64_t* segs, int64_t seg_cap, void* tabsets,
                                        int64_t tabset_cap, int64_t* totals) {
     if ((tables_len > 0 && !tables) || tables_len < 0 || !data || !block_off || !block_nbytes || nblocks < 0 || !block_rows || !block_info ||
-        !totals || seg_cap < 0 || tabset_cap < 0 || (seg_cap > 0 && !segs) || (tabset_cap > 0 && !tabsets) || (bands != 1 && bands != 3) ||
+        !totals || seg_cap < 0 || tabset_cap < 0 || (seg_cap > 0 && !segs) || (tabset_cap > 0 && !tabsets) || (bands != 1 && bands != 3 && bands != 4) ||
         block_w < 1) {
         td_set_error("td_tiff_jpeg_plan: bad argument");
         return TD_ERR_INVALID;
@@ -438,7 +451,8 @@ extern "C" int64_t td_jpeg_decode(const uint8_t* src, int64_t n, uint8_t* dst, i
     }
     std::vector<int16_t> coef((size_t)g.total, 0);
     for (size_t i = 0; i < cut.size(); ++i)
-        if (jpeg_decode_segment(T, g, src + cut[i].off, (uint32_t)cut[i].len, cut[i].mcu0, cut[i].nmcu, coef.data())) {
+        if (mode == 4 ? jpeg_decode_segment<true>(T, g, src + cut[i].off, (uint32_t)cut[i].len, cut[i].mcu0, cut[i].nmcu, coef.data())
+                      : jpeg_decode_segment<false>(T, g, src + cut[i].off, (uint32_t)cut[i].len, cut[i].mcu0, cut[i].nmcu, coef.data())) {
             td_set_error("td_jpeg_decode: corrupt entropy-coded data (segment %d)", (int)i);
             return TD_ERR_INVALID;
         }
@@ -449,6 +463,14 @@ extern "C" int64_t td_jpeg_decode(const uint8_t* src, int64_t n, uint8_t* dst, i
                 jpeg_idct_islow(coef.data() + g.off[c] + ((int64_t)by * g.bw[c] + bx) * 64, T.q[c],
                                 planes.data() + g.off[c] + (int64_t)by * 8 * (g.bw[c] * 8) + bx * 8, g.bw[c] * 8);
     for (int y = 0; y < h.height; ++y)
-        for (int x = 0; x < h.width; ++x) jpeg_pixel(planes.data(), g, ycc, x, y, dst + ((int64_t)y * h.width + x) * h.ncomp);
+        for (int x = 0; x < h.width; ++x) {
+            uint8_t* px = dst + ((int64_t)y * h.width + x) * h.ncomp;
+            if (mode == 4) {
+                const uint32_t v = jpeg_pixel4(planes.data(), g.mcus_x, g.mcus_y, x, y);
+                for (int c = 0; c < 4; ++c) px[c] = (uint8_t)(v >> (8 * c));
+            } else {
+                jpeg_pixel(planes.data(), g, ycc, x, y, px);
+            }
+        }
     return need;
 }

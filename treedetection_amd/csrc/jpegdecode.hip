@@ -6,6 +6,9 @@
 //      beside the forwards leaves whole CUs to them. Coefficients land in a zeroed int16 buffer (only the non-zero ones are written);
 //   2. dequantisation + the accurate integer IDCT, one thread per 8x8 block → the component planes (uint8);
 //   3. fancy upsampling + YCbCr → RGB, one thread per raster pixel → image [height][width][bands], each block cropped to the raster.
+// Four bands (mode 4: four components sampled 1x1, stored as they decode) take an instantiation of their own of the entropy kernel
+// (four DC predictors, four blocks per MCU; the one- and three-component instantiation keeps its registers) and a pixel kernel that
+// gathers the four plane samples of a pixel and writes them as ONE dword: a wave stores 256 contiguous bytes.
 #include "common.h"
 #include "jpeg_core.h"
 
@@ -13,6 +16,7 @@ namespace {
 
 constexpr int JPG_WPB = 4;               // waves per workgroup of the entropy launch (no LDS: the tables are read through the caches)
 
+template <bool FOUR>
 __global__ __launch_bounds__(64 * JPG_WPB) void jpeg_entropy_kernel(const uint8_t* __restrict__ comp, const int64_t* __restrict__ info,
                                                                    const int64_t* __restrict__ segs, int nseg,
                                                                    const JpegTables* __restrict__ sets, int16_t* __restrict__ coef,
@@ -30,7 +34,7 @@ __global__ __launch_bounds__(64 * JPG_WPB) void jpeg_entropy_kernel(const uint8_
             const int64_t* bi = info + b * 8;
             const JpegGeom g = jpeg_geom((int)bi[2], (int)bi[4], (int)bi[5]);
             const uint64_t mm = (uint64_t)sg[3];
-            if (jpeg_decode_segment(sets[bi[1]], g, comp + sg[0], (uint32_t)sg[1], (uint32_t)mm, (uint32_t)(mm >> 32), coef + bi[6]))
+            if (jpeg_decode_segment<FOUR>(sets[bi[1]], g, comp + sg[0], (uint32_t)sg[1], (uint32_t)mm, (uint32_t)(mm >> 32), coef + bi[6]))
                 status[b] = 1;
         }
     }
@@ -89,6 +93,24 @@ __global__ __launch_bounds__(256) void jpeg_pixels_kernel(const uint8_t* __restr
     for (int c = 0; c < BANDS; ++c) image[p * BANDS + c] = px[c];
 }
 
+// Mode 4, one thread per raster pixel: the four planes of a block are read along x (a wave reads 64 consecutive bytes of each inside
+// a block), the pixel leaves as one 32-bit store — consecutive lanes, consecutive dwords. Pixels a block does not cover (the plan has
+// checked that there are none) are written as zero.
+__global__ __launch_bounds__(256) void jpeg_pixels4_kernel(const uint8_t* __restrict__ planes, const int64_t* __restrict__ info, int width,
+                                                           int height, int block_w, int block_h, int blocks_across,
+                                                           uint32_t* __restrict__ image) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= (int64_t)width * height) return;
+    const int Y = (int)(p / width), X = (int)(p - (int64_t)Y * width);
+    const int by = Y / block_h, bx = X / block_w;
+    const int64_t* bi = info + ((int64_t)by * blocks_across + bx) * 8;
+    const int x = X - bx * block_w, y = Y - by * block_h;
+    const int w = (int)bi[4], h = (int)bi[5];
+    uint32_t v = 0;
+    if (x < w && y < h) v = jpeg_pixel4(planes + bi[6], (w + 7) >> 3, (h + 7) >> 3, x, y);
+    image[p] = v;
+}
+
 }  // namespace
 
 extern "C" td_status td_tiff_jpeg_decode_dev(const uint8_t* comp, const int64_t* block_info, int nblocks, const int64_t* segs, int nseg,
@@ -98,13 +120,14 @@ extern "C" td_status td_tiff_jpeg_decode_dev(const uint8_t* comp, const int64_t*
     TD_REQUIRE(comp && block_info && segs && tabsets && coef && planes && status && image, "td_tiff_jpeg_decode_dev: null pointer");
     TD_REQUIRE(nblocks >= 1 && nseg >= nblocks && coef_count >= 0 && coef_count % 64 == 0, "td_tiff_jpeg_decode_dev: %d blocks, %d segments, "
                "%lld coefficients", nblocks, nseg, (long long)coef_count);
-    TD_REQUIRE((bands == 1 || bands == 3) && width >= 1 && height >= 1 && block_w >= 1 && block_h >= 1 && blocks_across >= 1 &&
+    TD_REQUIRE((bands == 1 || bands == 3 || bands == 4) && width >= 1 && height >= 1 && block_w >= 1 && block_h >= 1 && blocks_across >= 1 &&
                (int64_t)blocks_across * block_w >= width && (int64_t)(blocks_across - 1) * block_w < width &&
                nblocks % blocks_across == 0 &&
                (int64_t)(nblocks / blocks_across) * block_h >= height && (int64_t)(nblocks / blocks_across - 1) * block_h < height,
                "td_tiff_jpeg_decode_dev: %d blocks of %d x %d (%d across) do not tile a %d x %d raster", nblocks, block_w, block_h,
                blocks_across, width, height);
     TD_REQUIRE(reinterpret_cast<uintptr_t>(coef) % 16 == 0, "td_tiff_jpeg_decode_dev: coef must be 16-byte aligned");
+    TD_REQUIRE(bands != 4 || reinterpret_cast<uintptr_t>(image) % 4 == 0, "td_tiff_jpeg_decode_dev: a four-band image must be 4-byte aligned");
     hipStream_t s = static_cast<hipStream_t>(stream);
     TD_HIP_CHECK(hipMemsetAsync(coef, 0, (size_t)coef_count * sizeof(int16_t), s));
     TD_HIP_CHECK(hipMemsetAsync(status, 0, (size_t)nblocks * sizeof(int32_t), s));
@@ -114,8 +137,9 @@ extern "C" td_status td_tiff_jpeg_decode_dev(const uint8_t* comp, const int64_t*
     if (tst < 0) return tst;
     const int waves = (nseg + 63) / 64;
     const int groups = (waves + JPG_WPB - 1) / JPG_WPB < cus ? (waves + JPG_WPB - 1) / JPG_WPB : cus;
-    hipLaunchKernelGGL(jpeg_entropy_kernel, dim3(groups), dim3(64 * JPG_WPB), 0, s, comp, block_info, segs, nseg,
-                       static_cast<const JpegTables*>(tabsets), coef, status, ticket);
+    // (the plan gives a raster of four bands blocks of mode 4 only, and the others none of them)
+    hipLaunchKernelGGL(bands == 4 ? jpeg_entropy_kernel<true> : jpeg_entropy_kernel<false>, dim3(groups), dim3(64 * JPG_WPB), 0, s, comp,
+                       block_info, segs, nseg, static_cast<const JpegTables*>(tabsets), coef, status, ticket);
     TD_KERNEL_CHECK();
     const int64_t nblk8 = coef_count / 64;
     if (nblk8 > 0) {
@@ -125,7 +149,9 @@ extern "C" td_status td_tiff_jpeg_decode_dev(const uint8_t* comp, const int64_t*
     }
     const int64_t npx = (int64_t)width * height;
     const dim3 grid((unsigned)((npx + 255) / 256));
-    if (bands == 1) hipLaunchKernelGGL(jpeg_pixels_kernel<1>, grid, dim3(256), 0, s, planes, block_info, width, height, block_w, block_h,
+    if (bands == 4) hipLaunchKernelGGL(jpeg_pixels4_kernel, grid, dim3(256), 0, s, planes, block_info, width, height, block_w, block_h,
+                                       blocks_across, reinterpret_cast<uint32_t*>(image));
+    else if (bands == 1) hipLaunchKernelGGL(jpeg_pixels_kernel<1>, grid, dim3(256), 0, s, planes, block_info, width, height, block_w, block_h,
                                        blocks_across, image);
     else hipLaunchKernelGGL(jpeg_pixels_kernel<3>, grid, dim3(256), 0, s, planes, block_info, width, height, block_w, block_h,
                             blocks_across, image);

@@ -4,7 +4,8 @@ The reference reads rasters through rasterio/GDAL (``rasterio.open`` + ``rasteri
 TreeDetection/prediction.py:61,164); neither is installed here. The tile loader needs windowed reads of classic or
 BigTIFF rasters — strips or tiles, pixel-interleaved or planar, 8/16/32-bit integer or float samples, uncompressed or
 DEFLATE (zlib) / LZW / PackBits (td_tiff_*_decode in libtreedet_hip.so), horizontal-differencing predictor — plus the
-three geo tags (ModelPixelScale / ModelTiepoint / GeoKeyDirectory). JPEG-in-TIFF (compression 7, 8-bit, one or three bands)
+three geo tags (ModelPixelScale / ModelTiepoint / GeoKeyDirectory). JPEG-in-TIFF (compression 7, 8-bit, one, three or four bands —
+RGB + near-infrared as GDAL writes it: RGB with one extra sample, four components stored as they are)
 is windowed too: a block's abbreviated stream + the JPEGTables tag form one JPEG stream, decoded by Pillow's libjpeg block by
 block (GDAL does the same through libtiff). The floating-point predictor (predictor 3, TIFF Technical Note 3) of float32 rasters
 is undone block by block (td_tiff_unpredict_float). Other codecs (old-style JPEG, predictor 3 on float64, ...): whole image through Pillow.
@@ -182,16 +183,22 @@ class GeoTiff:
         return self._predictor == 3 and self.dtype.kind == "f" and self.dtype.itemsize == 4
 
     def _jpeg_blocks_ok(self) -> bool:
-        """New-style JPEG blocks this reader decodes one by one: 8-bit chunky samples, grey or three bands (RGB or YCbCr)."""
-        return (self.dtype == np.uint8 and self.planar == 1 and self.count in (1, 3) and self._predictor == 1
-                and int(self.tags.get(262, [2 if self.count == 3 else 1])[0]) in (1, 2, 6))
+        """New-style JPEG blocks this reader decodes one by one: 8-bit chunky samples, grey, three bands (RGB or YCbCr) or four (RGB
+        with an extra sample of any kind, or separated: libtiff stores the four components without a colour transform)."""
+        if not (self.dtype == np.uint8 and self.planar == 1 and self._predictor == 1):
+            return False
+        photometric = int(self.tags.get(262, [2 if self.count >= 3 else 1])[0])
+        return photometric in (2, 5) if self.count == 4 else self.count in (1, 3) and photometric in (1, 2, 6)
 
     def _decode_jpeg_block(self, raw: bytes, rows: int) -> np.ndarray:
         """One strip / tile of a compression-7 raster → uint8 [rows, bw, bands]. TIFF Technical Note 2: the block is an abbreviated JPEG
         stream (SOI, frame and scan headers, entropy-coded data, EOI); the quantisation / Huffman tables it leaves out are in the
         JPEGTables tag (SOI, DQT / DHT segments, EOI) — tables minus its EOI + block minus its SOI is a complete stream. The colour
         space is NOT in the stream (no JFIF header): libtiff tells libjpeg from PhotometricInterpretation; here an Adobe APP14 segment
-        (transform 0 = as stored, 1 = YCbCr) says the same thing to Pillow's libjpeg."""
+        (transform 0 = as stored, 1 = YCbCr) says the same thing to Pillow's libjpeg. Four bands need none: libjpeg takes four
+        components as stored (CMYK), and Pillow's JPEG plugin, which reads CMYK in Adobe's inverted polarity, is told to unpack the
+        decoder's bytes as they are — the samples the file stores, which is what libtiff hands out for RGB + extra sample.
+        An Adobe segment of the block's own that names a transform (YCCK) is refused: libtiff would not convert it either."""
         import io
         from PIL import Image
         data = bytes(raw)
@@ -203,8 +210,12 @@ class GeoTiff:
             head += b"\xff\xee\x00\x0eAdobe\x00\x64\x00\x00\x00\x00" + (b"\x01" if ycc else b"\x00")
         stream = head + self._jpeg_tables[2:-2] + data[2:]
         with Image.open(io.BytesIO(stream)) as im:
-            if im.format != "JPEG" or im.mode not in ("L", "RGB"):
+            if im.format != "JPEG" or im.mode != {1: "L", 3: "RGB", 4: "CMYK"}[self.count]:
                 raise ValueError(f"{self.path}: a JPEG block decodes to mode {im.mode}")
+            if self.count == 4:
+                if im.info.get("adobe_transform", 0) != 0:
+                    raise ValueError(f"{self.path}: a four-band JPEG block with Adobe colour transform {im.info['adobe_transform']} (YCCK)")
+                im.tile = [(t[0], t[1], t[2], ("CMYK",) + tuple(t[3][1:])) for t in im.tile]     # raw mode CMYK, not "CMYK;I": no inversion
             arr = np.asarray(im)
         arr = arr[:, :, None] if arr.ndim == 2 else arr
         if arr.shape[0] < rows or arr.shape[1] != self._bw or arr.shape[2] != self.count:
@@ -367,9 +378,9 @@ class GeoTiff:
     # -- compressed raster → HBM (tiffdecode.hip) --------------------------------------------------------------------------
     def device_decodable(self, float_samples: bool = False) -> bool:
         """True when the raster's blocks can be decoded on the GPU: LZW or DEFLATE (zlib) strips or tiles of pixel-interleaved
-        uint8 or native-order (little-endian) uint16 samples (<= 4 per pixel), predictor 1 or 2; JPEG (compression 7) grey or
-        three-band blocks when the host plan (td_tiff_jpeg_plan: sequential Huffman, 8-bit, 4:4:4 / 4:2:2 / 4:2:0) accepts every
-        one of them. ``float_samples=True`` (the height raster of the post-processing stage; the tile loop never asks) also admits
+        uint8 or native-order (little-endian) uint16 samples (<= 4 per pixel), predictor 1 or 2; JPEG (compression 7) grey,
+        three-band or four-band blocks when the host plan (td_tiff_jpeg_plan: sequential Huffman, 8-bit, 4:4:4 / 4:2:2 / 4:2:0, four
+        components all 1x1 and stored as they are) accepts every one of them. ``float_samples=True`` (the height raster of the post-processing stage; the tile loop never asks) also admits
         native-order float32 samples in the same LZW / DEFLATE layouts, predictor 1, 2 or 3 (floating-point predictor). Everything
         else keeps the host reader: big-endian and planar files, PackBits, int16 / int32 and float64 samples, 12-bit JPEG."""
         self._setup_blocks()
@@ -405,7 +416,7 @@ class GeoTiff:
         if len(offs) == nb == len(cnts) and int((offs + cnts).max()) <= self._mm.size and int(offs.min()) >= 0:
             rows = np.array([self._block_rows(by) for by in range(self._ny) for _ in range(self._nx)], dtype=np.int32)
             tables = np.frombuffer(self._jpeg_tables, dtype=np.uint8) if self._jpeg_tables else np.zeros(1, np.uint8)
-            photometric = int(self.tags.get(262, [2 if self.count == 3 else 1])[0])
+            photometric = int(self.tags.get(262, [2 if self.count >= 3 else 1])[0])
             info = np.zeros((nb, 8), dtype=np.int64)
             totals = np.zeros(4, dtype=np.int64)
             segs, sets = np.zeros((nb, 4), dtype=np.int64), np.zeros((4, _lib.JPEG_TABSET_BYTES), dtype=np.uint8)
@@ -766,20 +777,24 @@ class _NullCtx:
 
 def _jpeg_block(blk: np.ndarray, quality: int = 90, subsampling: int = 2, restart: int = 0) -> bytes:
     """One strip / tile as a COMPLETE JPEG stream (its own tables: the JPEGTables tag is optional, TIFF Technical Note 2), YCbCr 4:2:0
-    for three bands (``subsampling`` 0 = 4:4:4, 1 = 4:2:2), a restart marker every ``restart`` MCUs when > 0 — Pillow's libjpeg
-    encoder. Lossy: a test fixture for the windowed JPEG reader, not an archive format."""
+    for three bands (``subsampling`` 0 = 4:4:4, 1 = 4:2:2), four bands as four components sampled 1x1 and stored as they are (Pillow's
+    CMYK encoder inverts what it is given, Adobe's polarity, so it is given the inverse), a restart marker every ``restart`` MCUs
+    when > 0 — Pillow's libjpeg encoder. Lossy: a test fixture for the windowed JPEG reader, not an archive format."""
     import io
     from PIL import Image
     buf = io.BytesIO()
     kw = {"restart_marker_blocks": int(restart)} if restart else {}
-    Image.fromarray(blk[:, :, 0] if blk.shape[2] == 1 else blk).save(buf, "JPEG", quality=quality,
-                                                                       subsampling=subsampling if blk.shape[2] == 3 else 0, **kw)
+    if blk.shape[2] == 4:
+        im = Image.frombytes("CMYK", (blk.shape[1], blk.shape[0]), (255 - blk).tobytes())
+    else:
+        im = Image.fromarray(blk[:, :, 0] if blk.shape[2] == 1 else blk)
+    im.save(buf, "JPEG", quality=quality, subsampling=subsampling if blk.shape[2] == 3 else 0, **kw)
     return buf.getvalue()
 
 
 def _jpeg_split(stream: bytes) -> Tuple[bytes, bytes]:
     """A complete JPEG stream → (its tables as a JPEGTables tag: SOI, DQT / DHT segments, EOI; the abbreviated stream without them
-    and without JFIF) — the layout GDAL / libtiff write (TIFF Technical Note 2)."""
+    and without JFIF or Adobe segment) — the layout GDAL / libtiff write (TIFF Technical Note 2)."""
     tables, rest = [b"\xff\xd8"], [b"\xff\xd8"]
     pos = 2
     while pos < len(stream):
@@ -791,7 +806,7 @@ def _jpeg_split(stream: bytes) -> Tuple[bytes, bytes]:
         seg = stream[pos:pos + 2 + n]
         if m in (0xDB, 0xC4):
             tables.append(seg)
-        elif m != 0xE0:
+        elif m not in (0xE0, 0xEE):
             rest.append(seg)
         pos += 2 + n
     return b"".join(tables) + b"\xff\xd9", b"".join(rest)
@@ -810,7 +825,8 @@ def write_geotiff(path: str, data: np.ndarray, transform: Sequence[float], epsg:
     32-bit accumulator undoes) / 3 (floating-point predictor, TIFF Technical Note 3: float32 only), ``planar`` (one block grid per band). JPEG: ``jpeg_tables`` writes the GDAL / libtiff
     layout (the quantisation and Huffman tables once, in the JPEGTables tag; abbreviated blocks without JFIF) instead of complete
     streams; ``jpeg_restart`` > 0 puts a restart marker every that many MCUs; ``jpeg_quality``, ``jpeg_subsampling`` (2 = 4:2:0,
-    1 = 4:2:2, 0 = 4:4:4 for three bands)."""
+    1 = 4:2:2, 0 = 4:4:4 for three bands). Four bands: RGB + one unspecified extra sample (what GDAL writes for RGBI), four components
+    sampled 1x1 without a colour transform."""
     arr = np.asarray(data)
     if arr.ndim == 2:
         arr = arr[None]
@@ -829,8 +845,8 @@ def write_geotiff(path: str, data: np.ndarray, transform: Sequence[float], epsg:
             raise ValueError("tile sides must be multiples of 16")
     else:
         bh, bw = int(rows_per_strip or H), W
-    if compression == "jpeg" and (planar or predictor != 1 or arr.dtype != np.uint8 or C not in (1, 3) or bh % 16):
-        raise ValueError("jpeg: uint8 grey / three-band chunky rasters, no predictor, block heights in multiples of 16")
+    if compression == "jpeg" and (planar or predictor != 1 or arr.dtype != np.uint8 or C not in (1, 3, 4) or bh % 16):
+        raise ValueError("jpeg: uint8 grey / three-band / four-band chunky rasters, no predictor, block heights in multiples of 16")
     ny, nx = (H + bh - 1) // bh, (W + bw - 1) // bw
     blocks = []
     for p in range(C if planar else 1):
@@ -890,7 +906,7 @@ def write_geotiff(path: str, data: np.ndarray, transform: Sequence[float], epsg:
     add(257, 4, [H])
     add(258, 3, [fmt[1]] * C)
     add(259, 3, [{"deflate": 8, "lzw": 5, "jpeg": 7}.get(compression, 1)])
-    add(262, 3, [(6 if compression == "jpeg" else 2) if C >= 3 else 1])
+    add(262, 3, [(6 if compression == "jpeg" and C == 3 else 2) if C >= 3 else 1])
     add(277, 3, [C])
     add(284, 3, [2 if planar else 1])
     if predictor != 1:

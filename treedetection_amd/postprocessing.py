@@ -486,7 +486,7 @@ def _ndvi_on_device(rg: GeoTiff, n_scale: float, config, device: int):
     3 resampled to [int(rows * n_scale), int(cols * n_scale)] and turned into NDVI by one call of td_resample_gdal_dev (mode "ndvi";
     with ``n_scale`` 1 the same kernels run with identity taps) → float32 CUDA tensor for :func:`crown_stats`. None when the host
     reader has to serve it, by the gating of :func:`_height_on_device`: ``device_decode`` not explicitly true / "all", a raster that
-    is not uint8 with four bands in a layout the device decoders take (LZW / DEFLATE, pixel-interleaved), or a corrupt block (printed)."""
+    is not uint8 with four bands in a layout the device decoders take (LZW / DEFLATE / JPEG, pixel-interleaved), or a corrupt block (printed)."""
     if not _device_decode_on(config):
         return None
     out_h, out_w = int(rg.height * n_scale), int(rg.width * n_scale)
