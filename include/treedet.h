@@ -119,6 +119,15 @@ td_status td_engine_forward_phase(td_engine* e, int phase, const void* images, i
  * "rpn_cand_idx","rpn_cand_scores","rpn_cand_valid","rpn_cand_boxes" ([B,5,1024(,4)]), "rpn_keep" ([B,5,1024]) and
  * "rpn_keep_count" ([B,5]). The "rpn_head*" pointers may be overwritten between phase 0 and phase 1 of
  * td_engine_forward_phase (after phase 0 has completed on its stream): stage tests feed crafted heads that way.
+ * Of the detection stage: "box_pred" ([B*P,6] float32 in both precisions: two logits, foreground first, then four
+ * deltas), "det_all_boxes" / "det_all_scores" / "det_flags" ([B,P(,4)], flags int32), "det_sorted_boxes" /
+ * "det_sorted_scores" ([B,P(,4)]: the flagged rows by score descending, index ascending) with "det_sorted_count" ([B]
+ * int32), "det_keep" ([B,D] int32 positions in the sorted list) with "det_keep_count" ([B] int32), "det_boxes_net";
+ * of the mask tail: "mask_deconv" ([B*D,28,28,C], float16 in the fp16 engine), "mask_logits" and
+ * "mask_probs_compact" ([B*D,28,28] float32; the first total = sum of counts rows are live). The same way,
+ * "proposals", "proposal_count" (int32, every entry within [0, P]) and "box_pred" may be overwritten between phase 2
+ * and phase 3, and "mask_deconv" between phase 4 and phase 5, each after the earlier phase has completed on its
+ * stream: the later phases then run on the crafted values. No other buffer may be written.
  * dims is filled with up to 4 extents (0-padded); *elem_size with the element size in bytes. */
 td_status td_engine_tensor(td_engine* e, const char* name, void** dev_ptr, int64_t dims[4], int* elem_size);
 /* Copy that activation into a caller-owned device buffer of `bytes` bytes (asynchronous on `stream`). */

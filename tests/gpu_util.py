@@ -66,11 +66,17 @@ class _DeviceArray:
         self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2}
 
 
-def engine_tensor_view(eng, name):
-    """Zero-copy float32 torch view of an engine buffer (the raw pointer td_engine_tensor returns), for stage tests that
-    overwrite it between two phases: ``view.copy_(crafted)``. The engine owns the memory; use the view at once."""
+def engine_tensor_view(eng, name, dtype=None):
+    """Zero-copy torch view of an engine buffer (the raw pointer td_engine_tensor returns), for stage tests that overwrite
+    it between two phases: ``view.copy_(crafted)``. ``dtype``: None = the buffer's floating type (float32 for 4-byte
+    elements, float16 for 2-byte ones); torch.int32 for the 4-byte integer buffers (counts, flags, index lists) — the ABI
+    reports the element size only. The engine owns the memory; use the view at once."""
     import ctypes as C
     ptr, dims, elem = C.c_void_p(), (C.c_int64 * 4)(), C.c_int()
     _lib.check(eng.lib.td_engine_tensor(eng._h, name.encode(), C.byref(ptr), dims, C.byref(elem)), "td_engine_tensor")
-    assert elem.value == 4 and ptr.value, (name, elem.value)
-    return torch.as_tensor(_DeviceArray(ptr.value, [int(d) for d in dims if d > 0], "<f4"), device=torch.device("cuda", eng.device))
+    assert elem.value in (2, 4) and ptr.value, (name, elem.value)
+    if dtype is None:
+        dtype = torch.float32 if elem.value == 4 else torch.float16
+    typestr = {torch.float32: "<f4", torch.int32: "<i4", torch.float16: "<f2"}[dtype]
+    assert int(typestr[2]) == elem.value, (name, dtype, elem.value)
+    return torch.as_tensor(_DeviceArray(ptr.value, [int(d) for d in dims if d > 0], typestr), device=torch.device("cuda", eng.device))

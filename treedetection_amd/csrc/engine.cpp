@@ -1379,9 +1379,14 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
     { ProfScope ps(e, s, 5);
     if ((st = sort_boxes_launch(e->dboxes, e->dscores, e->dflags, e->prop_count, B, P, e->sboxes, e->sscores, e->sidx,
                                 e->scount, s)) < 0) return st; }
+    set_named(e, "det_sorted_boxes", e->sboxes, B, P, 4);
+    set_named(e, "det_sorted_scores", e->sscores, B, P);
+    set_named(e, "det_sorted_count", e->scount, B);
     { ProfScope ps(e, s, 5);
     if ((st = nms_launch(e->sboxes, e->scount, nullptr, B, P, e->desc.nms_thresh, e->nms_mask, e->det_keep,
                          e->det_keep_count, D, s)) < 0) return st; }
+    set_named(e, "det_keep", e->det_keep, B, D);
+    set_named(e, "det_keep_count", e->det_keep_count, B);
     { ProfScope ps(e, s, 5);
     if ((st = det_finalize_launch(e->sboxes, e->sscores, e->det_keep, e->det_keep_count, valid, outsz, B, P, D,
                                   e->det_boxes_net, o_boxes, o_scores, o_classes, o_count, s)) < 0) return st; }
@@ -1410,6 +1415,7 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
     if ((st = mask_predict_launch(e->deconv_out, e->mask_pred_w, e->mask_pred_b, e->deconv.cout / 4, mrows * 784,
                                   e->total_rows, 784, e->mask_logits, e->mask_probs_compact, prec, s)) < 0) return st; }
     set_named(e, "mask_logits", e->mask_logits, mrows, 28, 28);
+    set_named(e, "mask_probs_compact", e->mask_probs_compact, mrows, 28, 28);
     { ProfScope ps(e, s, 6);
     if ((st = mask_scatter_launch(e->mask_probs_compact, o_count, B, D, o_probs, s)) < 0) return st; }
     if (out->mask_bits) {

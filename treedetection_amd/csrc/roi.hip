@@ -438,8 +438,9 @@ __global__ void det_decode_kernel(const float* __restrict__ cls_reg, int cr_stri
         score = __fdiv_rn(e0, __fadd_rn(e0, e1));
         const float4 p = *reinterpret_cast<const float4*>(props + (size_t)idx * 4);
         decode_box(p.x, p.y, p.z, p.w, cr[2], cr[3], cr[4], cr[5], 10.f, 10.f, 5.f, 5.f, x1, y1, x2, y2);
+        // (fminf in decode_box's clamp returns the other operand for a NaN dw / dh where the oracle's minimum keeps the NaN)
         const bool fin = isfinite(x1) && isfinite(y1) && isfinite(x2) && isfinite(y2) && isfinite(score) &&
-                         isfinite(__fsub_rn(1.f, score));
+                         isfinite(__fsub_rn(1.f, score)) && !isnan(cr[4]) && !isnan(cr[5]);
         const float ih = (float)valid.h[b], iw = (float)valid.w[b];
         x1 = fminf(fmaxf(x1, 0.f), iw);
         y1 = fminf(fmaxf(y1, 0.f), ih);
