@@ -423,6 +423,24 @@ td_status td_tiff_jpeg_decode_dev(const uint8_t* comp, const int64_t* block_info
  * receives (height, width, components). Returns the bytes written, TD_ERR_UNSUPPORTED, TD_ERR_INVALID (corrupt stream) or
  * TD_ERR_CAPACITY. */
 int64_t td_jpeg_decode(const uint8_t* src, int64_t n, uint8_t* dst, int64_t cap, int32_t* shape);
+/* td_tiff_jpeg_decode_dev for rasters with entropy-coded segments too long for one lane (blocks without restart markers). The plan's
+ * segments come as two lists (DEVICE int64 [n][4], either may be empty): segs_short goes through the lane-per-segment kernel as
+ * above; each segment of segs_long is decoded by the 64 lanes of one wave (self-synchronising Huffman decoding, jpeg_core.h: the
+ * bytes are cut into subsequences of subseq_bytes (4 .. 1 << 20) raw bytes, 64 of them form a window, the lanes walk them from
+ * guessed states and again from their predecessor's exit state until the states agree, at most 64 rounds a window; then they write
+ * the coefficients, and a second kernel turns the DC differences into DC values, one wave per (segment, component)). Same
+ * coefficients, same status as one lane gives, then the same IDCT and pixel kernels. stats: DEVICE int64 [4], zeroed here, then
+ * {walk rounds summed over the windows, windows, the most rounds one window took, windows that took one round} of the long segments.
+ * nshort + nlong >= nblocks. Asynchronous on `stream`, whose device must be the calling thread's current one. */
+td_status td_tiff_jpeg_decode_long_dev(const uint8_t* comp, const int64_t* block_info, int nblocks, const int64_t* segs_short, int nshort,
+                                       const int64_t* segs_long, int nlong, int subseq_bytes, const void* tabsets, int16_t* coef,
+                                       uint8_t* planes, int64_t coef_count, int32_t* status, int64_t* stats, uint8_t* image, int width,
+                                       int height, int bands, int block_w, int block_h, int blocks_across, void* stream);
+/* td_jpeg_decode with every entropy-coded segment decoded by that window procedure on one host thread, `lanes` (1 .. 64) emulated
+ * lanes walking subsequences of subseq_bytes bytes: the same bytes and the same errors as td_jpeg_decode. stats (int64 [4], may be
+ * NULL) receives what td_tiff_jpeg_decode_long_dev counts. */
+int64_t td_jpeg_decode_sync(const uint8_t* src, int64_t n, uint8_t* dst, int64_t cap, int32_t* shape, int subseq_bytes, int lanes,
+                            int64_t* stats);
 /* Window of an uncompressed pixel-interleaved raster with contiguous strips (the tile windows of reference
  * prediction.py:164, rasterio.mask.mask(..., crop=True)): `rows` pieces of `row_bytes` bytes lying `row_stride` bytes apart
  * from `file_off` on, read with pread(2) into the dense buffer dst (e.g. pinned staging memory). Returns the bytes read or

@@ -1,10 +1,11 @@
 """Files-to-files Predictor rate on a JPEG-in-TIFF raster, device decoder on ("auto" / true) against the host reader (false):
 python tools/jpeg_e2e.py [side=9000] [tile=256] [quality=90] [subsampling=2] [layout=complete|gdal] [restart=0] [precision=fp16]
-[batch=16] [images=3] [modes=true,false] [bands=3|4]
+[batch=16] [images=3] [modes=true,false] [bands=3|4] [device_decode_long_jpeg=false|true]
 The raster (side x side x bands uint8, synthetic orthophoto tiles; bands=4 adds the green band again as a near-infrared band: RGBI,
 of which the tile loop reads bands 0 - 2) is cut into the reference's 450 x 450 px tiles; every mode predicts
 one warm-up image, then `images` images back to back as detection.predict_on_model walks them (the next one prefetched while the
-current one predicts). Prints one JSON line: tiles/s per mode, the decode stats, and whether the Prediction_*.json files are identical."""
+current one predicts). ``device_decode_long_jpeg=true`` passes the config key of that name: a raster without restart markers, which the
+device modes otherwise leave to the host reader, is decoded on the device with a wave per entropy-coded segment. Prints one JSON line: tiles/s per mode, the decode stats, and whether the Prediction_*.json files are identical."""
 import json
 import os
 import shutil
@@ -25,6 +26,7 @@ from treedetection_amd.weights import make_synthetic_state_dict   # noqa: E402
 args = dict(a.split("=", 1) for a in sys.argv[1:] if "=" in a)
 side, tile, nimg, bands = int(args.get("side", 9000)), int(args.get("tile", 256)), int(args.get("images", 3)), int(args.get("bands", 3))
 modes = [m if m in ("auto", "all") else m == "true" for m in args.get("modes", "true,false").split(",")]
+long_jpeg = args.get("device_decode_long_jpeg", "false")
 base = "/dev/shm" if os.path.isdir("/dev/shm") and os.access("/dev/shm", os.W_OK) else None
 root = tempfile.mkdtemp(prefix="td_jpeg_e2e_", dir=base)
 try:
@@ -53,12 +55,12 @@ try:
     sd = make_synthetic_state_dict(int(args.get("depth", 50)), seed=0)
     cfg = T.setup_model_cfg(update_model="synthetic", device="0")
     res = {"raster": f"{side}x{side}x{bands} uint8 JPEG, {tile}x{tile} tiles", "tiles_per_image": ntiles, "file_bytes": os.path.getsize(tif),
-           "precision": args.get("precision", "fp16")}
+           "precision": args.get("precision", "fp16"), "device_decode_long_jpeg": long_jpeg}
     outs = {}
     for dd in modes:
         out = f"{root}/out_{dd}"
         pred = T.Predictor(cfg, device_type="0", max_batch_size=int(args.get("batch", 16)), output_dir=out, precision=args.get("precision", "fp16"),
-                           state_dict=sd, return_predictions=False, device_decode=dd)
+                           state_dict=sd, return_predictions=False, device_decode=dd, device_decode_long_jpeg=long_jpeg)
         try:
             pred.prefetch(tif)
             pred(tif, tjson)                               # warm-up image

@@ -1,7 +1,10 @@
 """Decode rate of LZW / DEFLATE / JPEG rasters on the GPU (tiffdecode.hip, jpegdecode.hip): python tools/raster_decode_bench.py
 [codec=lzw|deflate|jpeg] [side=9000] [tile=256|strip=N] [predictor=2] [data=tiles|noise|flat]
 JPEG (predictor ignored): [bands=3 | 4 (RGB + near-infrared: four components as stored, subsampling ignored) | 1] [quality=90] [subsampling=2 (4:2:0) | 1 (4:2:2) | 0 (4:4:4)] [layout=complete|gdal] [restart=MCUs]
-[host_threads=16] — also times the host reader (Pillow's libjpeg per block, on that many threads) on the same raster and checks that
+[long=1 [subseq=256] [threshold=32768]: a raster with entropy-coded segments above GeoTiff.JPEG_DEVICE_MAX_SEGMENT (no restart markers),
+which otherwise "stays with the host reader", is decoded on the device with a wave per long segment (decode_to_device(long_segments=True));
+the line then carries the long segments, the walk rounds per window of 64 subsequences (mean, the most, windows of one round) and the
+subsequence size] [host_threads=16] — also times the host reader (Pillow's libjpeg per block, on that many threads) on the same raster and checks that
 both give the same bytes.
 Raster side x side x 4 uint8 (default 9000: the 400 windows of 450 x 450 px the reference cuts from one image, twice over); prints per
 call file → pinned → device → decoded raster in HBM, and the kernels alone (HIP events). Under rocprofv3 --kernel-trace --stats the
@@ -174,15 +177,24 @@ try:
     pinned, pool = [None], ThreadPoolExecutor(max_workers=8)
     # a JPEG raster the device decoder does not take (a segment above GeoTiff.JPEG_DEVICE_MAX_SEGMENT: one lane would walk it alone)
     # stays with the host reader under every setting: only the host reader is timed, and the line says so
-    on_device = codec != "jpeg" or g.device_decodable()
+    long_kw = {}
+    if codec == "jpeg" and args.get("long", "0") == "1":
+        long_kw = {"long_segments": True, "subseq_bytes": int(args.get("subseq", GeoTiff.JPEG_SYNC_SUBSEQ)),
+                   "long_threshold": int(args["threshold"]) if "threshold" in args else None}
+    on_device = codec != "jpeg" or g.device_decodable(long_segments=bool(long_kw))
+    sync = {}
     dev0 = slow = None
     for k in range(5 if on_device else 0):
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t0 = time.perf_counter()
-        image, check = g.decode_to_device("cuda:0", None, pinned, pool)
+        image, check = g.decode_to_device("cuda:0", None, pinned, pool, **long_kw)
         got = check()
         times.append(time.perf_counter() - t0)
+        if long_kw:
+            st = check.sync_stats
+            sync = {"long_segments": check.long_segments, "subseq_bytes": long_kw["subseq_bytes"], "windows": st[1],
+                    "rounds_per_window": round(check.sync_rounds, 2), "most_rounds_of_a_window": st[2], "windows_of_one_round": st[3]}
         ktimes.append(check.kernel_ms)
         slow = getattr(check, "slow_codes", 0)
         if k == 0 and codec == "jpeg":
@@ -252,7 +264,8 @@ try:
         extra = {"quality": kw["jpeg_quality"], "subsampling": kw["jpeg_subsampling"], "layout": args.get("layout", "complete"),
                  "restart": kw["jpeg_restart"], "segments": len(segs), "table_sets": len(sets), "host_threads": nth,
                  "host_reader_ms": [round(t * 1e3, 1) for t in host_s], "device_equals_host_reader": True if on_device else None,
-                 "device_decodable": on_device, "largest_segment_bytes": int(segs[:, 1].max())}
+                 "device_decodable": on_device, "largest_segment_bytes": int(segs[:, 1].max()),
+                 "decodable_without_long": g.device_decodable(), **sync}
         kw = {k: v for k, v in kw.items() if not k.startswith("jpeg_")}
     raw = img.nbytes
     if not on_device:

@@ -220,6 +220,306 @@ TD_JPG_HD TD_JPG_INLINE int jpeg_decode_segment(const JpegTables& T, const JpegG
     return left > 0 && (uint32_t)(b.acc >> (64 - left)) != (1u << left) - 1u;
 }
 
+// ---- one long segment decoded by many lanes: self-synchronising Huffman decoding ------------------------------------------------
+// A segment's bytes are cut into subsequences of S raw bytes; 64 consecutive ones form a window, one per lane. The state of a decoder
+// between two symbols (a Huffman code + its extra bits) is (bit position, zig-zag index k in the current 8x8 block with k == 0 = "a DC
+// code comes next", index j of that block in its MCU): two decoders in the same state have the same future. Lane 0 of a window enters
+// with the true state; every other lane guesses (its first byte, k = 0, j = 0), walks its subsequence WITHOUT writing and records the
+// state at the first symbol boundary at or past the subsequence's end and the blocks it completed. Then rounds: lane i takes lane
+// i - 1's exit and walks again when it differs from the entry it last walked from. A lane is validated when its predecessor is and its
+// entry equals the predecessor's exit; the validated lanes are a growing prefix (at least one more per round), so at most 64 rounds,
+// and a few when the stream synchronises. An exclusive prefix sum of the validated counts gives each lane the ordinal of its first
+// block; a last walk from the validated entries writes the coefficients (DC: the DIFFERENCE — jpeg_sync_dc / jpeg_dc_scan_kernel sums them).
+//
+// The bit position is (raw byte index, bit 0..7 from the MSB) of the next unconsumed bit, canonical: the byte index never names the
+// 00 of a stuffed FF 00 (inside the data a 00 after an FF is always the stuffed one, an FF followed by anything else ends the data),
+// and a guess that would start on such a 00 starts one byte later. A position at the end of the data is (index of the marker, 0).
+// "Lost" (an invalid code, a size beyond the 8-bit limits, a run past coefficient 63, bits consumed past the end of the data) equals
+// no state: the successor of a lost guess keeps its own guess; the successors of a lost VALIDATED lane have nothing left to decode.
+typedef uint64_t JpegSyncState;                            // byte | bit << 32 | k << 35 | j << 41
+constexpr JpegSyncState JPG_SYNC_LOST = ~(uint64_t)0;
+constexpr uint32_t JPG_SYNC_NO_END = 0xFFFFFFFFu;          // the segment's last subsequence ends with the blocks, not at a byte
+constexpr int JPG_SYNC_MIN_SUBSEQ = 4, JPG_SYNC_MAX_SUBSEQ = 1 << 20;      // a symbol is at most 27 bits
+
+TD_JPG_HD JpegSyncState jpeg_sync_state(uint32_t byte, int bit, int k, int j) {
+    return (uint64_t)byte | (uint64_t)bit << 32 | (uint64_t)k << 35 | (uint64_t)j << 41;
+}
+
+// JpegBits + what it takes to name the position of the next bit: which of the bytes in acc were an FF with its stuffed 00.
+struct JpegSyncBits {
+    JpegBits b;
+    uint32_t stuff;                      // bit i: the (i + 1)-th most recently fetched data byte took two raw bytes
+#ifdef __HIP_DEVICE_COMPILE__
+    uint32_t word, wat;                  // the compressed bytes come a dword at a time: the aligned dword last loaded, and which
+#endif
+};
+
+TD_JPG_HD TD_JPG_INLINE uint32_t jpeg_sync_byte(JpegSyncBits& r, uint32_t i) {       // byte i < n of the segment
+#ifdef __HIP_DEVICE_COMPILE__
+    const uintptr_t lo = (uintptr_t)r.b.p, a = lo + i, q = a & ~(uintptr_t)3;
+    const uint32_t at = (uint32_t)((q - (lo & ~(uintptr_t)3)) >> 2);
+    if (at != r.wat) {
+        r.wat = at;
+        if (q >= lo && q + 4 <= lo + r.b.n) {
+            r.word = *reinterpret_cast<const uint32_t*>(q);
+        } else {                                           // the dwords that hold the segment's first and last bytes: those bytes only
+            r.word = 0;
+            for (int t = 0; t < 4; ++t)
+                if (q + t >= lo && q + t < lo + r.b.n) r.word |= (uint32_t)*reinterpret_cast<const uint8_t*>(q + t) << (8 * t);
+        }
+    }
+    return (r.word >> (8 * (int)(a & 3))) & 255u;
+#else
+    return r.b.p[i];
+#endif
+}
+
+TD_JPG_HD TD_JPG_INLINE void jpeg_sync_fill(JpegSyncBits& r) {       // jpeg_fill, keeping r.stuff
+    JpegBits& b = r.b;
+    while (b.have <= 56) {
+        uint32_t v = 0;
+        if (b.pad == 0 && b.pos < b.n) {
+            v = jpeg_sync_byte(r, b.pos);
+            if (v != 0xFF) {
+                ++b.pos;
+                r.stuff <<= 1;
+            } else if (b.pos + 1 < b.n && jpeg_sync_byte(r, b.pos + 1) == 0) {
+                b.pos += 2;
+                r.stuff = r.stuff << 1 | 1u;
+            } else {
+                v = 0;
+                b.pad = 8;
+            }
+        } else {
+            b.pad += 8;
+        }
+        b.acc |= (uint64_t)v << (56 - b.have);
+        b.have += 8;
+    }
+}
+
+TD_JPG_HD TD_JPG_INLINE void jpeg_sync_open(JpegSyncBits& r, const uint8_t* src, uint32_t n, JpegSyncState at) {
+    r.b.p = src;
+    r.b.pos = (uint32_t)at;
+    r.b.n = n;
+    r.b.acc = 0;
+    r.b.have = 0;
+    r.b.pad = 0;
+    r.stuff = 0;
+#ifdef __HIP_DEVICE_COMPILE__
+    r.word = 0;
+    r.wat = 0xFFFFFFFFu;
+#endif
+    jpeg_sync_fill(r);
+    const int bit = (int)(at >> 32) & 7;
+    r.b.acc <<= bit;
+    r.b.have -= bit;
+}
+
+// The canonical byte of the next unconsumed bit (have >= pad: no padding consumed) and its bit.
+TD_JPG_HD TD_JPG_INLINE uint32_t jpeg_sync_at(const JpegSyncBits& r, int& bit) {
+    const int real = r.b.have - r.b.pad, nb = (real + 7) >> 3;
+    bit = (8 - (real & 7)) & 7;
+    return r.b.pos - (uint32_t)nb - (uint32_t)__builtin_popcount(r.stuff & ((1u << nb) - 1u));
+}
+
+// What a lane other than a window's first assumes at the start of subsequence `sub` (> 0) of S bytes.
+TD_JPG_HD JpegSyncState jpeg_sync_guess(const uint8_t* src, uint32_t n, uint32_t sub, uint32_t S) {
+    uint32_t at = sub * S;
+    if (at < n && src[at] == 0 && src[at - 1] == 0xFF) ++at;         // the boundary fell between an FF and its stuffed 00
+    return jpeg_sync_state(at, 0, 0, 0);
+}
+
+TD_JPG_HD int jpeg_sync_blocks_per_mcu(const JpegGeom& g, bool four) { return four ? 4 : (g.ncomp == 1 ? 1 : g.hmax * g.vmax + 2); }
+
+// Block j of MCU m → its component and where its 64 coefficients start (what jpeg_decode_segment computes).
+template <bool FOUR>
+TD_JPG_HD TD_JPG_INLINE int64_t jpeg_sync_block_at(const JpegGeom& g, uint32_t m, int j, int& c) {
+    const int mx = (int)(m % (uint32_t)g.mcus_x), my = (int)(m / (uint32_t)g.mcus_x);
+    if constexpr (FOUR) {
+        c = j;
+        return (int64_t)j * ((int64_t)g.mcus_x * g.mcus_y * 64) + ((int64_t)my * g.mcus_x + mx) * 64;
+    }
+    const int ny = g.hmax * g.vmax;
+    if (g.ncomp == 1 || j < ny) {
+        c = 0;
+        const int v = g.ncomp == 1 ? 0 : j / g.hmax, h = g.ncomp == 1 ? 0 : j - v * g.hmax;
+        return ((int64_t)(my * g.vmax + v) * g.bw[0] + mx * g.hmax + h) * 64;
+    }
+    c = j - ny + 1;                                        // Cb or Cr (selected, not indexed: g stays in registers)
+    return (c == 1 ? g.off[1] : g.off[2]) + ((int64_t)my * g.bw[1] + mx) * 64;
+}
+
+// One walk: from `entry` over the symbols that start before byte `end` of [src, src + n) (JPG_SYNC_NO_END: until the data gives out).
+// → the exit state or JPG_SYNC_LOST; blocks: how many it completed. WRITE: the walk of a validated entry whose first block has ordinal
+// `first` in the segment, `limit` (> 0) blocks short of the segment's last: the non-zero AC coefficients and the DC differences go to
+// coef (zeroed), block by block as jpeg_sync_block_at places them; flags |= 1: corrupt data (everything jpeg_block reports but the DC
+// value itself), |= 2: the walk completed the segment's last block and has checked the bits that are left as jpeg_decode_segment
+// does. Without WRITE nothing is stored and g, coef, mcu0, first, limit and flags are not used.
+template <bool FOUR, bool WRITE>
+TD_JPG_HD TD_JPG_INLINE JpegSyncState jpeg_sync_walk(const JpegTables& T, const JpegGeom& g, const uint8_t* src, uint32_t n,
+                                                     JpegSyncState entry, uint32_t end, uint32_t& blocks, int16_t* coef, uint32_t mcu0,
+                                                     uint32_t first, uint32_t limit, int& flags) {
+    const int bpm = jpeg_sync_blocks_per_mcu(g, FOUR), ny = bpm - 2;
+    JpegSyncBits r;
+    jpeg_sync_open(r, src, n, entry);
+    JpegBits& b = r.b;
+    int k = (int)(entry >> 35) & 63, j = (int)(entry >> 41) & 7, c = 0;
+    uint32_t m = 0;
+    int16_t* blk = nullptr;
+    if constexpr (WRITE) {
+        j = (int)(first % (uint32_t)bpm);
+        m = mcu0 + first / (uint32_t)bpm;
+        blk = coef + jpeg_sync_block_at<FOUR>(g, m, j, c);
+    } else {
+        c = FOUR || g.ncomp == 1 ? j : (j < ny ? 0 : j - ny + 1);
+    }
+    blocks = 0;
+    for (;;) {
+        if (b.have < 32) jpeg_sync_fill(r);
+        if (b.have < b.pad) break;                         // consumed bits past the end of the data
+        if (b.pos >= end) {                                // (the next bit lies at or before pos)
+            int bit;
+            const uint32_t at = jpeg_sync_at(r, bit);
+            if (at >= end) return jpeg_sync_state(at, bit, k, j);
+        }
+        if (k == 0) {
+            const int t = jpeg_huff(T.dc[c], b);
+            if (t < 0 || t > 11) break;
+            const int diff = t ? jpeg_extend(jpeg_bits(b, t), t) : 0;
+            if constexpr (WRITE) blk[0] = (int16_t)diff;
+            k = 1;
+        } else {
+            const int rs = jpeg_huff(T.ac[c], b);
+            if (rs < 0) break;
+            const int run = rs >> 4, s = rs & 15;
+            if (s) {
+                if (s > 10) break;
+                k += run;
+                if (k > 63) break;                         // a run past coefficient 63
+                const int v = jpeg_extend(jpeg_bits(b, s), s);
+                if constexpr (WRITE) {
+                    const int z = jpeg_zigzag(k);
+                    if (!jpeg_coef_ok(v, T.q[c][z])) break;
+                    blk[z] = (int16_t)v;
+                }
+                ++k;
+            } else if (run == 15) {
+                k += 16;
+                if (k > 64) break;
+            } else {
+                k = 64;                                    // end of block
+            }
+        }
+        if (k < 64) continue;
+        if (b.have < b.pad) break;
+        k = 0;
+        ++blocks;
+        if (++j == bpm) {
+            j = 0;
+            ++m;
+        }
+        if constexpr (WRITE) {
+            if (blocks == limit) {                         // the segment's last block: at most 7 bits are left, all ones
+                jpeg_sync_fill(r);
+                const int left = b.have - b.pad;
+                if (b.pad == 0 || left >= 8 || (left > 0 && (uint32_t)(b.acc >> (64 - left)) != (1u << left) - 1u)) flags |= 1;
+                flags |= 2;
+                int bit;
+                const uint32_t at = jpeg_sync_at(r, bit);
+                return jpeg_sync_state(at, bit, 0, j);
+            }
+            blk = coef + jpeg_sync_block_at<FOUR>(g, m, j, c);
+        } else {
+            c = FOUR || g.ncomp == 1 ? j : (j < ny ? 0 : j - ny + 1);
+        }
+    }
+    if constexpr (WRITE) flags |= 1;
+    return JPG_SYNC_LOST;
+}
+
+// Block t (scan order inside the segment that starts at MCU mcu0) of component c → where its coefficients start.
+template <bool FOUR>
+TD_JPG_HD TD_JPG_INLINE int64_t jpeg_sync_dc_block_at(const JpegGeom& g, uint32_t mcu0, int c, uint32_t t) {
+    const int ny = FOUR || g.ncomp == 1 ? 1 : g.hmax * g.vmax;
+    const uint32_t per = c == 0 ? (uint32_t)ny : 1u;
+    const int j = (c == 0 ? 0 : (FOUR ? c : ny + c - 1)) + (int)(t % per);
+    int cc;
+    return jpeg_sync_block_at<FOUR>(g, mcu0 + t / per, j, cc);
+}
+TD_JPG_HD uint32_t jpeg_sync_dc_blocks(const JpegGeom& g, bool four, int c, uint32_t nmcu) {
+    return nmcu * (c == 0 && !four && g.ncomp != 1 ? (uint32_t)(g.hmax * g.vmax) : 1u);
+}
+
+// The window procedure with `lanes` (1 .. 64) emulated lanes on one host thread: jpeg_decode_segment's contract (coef zeroed; → 0 ok,
+// 1 corrupt) by the walks above, lane after lane where a wave runs them side by side (jpegdecode.hip: jpeg_entropy_sync_kernel, which
+// follows this text step by step). stats (may be null) += {rounds summed over the windows, windows, (max) the most rounds one window
+// took, windows that took one round}.
+template <bool FOUR>
+static inline int jpeg_sync_segment(const JpegTables& T, const JpegGeom& g, const uint8_t* src, uint32_t n, uint32_t mcu0, uint32_t nmcu,
+                                    int16_t* coef, uint32_t S, int lanes, int64_t* stats) {
+    const uint32_t total = nmcu * (uint32_t)jpeg_sync_blocks_per_mcu(g, FOUR);
+    const uint32_t nsub = n > S ? (uint32_t)(((uint64_t)n + S - 1) / S) : 1u;
+    JpegSyncState entry[64], exit[64], seen[64], carry = jpeg_sync_state(0, 0, 0, 0);
+    uint32_t cnt[64], base = 0;
+    int none = 0;
+    for (uint32_t w0 = 0; w0 < nsub; w0 += (uint32_t)lanes) {
+        const int L = (int)(nsub - w0 < (uint32_t)lanes ? nsub - w0 : (uint32_t)lanes);
+        auto end_of = [&](int i) { return w0 + (uint32_t)i == nsub - 1 ? JPG_SYNC_NO_END : (w0 + (uint32_t)i + 1) * S; };
+        for (int i = 0; i < L; ++i) {
+            entry[i] = i == 0 ? carry : jpeg_sync_guess(src, n, w0 + (uint32_t)i, S);
+            exit[i] = jpeg_sync_walk<FOUR, false>(T, g, src, n, entry[i], end_of(i), cnt[i], nullptr, 0, 0, 0, none);
+        }
+        int rounds = 1, valid = 0;
+        for (;;) {
+            for (valid = 1; valid < L && entry[valid] == exit[valid - 1]; ++valid) {}
+            if (valid == L || exit[valid - 1] == JPG_SYNC_LOST) break;
+            for (int i = 0; i < L; ++i) seen[i] = exit[i];             // the lanes of a wave all read before any of them walks again
+            for (int i = valid; i < L; ++i)
+                if (seen[i - 1] != JPG_SYNC_LOST && seen[i - 1] != entry[i]) {
+                    entry[i] = seen[i - 1];
+                    exit[i] = jpeg_sync_walk<FOUR, false>(T, g, src, n, entry[i], end_of(i), cnt[i], nullptr, 0, 0, 0, none);
+                }
+            ++rounds;
+        }
+        if (stats) {
+            stats[0] += rounds;
+            stats[1] += 1;
+            if (rounds > stats[2]) stats[2] = rounds;
+            stats[3] += rounds == 1;
+        }
+        int flags = 0;
+        for (int i = 0; i < valid && !(flags & 2); ++i) {
+            if (base >= total) return 1;                   // (only behind a lane that has finished: cannot be reached)
+            uint32_t wrote;
+            jpeg_sync_walk<FOUR, true>(T, g, src, n, entry[i], end_of(i), wrote, coef, mcu0, base, total - base, flags);
+            if (flags & 1) return 1;
+            base += cnt[i];
+        }
+        if (flags & 2) return 0;
+        if (valid < L) return 1;                           // (a validated lane was lost: its write walk has reported it)
+        carry = exit[L - 1];
+    }
+    return 1;                                              // the data gave out before the last block
+}
+
+// DC differences → DC values, component by component in scan order, as jpeg_block predicts and checks them. → 0 ok, 1 corrupt.
+template <bool FOUR>
+static inline int jpeg_sync_dc(const JpegTables& T, const JpegGeom& g, uint32_t mcu0, uint32_t nmcu, int16_t* coef) {
+    int bad = 0;
+    for (int c = 0; c < g.ncomp; ++c) {
+        uint32_t pred = 0;
+        const uint32_t nb = jpeg_sync_dc_blocks(g, FOUR, c, nmcu);
+        for (uint32_t t = 0; t < nb; ++t) {
+            int16_t* blk = coef + jpeg_sync_dc_block_at<FOUR>(g, mcu0, c, t);
+            pred += (uint32_t)(int32_t)blk[0];
+            bad |= !jpeg_coef_ok((int32_t)pred, T.q[c][0]);
+            blk[0] = (int16_t)(int32_t)pred;
+        }
+    }
+    return bad;
+}
+
 // ---- dequantisation + accurate integer IDCT of one 8x8 block ---------------------------------------------------------------------
 TD_JPG_HD uint8_t jpeg_range_limit(int64_t x) {            // the decoder's post-IDCT table, indexed by x & 1023
     const int i = (int)(x & 1023);

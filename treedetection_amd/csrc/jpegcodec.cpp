@@ -421,9 +421,23 @@ extern "C" td_status td_tiff_jpeg_plan(const uint8_t* tables, int64_t tables_len
     return TD_OK;
 }
 
-extern "C" int64_t td_jpeg_decode(const uint8_t* src, int64_t n, uint8_t* dst, int64_t cap, int32_t* shape) {
+namespace {
+
+// One segment of a complete stream: the sequential decoder (subseq == 0), or the window procedure with `lanes` emulated lanes and the
+// DC pass that follows it.
+template <bool FOUR>
+int decode_one_segment(const JpegTables& T, const JpegGeom& g, const uint8_t* src, const Seg& s, int16_t* coef, int subseq, int lanes,
+                       int64_t* stats) {
+    if (subseq == 0) return jpeg_decode_segment<FOUR>(T, g, src + s.off, (uint32_t)s.len, s.mcu0, s.nmcu, coef);
+    if (jpeg_sync_segment<FOUR>(T, g, src + s.off, (uint32_t)s.len, s.mcu0, s.nmcu, coef, (uint32_t)subseq, lanes, stats)) return 1;
+    return jpeg_sync_dc<FOUR>(T, g, s.mcu0, s.nmcu, coef);
+}
+
+// td_jpeg_decode (subseq == 0) and td_jpeg_decode_sync: everything but the entropy decoding of a segment is the same code.
+int64_t decode_stream(const char* name, const uint8_t* src, int64_t n, uint8_t* dst, int64_t cap, int32_t* shape, int subseq, int lanes,
+                      int64_t* stats) {
     if (!src || n < 0 || !dst || cap < 0 || !shape || n >= ((int64_t)1 << 31)) {
-        td_set_error("td_jpeg_decode: bad argument");
+        td_set_error("%s: bad argument", name);
         return TD_ERR_INVALID;
     }
     JpegHeader h;
@@ -432,7 +446,7 @@ extern "C" int64_t td_jpeg_decode(const uint8_t* src, int64_t n, uint8_t* dst, i
     if (n < 4 || src[0] != 0xFF || src[1] != 0xD8) h.why = "no SOI";
     else walk_markers(h, src, n, 2, true);
     if (h.why || !resolve(h, mode, ycc, T)) {
-        td_set_error("td_jpeg_decode: unsupported stream (%s)", h.why ? h.why : "?");
+        td_set_error("%s: unsupported stream (%s)", name, h.why ? h.why : "?");
         return TD_ERR_UNSUPPORTED;
     }
     shape[0] = h.height;
@@ -440,20 +454,20 @@ extern "C" int64_t td_jpeg_decode(const uint8_t* src, int64_t n, uint8_t* dst, i
     shape[2] = h.ncomp;
     const int64_t need = (int64_t)h.width * h.height * h.ncomp;
     if (need > cap) {
-        td_set_error("td_jpeg_decode: %lld bytes, capacity %lld", (long long)need, (long long)cap);
+        td_set_error("%s: %lld bytes, capacity %lld", name, (long long)need, (long long)cap);
         return TD_ERR_CAPACITY;
     }
     const JpegGeom g = jpeg_geom(mode, h.width, h.height);
     std::vector<Seg> cut;
     if (cut_segments(src, h.entropy, n, (uint32_t)g.mcus_x * (uint32_t)g.mcus_y, h.restart, cut) < 0) {
-        td_set_error("td_jpeg_decode: restart markers missing or out of sequence");
+        td_set_error("%s: restart markers missing or out of sequence", name);
         return TD_ERR_INVALID;
     }
     std::vector<int16_t> coef((size_t)g.total, 0);
     for (size_t i = 0; i < cut.size(); ++i)
-        if (mode == 4 ? jpeg_decode_segment<true>(T, g, src + cut[i].off, (uint32_t)cut[i].len, cut[i].mcu0, cut[i].nmcu, coef.data())
-                      : jpeg_decode_segment<false>(T, g, src + cut[i].off, (uint32_t)cut[i].len, cut[i].mcu0, cut[i].nmcu, coef.data())) {
-            td_set_error("td_jpeg_decode: corrupt entropy-coded data (segment %d)", (int)i);
+        if (mode == 4 ? decode_one_segment<true>(T, g, src, cut[i], coef.data(), subseq, lanes, stats)
+                      : decode_one_segment<false>(T, g, src, cut[i], coef.data(), subseq, lanes, stats)) {
+            td_set_error("%s: corrupt entropy-coded data (segment %d)", name, (int)i);
             return TD_ERR_INVALID;
         }
     std::vector<uint8_t> planes((size_t)g.total);
@@ -473,4 +487,21 @@ extern "C" int64_t td_jpeg_decode(const uint8_t* src, int64_t n, uint8_t* dst, i
             }
         }
     return need;
+}
+
+}  // namespace
+
+extern "C" int64_t td_jpeg_decode(const uint8_t* src, int64_t n, uint8_t* dst, int64_t cap, int32_t* shape) {
+    return decode_stream("td_jpeg_decode", src, n, dst, cap, shape, 0, 0, nullptr);
+}
+
+extern "C" int64_t td_jpeg_decode_sync(const uint8_t* src, int64_t n, uint8_t* dst, int64_t cap, int32_t* shape, int subseq_bytes, int lanes,
+                                       int64_t* stats) {
+    if (subseq_bytes < JPG_SYNC_MIN_SUBSEQ || subseq_bytes > JPG_SYNC_MAX_SUBSEQ || lanes < 1 || lanes > 64) {
+        td_set_error("td_jpeg_decode_sync: subsequences of %d bytes (%d .. %d), %d lanes (1 .. 64)", subseq_bytes, JPG_SYNC_MIN_SUBSEQ,
+                     JPG_SYNC_MAX_SUBSEQ, lanes);
+        return TD_ERR_INVALID;
+    }
+    if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
+    return decode_stream("td_jpeg_decode_sync", src, n, dst, cap, shape, subseq_bytes, lanes, stats);
 }

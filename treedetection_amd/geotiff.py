@@ -376,19 +376,21 @@ class GeoTiff:
         return out
 
     # -- compressed raster → HBM (tiffdecode.hip) --------------------------------------------------------------------------
-    def device_decodable(self, float_samples: bool = False) -> bool:
+    def device_decodable(self, float_samples: bool = False, long_segments: bool = False) -> bool:
         """True when the raster's blocks can be decoded on the GPU: LZW or DEFLATE (zlib) strips or tiles of pixel-interleaved
         uint8 or native-order (little-endian) uint16 samples (<= 4 per pixel), predictor 1 or 2; JPEG (compression 7) grey,
         three-band or four-band blocks when the host plan (td_tiff_jpeg_plan: sequential Huffman, 8-bit, 4:4:4 / 4:2:2 / 4:2:0, four
         components all 1x1 and stored as they are) accepts every one of them. ``float_samples=True`` (the height raster of the post-processing stage; the tile loop never asks) also admits
         native-order float32 samples in the same LZW / DEFLATE layouts, predictor 1, 2 or 3 (floating-point predictor). Everything
-        else keeps the host reader: big-endian and planar files, PackBits, int16 / int32 and float64 samples, 12-bit JPEG."""
+        else keeps the host reader: big-endian and planar files, PackBits, int16 / int32 and float64 samples, 12-bit JPEG — and JPEG
+        rasters with an entropy-coded segment beyond JPEG_DEVICE_MAX_SEGMENT (blocks without restart markers), unless
+        ``long_segments=True``: ``decode_to_device(long_segments=True)`` decodes such segments with a whole wave each."""
         self._setup_blocks()
         if self.compression == 7:
             if not (hasattr(self, "_jpeg_tables") and self._counts is not None and self._pil is None and self._flat is None):
                 return False
             plan = self._jpeg_plan()
-            return plan is not None and int(plan[1][:, 1].max()) <= self.JPEG_DEVICE_MAX_SEGMENT
+            return plan is not None and (long_segments or int(plan[1][:, 1].max()) <= self.JPEG_DEVICE_MAX_SEGMENT)
         f32 = float_samples and self.dtype.kind == "f" and self.dtype.itemsize == 4 and self.dtype.isnative
         return (self.compression in (5, 8, 32946) and self.planar == 1 and (self._device_samples() or f32) and 1 <= self.count <= 4
                 and self._predictor in ((1, 2, 3) if f32 else (1, 2)) and self._counts is not None and self._pil is None
@@ -401,6 +403,9 @@ class GeoTiff:
     # One lane decodes one entropy-coded segment at ~1.1 MB/s (a 4096² raster in ONE block without restart markers: 4.0 s on the
     # device against 85 ms for the host reader): rasters with a larger segment stay with the host reader
     JPEG_DEVICE_MAX_SEGMENT = 32 << 10
+    # ... unless the caller asks for the wave-per-segment decoder (``long_segments=True``), which cuts a longer segment into
+    # subsequences of this many bytes, one per lane (td_tiff_jpeg_decode_long_dev; measured in DESIGN.md §7)
+    JPEG_SYNC_SUBSEQ = 256
 
     def _jpeg_plan(self):
         """The JPEG raster's decode plan (td_tiff_jpeg_plan over the blocks as they lie in the file), or None when a block is not one
@@ -434,7 +439,8 @@ class GeoTiff:
         self._jpeg_plan_cache = plan
         return plan
 
-    def decode_to_device(self, device, stream=None, pinned=None, pool=None):
+    def decode_to_device(self, device, stream=None, pinned=None, pool=None, long_segments: bool = False, long_threshold: Optional[int] = None,
+                         subseq_bytes: Optional[int] = None):
         """The whole raster decoded in HBM: the compressed blocks are read as they lie in the file (one pread of the span that
         holds them, into pinned memory), copied to the device once, decoded one wave per block (td_tiff_lzw_decode_dev /
         td_tiff_inflate_verified_dev, which also checks every DEFLATE block's Adler-32 trailer as zlib does; JPEG: one lane per
@@ -444,10 +450,14 @@ class GeoTiff:
         or, DEFLATE, its bytes do not sum to the stream's checksum ("Adler-32 mismatch": the host reader's zlib raises on the same block) — the
         caller then falls back to the host reader. Everything is enqueued on ``stream`` (default: the current one). ``pinned``:
         a one-element list holding a pinned uint8 tensor to read the file into (grown and put back when too small — pinning
-        hundreds of MB per image costs as much as reading them); ``pool``: threads the file read is spread over."""
+        hundreds of MB per image costs as much as reading them); ``pool``: threads the file read is spread over.
+        ``long_segments`` (JPEG only): entropy-coded segments of more than ``long_threshold`` bytes (default JPEG_DEVICE_MAX_SEGMENT;
+        0: every segment) are decoded by one wave each, in subsequences of ``subseq_bytes`` (default JPEG_SYNC_SUBSEQ), the others one
+        per lane as ever (td_tiff_jpeg_decode_long_dev); ``check`` then carries ``.long_segments`` (how many took the wave) and
+        ``.sync_rounds`` (walk rounds per window of 64 subsequences, mean; 1.0 = every guess was right)."""
         import torch
         from . import _lib
-        if not self.device_decodable(float_samples=True):
+        if not self.device_decodable(float_samples=True, long_segments=long_segments):
             raise ValueError(f"{self.path}: not decodable on the device (compression {self.compression}, {self.dtype}, {self.count} bands)")
         lib = _lib.load()
         dev = torch.device(device)
@@ -494,7 +504,7 @@ class GeoTiff:
             comp = pin[:span + 16].to(dev, non_blocking=True)
             k0, k1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             if self.compression == 7:
-                return self._jpeg_to_device(dev, pin, comp, lo, span, k0, k1)
+                return self._jpeg_to_device(dev, pin, comp, lo, span, k0, k1, long_segments, long_threshold, subseq_bytes)
             meta = torch.from_numpy(np.stack([offs - lo, cnts])).to(dev, non_blocking=True)
             blocks = torch.empty((nb, block_cap), dtype=torch.uint8, device=dev)
             decoded = torch.empty((nb,), dtype=torch.int64, device=dev)
@@ -540,10 +550,11 @@ class GeoTiff:
         check.compressed_bytes = span
         return image, check
 
-    def _jpeg_to_device(self, dev, pin, comp, lo, span, k0, k1):
+    def _jpeg_to_device(self, dev, pin, comp, lo, span, k0, k1, long_segments=False, long_threshold=None, subseq_bytes=None):
         """decode_to_device for JPEG blocks (inside its device / stream context, the compressed bytes already on their way to ``comp``):
         the plan's arrays go to the device, td_tiff_jpeg_decode_dev decodes (entropy segments one per lane, IDCT, upsampling + colour)
-        straight into the raster. Same (image, check) contract; ``check()`` names the first block whose data is corrupt."""
+        straight into the raster. Same (image, check) contract; ``check()`` names the first block whose data is corrupt.
+        ``long_segments``: the plan's segments are split at ``long_threshold`` bytes and td_tiff_jpeg_decode_long_dev decodes both lists."""
         import torch
         from . import _lib
         lib = _lib.load()
@@ -559,23 +570,46 @@ class GeoTiff:
         status = torch.empty((nb,), dtype=torch.int32, device=dev)
         image = torch.empty((self.height, self.width, self.count), dtype=torch.uint8, device=dev)
         st = _lib.stream_ptr()
+        nlong, stats, stats_h = 0, None, None
+        if long_segments:
+            limit = self.JPEG_DEVICE_MAX_SEGMENT if long_threshold is None else int(long_threshold)
+            is_long = segs[:, 1] > limit
+            nlong = int(is_long.sum())
+            # (one upload: the short segments first, the long ones behind them, each list in the plan's order)
+            segs_d = torch.from_numpy(np.concatenate([segs[~is_long], segs[is_long]])).to(dev, non_blocking=True)
+            stats = torch.empty((4,), dtype=torch.int64, device=dev)
         k0.record()
-        _lib.check(lib.td_tiff_jpeg_decode_dev(comp.data_ptr(), info_d.data_ptr(), nb, segs_d.data_ptr(), len(segs), sets_d.data_ptr(),
-                                               coef.data_ptr(), planes.data_ptr(), ncoef, status.data_ptr(), image.data_ptr(), self.width,
-                                               self.height, self.count, self._bw, self._bh, self._nx, st), "td_tiff_jpeg_decode_dev")
+        if long_segments:
+            nshort = len(segs) - nlong
+            _lib.check(lib.td_tiff_jpeg_decode_long_dev(comp.data_ptr(), info_d.data_ptr(), nb, segs_d.data_ptr() if nshort else None, nshort,
+                                                        segs_d[nshort:].data_ptr() if nlong else None, nlong,
+                                                        int(subseq_bytes or self.JPEG_SYNC_SUBSEQ), sets_d.data_ptr(), coef.data_ptr(),
+                                                        planes.data_ptr(), ncoef, status.data_ptr(), stats.data_ptr(), image.data_ptr(),
+                                                        self.width, self.height, self.count, self._bw, self._bh, self._nx, st),
+                       "td_tiff_jpeg_decode_long_dev")
+        else:
+            _lib.check(lib.td_tiff_jpeg_decode_dev(comp.data_ptr(), info_d.data_ptr(), nb, segs_d.data_ptr(), len(segs), sets_d.data_ptr(),
+                                                   coef.data_ptr(), planes.data_ptr(), ncoef, status.data_ptr(), image.data_ptr(), self.width,
+                                                   self.height, self.count, self._bw, self._bh, self._nx, st), "td_tiff_jpeg_decode_dev")
         k1.record()
         done = torch.cuda.Event()
         done.record()
         st_h = torch.empty((nb,), dtype=torch.int32, pin_memory=True)
         st_h.copy_(status, non_blocking=True)
+        if stats is not None:
+            stats_h = torch.empty((4,), dtype=torch.int64, pin_memory=True)
+            stats_h.copy_(stats, non_blocking=True)
         copied = torch.cuda.Event(blocking=True)
         copied.record()
-        keep = [pin, comp, info_d, segs_d, sets_d, coef, planes, status]     # alive until check() has run: the kernels read them
+        keep = [pin, comp, info_d, segs_d, sets_d, coef, planes, status, stats]     # alive until check() has run: the kernels read them
 
         def check():
             copied.synchronize()
             check.kernel_ms = k0.elapsed_time(k1)          # entropy decode + IDCT + upsampling / colour
             keep.clear()
+            if stats_h is not None:                        # rounds, windows, most rounds of a window, windows of one round
+                check.sync_stats = [int(v) for v in stats_h]
+                check.sync_rounds = check.sync_stats[0] / max(1, check.sync_stats[1])
             bad = np.nonzero(st_h.numpy() != 0)[0]
             if bad.size:
                 b = int(bad[0])
@@ -584,6 +618,8 @@ class GeoTiff:
         check.event = done
         check.compressed_bytes = span
         check.segments = len(segs)
+        check.long_segments = nlong
+        check.sync_rounds = 0.0
         return image, check
 
     def device_uploadable(self) -> bool:
@@ -765,6 +801,17 @@ def device_decode_setting(value="auto"):
     if value not in (True, False, "auto", "true", "false", "all"):
         raise ValueError(f"device_decode must be true, false, 'auto' or 'all', got {value!r}")
     return value in (True, "auto", "true", "all"), value == "all"
+
+
+def device_decode_long_jpeg_setting(value=False) -> bool:
+    """The ``device_decode_long_jpeg`` config key as both stages read it: true / false (default) → whether JPEG rasters with segments
+    beyond GeoTiff.JPEG_DEVICE_MAX_SEGMENT go to the device too (``device_decodable(long_segments=True)``), where ``device_decode``
+    sends rasters there at all. Anything else is refused."""
+    if value is None:
+        value = False
+    if not any(value is v for v in (True, False)) and value not in ("true", "false"):
+        raise ValueError(f"device_decode_long_jpeg must be true or false, got {value!r}")
+    return value in (True, "true")
 
 
 class _NullCtx:

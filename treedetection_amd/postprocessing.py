@@ -29,7 +29,7 @@ import torch
 import yaml
 
 from . import _lib
-from .geotiff import GeoTiff, device_decode_setting
+from .geotiff import GeoTiff, device_decode_long_jpeg_setting, device_decode_setting
 from .gpkg import polygon_blob, read_layer, write_blobs
 from .stitching import simplify_ring
 
@@ -481,19 +481,26 @@ def _device_decode_on(config) -> bool:
     return value in (True, "true", "all")
 
 
+def _long_jpeg_on(config) -> bool:
+    """``device_decode_long_jpeg`` as the Predictor reads it: JPEG rasters with segments too long for one lane take the device path too."""
+    return device_decode_long_jpeg_setting(config.get("device_decode_long_jpeg", False))
+
+
 def _ndvi_on_device(rg: GeoTiff, n_scale: float, config, device: int):
     """The NDVI raster of the crown statistics computed in HBM: the RGBI raster decoded there (GeoTiff.decode_to_device), bands 0 and
     3 resampled to [int(rows * n_scale), int(cols * n_scale)] and turned into NDVI by one call of td_resample_gdal_dev (mode "ndvi";
     with ``n_scale`` 1 the same kernels run with identity taps) → float32 CUDA tensor for :func:`crown_stats`. None when the host
     reader has to serve it, by the gating of :func:`_height_on_device`: ``device_decode`` not explicitly true / "all", a raster that
-    is not uint8 with four bands in a layout the device decoders take (LZW / DEFLATE / JPEG, pixel-interleaved), or a corrupt block (printed)."""
+    is not uint8 with four bands in a layout the device decoders take (LZW / DEFLATE / JPEG, pixel-interleaved; JPEG blocks without
+    restart markers only with ``device_decode_long_jpeg: true``), or a corrupt block (printed)."""
     if not _device_decode_on(config):
         return None
     out_h, out_w = int(rg.height * n_scale), int(rg.width * n_scale)
-    if rg.dtype != np.uint8 or rg.count < 4 or out_h < 1 or out_w < 1 or not rg.device_decodable():
+    long_jpeg = _long_jpeg_on(config)
+    if rg.dtype != np.uint8 or rg.count < 4 or out_h < 1 or out_w < 1 or not rg.device_decodable(long_segments=long_jpeg):
         return None
     try:
-        _, check = rg.decode_to_device(torch.device("cuda", device))
+        _, check = rg.decode_to_device(torch.device("cuda", device), long_segments=long_jpeg)
         rgbi = check()
     except ValueError as e:
         print(f"device decode of {rg.path} failed ({e}): using the host reader")

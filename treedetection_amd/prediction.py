@@ -24,7 +24,7 @@ from . import _lib
 from . import distributed as D
 from .contours import batch_prediction_files, find_contours, tile_polygons_json, tile_polygons_json_dev, tile_prediction_file, xy
 from .engine import Engine, INPUT_F32_CHW, INPUT_U8_HWC
-from .geotiff import GeoTiff, device_decode_setting
+from .geotiff import GeoTiff, device_decode_long_jpeg_setting, device_decode_setting
 from .weights import load_checkpoint
 
 
@@ -187,7 +187,7 @@ class Predictor:
                  precision: str = "fp32", state_dict: Optional[Dict[str, np.ndarray]] = None,
                  return_predictions: bool = True, host_workers: Optional[int] = None, pipeline: bool = True,
                  device_contours: bool = False, sharded_epilogue: str = "rank0", schedule: str = "streams",
-                 device_decode="auto"):
+                 device_decode="auto", device_decode_long_jpeg=False):
         """cfg from ``setup_model_cfg``; ``device_type`` = GPU index ("0", 0) as config["device"] carries it.
         ``state_dict`` lets tests and the bench inject weights instead of reading cfg.MODEL.WEIGHTS.
         ``return_predictions=False`` skips rebuilding the Python list ``__call__`` returns (the reference's own caller
@@ -208,6 +208,9 @@ class Predictor:
         # per tile; on a 16-core host -20 % (the upload's reader threads compete with the epilogue workers, and an image that was not
         # prefetched waits for its whole raster before its first batch) — so the default keeps the per-window host reader for them
         self.device_decode, self.device_upload = device_decode_setting(device_decode)
+        # JPEG rasters with entropy-coded segments too long for one lane (blocks without restart markers) go to the device as well, a
+        # wave per segment (GeoTiff.decode_to_device(long_segments=True)); off by default (the measurements: DESIGN.md §7)
+        self.device_decode_long_jpeg = device_decode_long_jpeg_setting(device_decode_long_jpeg)
         self._rasters: Dict[str, "object"] = {}
         self._raster_pool = None
         self._decode_stream = None
@@ -393,7 +396,7 @@ class Predictor:
         img = None
         try:
             img = GeoTiff(tifpath)
-            decode = img.device_decodable()
+            decode = img.device_decodable(long_segments=self.device_decode_long_jpeg)
             if not decode and not (self.device_upload and img.device_uploadable()
                                    and img.height * img.width * img.count * img.dtype.itemsize <= self.device_raster_max_bytes):
                 return None
@@ -405,7 +408,8 @@ class Predictor:
             if self._upload_pool is None:
                 self._upload_pool = ThreadPoolExecutor(max_workers=max(1, min(8, host_core_share() // 4)), thread_name_prefix="td-upload")
             if decode:
-                image, check = img.decode_to_device(self.device, self._decode_stream, self._decode_pinned, self._upload_pool)
+                image, check = img.decode_to_device(self.device, self._decode_stream, self._decode_pinned, self._upload_pool,
+                                                    long_segments=self.device_decode_long_jpeg)
             else:
                 # an uncompressed raster: its bytes go to HBM in large sequential pieces (GeoTiff.upload_to_device), the windows
                 # are cut there — one memcpy per byte out of the page cache instead of a pread per window row + an H2D per batch
