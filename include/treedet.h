@@ -160,7 +160,7 @@ td_status td_engine_profile_read(td_engine* e, double* ms, int64_t* launches, do
 #define TD_CLS_FC 4          /* box head: fc1, fc2, predictors */
 #define TD_CLS_MASK_HEAD 5   /* mask-head contractions and transforms (rows = live detections, known on the device only) */
 #define TD_CLS_TAIL 6        /* fused bottleneck tail: 3x3 (mid -> mid) + 1x1 (mid -> 4 mid) + shortcut in one launch (res2; fp16: res3 too) */
-#define TD_PEAK_F32_MFMA_TFLOPS 157.3   /* v_mfma_f32_32x32x2_f32, dense */
+#define TD_PEAK_F32_MFMA_TFLOPS 157.3   /* v_mfma_f32_32x32x2_f32, dense (a split-bf16 launch enters the accounting with 6/16 of its FLOPs: its MFMA pipe time at this rate) */
 #define TD_PEAK_F16_MFMA_TFLOPS 2500.0  /* v_mfma_f32_32x32x16_f16, dense */
 #define TD_HBM_ACHIEVABLE_TBS 6.3       /* measured streaming rate (8.0 TB/s spec) */
 td_status td_engine_profile_classes(td_engine* e, double* ms, int64_t* launches, double* exec_flops, double* bytes, double* tmin_ms, int reset);
@@ -219,7 +219,10 @@ td_status td_bottleneck_tail_nhwc(const void* x, const void* w2, const float* sc
  * TD_CONV_CFG diagnostic) that cannot run this launch — an fp16-only tile on float32 tensors, a plane-contraction tile
  * (18-20) off a plain fp32 1x1 / stride-1 layer, the filter-stationary tile (33) where conv_bs_ok fails, a filter-direct
  * tile where conv_bd_ok fails — returns TD_ERR_INVALID with a message naming the id and the condition, instead of running
- * the heuristic tile in its place. */
+ * the heuristic tile in its place.
+ * Tile ids 34-36 (float32 tensors, 1x1 without padding, Cin a multiple of 32 only) contract on the bf16 matrix cores with both
+ * operands written as three bf16 pieces (six piece products per 16 k into the float32 accumulator, conv_split.hip): float32 in
+ * and out, another rounding than ids 0-33 (inside the same float64 bound), bit-identical to each other. */
 td_status td_conv2d_nhwc(const void* x, const void* w, const float* scale, const float* bias,
                          const void* residual, int res_shift, void* y, int B, int H, int W, int Cin,
                          int Cout, int KH, int KW, int stride, int pad, int relu, int precision,

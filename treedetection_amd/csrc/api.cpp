@@ -79,6 +79,29 @@ static td_status conv2d_api(ConvArgs& a, int precision, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     ConvArgs with_frag = a;
     with_frag.w_frag = a.w;          // stands in for the copy packed below: made only for a launch the tile can run
+    with_frag.w_split = a.w;
+    if (conv_tile(a.tile_cfg) && conv_tile(a.tile_cfg)->family == TILE_SPLIT && !conv_tile_refusal(a.tile_cfg, with_frag, precision & 0xff)) {
+        // tests: the split-bf16 tiles (conv_split.hip) need the three-piece filter bank: split here from the caller's fp32
+        // [Cout][Cin] bank (the engine splits once at load time)
+        const size_t n = (size_t)a.Cout * a.Cin;
+        std::vector<float> wh(n);
+        std::vector<unsigned char> packed;
+        TD_HIP_CHECK(hipStreamSynchronize(s));
+        TD_HIP_CHECK(hipMemcpy(wh.data(), a.w, n * sizeof(float), hipMemcpyDeviceToHost));
+        conv_split_pack(wh.data(), a.Cout, a.Cin, packed);
+        void* ws = nullptr;
+        td_status st = scratch(&ws, packed.size());
+        if (st < 0) return st;
+        hipError_t herr = hipMemcpy(ws, packed.data(), packed.size(), hipMemcpyHostToDevice);
+        a.w_split = ws;
+        if (herr == hipSuccess) st = conv2d_launch(a, precision & 0xff, s);
+        hipError_t herr2 = hipStreamSynchronize(s);
+        (void)hipFree(ws);
+        if (st < 0) return st;
+        TD_HIP_CHECK(herr);
+        TD_HIP_CHECK(herr2);
+        return TD_OK;
+    }
     if (!conv_tile(a.tile_cfg) || !conv_tile(a.tile_cfg)->frag || conv_tile_refusal(a.tile_cfg, with_frag, precision & 0xff))
         return conv2d_launch(a, precision & 0xff, s);
     // tests: the filter-direct tiles (conv_bdirect.hip) need the filters in fragment order: packed here from the caller's

@@ -61,6 +61,7 @@ struct ConvArgs {
     int batch_count;
     long long x_bs, w_bs, y_bs;
     const void* w_frag;   // the same filters in MFMA fragment order (the tiles with ConvTile::frag), or nullptr
+    const void* w_split;  // fp32 1x1 / FC filters as three bf16 pieces per weight in fragment order (conv_split_pack; the TILE_SPLIT ids), or nullptr
     int tile_cfg;         // -1 = heuristic; else an id of TD_CONV_TILES (engine autotunes)
     int tile_strict;      // 1: a forced tile_cfg this launch cannot run is an error, not a silent switch to the heuristic tile (tests)
     // fused 1x1 head (fp16 engine, block tiles that own all 256 output channels: ConvTile::head): the finished fp16
@@ -88,8 +89,10 @@ struct ConvArgs {
 // id keeps its number and a retired one keeps its row. Adding a tile: a row here and a case in its family's launcher.
 // Families: conv_igemm_kernel (conv_igemm.hip:dispatch); conv_pp8_kernel (8 waves, ping-pong phases, DMA 1.5 k-chunks ahead);
 // plane_gemm_kernel (persistent walk over the fp32 Winograd planes); conv_bd_kernel (conv_bdirect.hip: filter fragments from the
-// fragment-ordered copy straight into registers); conv_bs_kernel (conv_bstat.hip: filter-stationary 1x1, one block per CU).
-enum ConvFamily : unsigned char { TILE_IGEMM, TILE_PP8, TILE_PLANE, TILE_BD, TILE_BS, TILE_RETIRED };
+// fragment-ordered copy straight into registers); conv_bs_kernel (conv_bstat.hip: filter-stationary 1x1, one block per CU);
+// conv_split_kernel (conv_split.hip: fp32 1x1 / FC on the bf16 matrix cores, operands as three bf16 pieces — its own rounding: a
+// launch runs these ids if and only if it carries ConvArgs::w_split, which the engine sets by a fixed rule on the layer).
+enum ConvFamily : unsigned char { TILE_IGEMM, TILE_PP8, TILE_PLANE, TILE_BD, TILE_BS, TILE_RETIRED, TILE_SPLIT };
 enum : unsigned char { TILE_F32 = 1 << TD_PRECISION_FP32, TILE_F16 = 1 << TD_PRECISION_FP16, TILE_ANY = TILE_F32 | TILE_F16 };
 struct ConvTile {
     ConvFamily family;
@@ -142,6 +145,9 @@ inline constexpr ConvTile TD_CONV_TILES[] = {
     {TILE_IGEMM,   0, TILE_ANY, false, false, 15, 0,   0, 32},     // 31: 256x32, 4 x 1 waves (the thin heads)
     {TILE_IGEMM,   0, TILE_ANY, false, false, 17, 0,   0, 32},     // 32: 128x32
     {TILE_BS,      0, TILE_ANY, false, true,   0, 4, 128,  0},     // 33: conv_bs_kernel (its other tuning rules: conv_bs_ok)
+    {TILE_SPLIT,   0, TILE_F32, false, false, 21, 0,   0,  0},     // 34: conv_split_kernel 128x256 (ranks 21 - 23: timed for launches with w_split only,
+    {TILE_SPLIT,   1, TILE_F32, false, false, 22, 0,   0,  0},     // 35: 128x128               and then nothing else is — tuned_cfg filters by family)
+    {TILE_SPLIT,   2, TILE_F32, false, false, 23, 0,   0,  0},     // 36: 64x256
 };
 static inline const ConvTile* conv_tile(int id) { return id >= 0 && id < (int)(sizeof TD_CONV_TILES / sizeof *TD_CONV_TILES) ? &TD_CONV_TILES[id] : nullptr; }
 static inline bool conv_head_capable(int id, int precision) { return precision == TD_PRECISION_FP16 && conv_tile(id) && conv_tile(id)->head; }
@@ -159,6 +165,10 @@ td_status conv_bd_launch(const ConvArgs& a, int precision, int variant, hipStrea
 // filter-stationary form (conv_bstat.hip, tile id 33)
 bool conv_bs_ok(const ConvArgs& a, int precision);
 td_status conv_bs_launch(const ConvArgs& a, int precision, hipStream_t stream);
+// split-bf16 form (conv_split.hip, tile ids 34 - 36): w [cout][cin] fp32 → the three-piece fragment bank (6 bytes per weight)
+void conv_split_pack(const float* w, int cout, int cin, std::vector<unsigned char>& out);
+bool conv_split_ok(const ConvArgs& a, int precision);
+td_status conv_split_launch(const ConvArgs& a, int variant, hipStream_t stream);
 td_status wino_gemm_launch(const ConvArgs& a, hipStream_t stream);     // Winograd plane contractions, input transform fused (fp32)
 
 // ---- fused bottleneck tail (bottleneck.hip): 3x3 (mid -> mid) + BN + ReLU, then 1x1 (mid -> 4 mid) + BN + shortcut + ReLU ----

@@ -1089,6 +1089,8 @@ const char* conv_tile_refusal(int id, const ConvArgs& a, int precision) {
     if (t->family == TILE_BS && !conv_bs_ok(a, precision))
         return "conv_bs_ok failed (1x1, stride 1, 1 / 2 / 4 k-chunks, 128 <= Cout <= 2048, Cout % 8 == 0, packed filters)";
     if (t->family == TILE_BD && !conv_bd_ok(a, precision)) return "conv_bd_ok failed (packed filters, plain output)";
+    if (t->family == TILE_SPLIT && !conv_split_ok(a, precision))
+        return "conv_split_ok failed (fp32 1x1 without padding, plain output, Cin a multiple of 32, split filter bank)";
     return nullptr;
 }
 
@@ -1129,6 +1131,7 @@ td_status conv2d_launch(const ConvArgs& a, int precision, hipStream_t stream) {
     const ConvTile& t = *conv_tile(cfg);
     if (t.family == TILE_BS) return conv_bs_launch(a, precision, stream);
     if (t.family == TILE_BD) return conv_bd_launch(a, precision, t.variant, stream);
+    if (t.family == TILE_SPLIT) return conv_split_launch(a, t.variant, stream);
     TD_REQUIRE(a.batch_count <= 1 || (a.KH == 1 && a.KW == 1 && !a.res), "conv2d: batched launches are 1x1 contractions");
     if (t.family == TILE_PP8) return a.out_f32 ? pp8_launch<float>(a, stream) : pp8_launch<_Float16>(a, stream);
     if (t.family == TILE_PLANE) return plane_launch(a, cfg, stream);

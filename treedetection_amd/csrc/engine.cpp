@@ -32,6 +32,8 @@ struct HostTensor {
     }
 };
 
+enum { SPLIT_FC = 1, SPLIT_LATERAL = 2, SPLIT_CONV1 = 4, SPLIT_CONV3 = 8, SPLIT_SHORTCUT = 16, SPLIT_DEFAULT = SPLIT_FC };
+
 struct ConvLayer {
     int cout = 0, cin = 0, kh = 1, kw = 1;
     void* w = nullptr;        // [cout][kh][kw][cin], float32 or float16 (engine precision)
@@ -39,6 +41,8 @@ struct ConvLayer {
     float* bias = nullptr;    // [cout] or null
     bool out_f32 = false;     // fp16 engine: this layer still writes float32 (feeds the fp32 selection kernels)
     void* w_frag = nullptr;   // fp16 engine: the filters in MFMA fragment order (conv_bdirect.hip), layers with cin % 64 == 0
+    void* w_split = nullptr;  // fp32 engine, the layers of the split rule (td_engine::f32_split): three bf16 pieces per weight in fragment
+                              // order (conv_split.hip); a layer that has it runs the TILE_SPLIT ids and nothing else
     float* wino_u = nullptr;  // fp32 engine, 3x3 layers: Winograd-transformed filters U [16][cout][cin] (winograd.hip)
     float* wino_u43 = nullptr;  // the same for F(4x4,3x3): U [36][cout][cin] (layers with >= 128 channels on both sides)
 };
@@ -140,6 +144,14 @@ struct td_engine {
     // stream schedule but 574 → 545 one forward at a time (88-block launches on 256 CUs), not taken.
     // 32 = the RPN conv on the 160 x 160+ maps folds too (its head becomes a launch of its own).
     int wino_fold = 39;
+    // fp32 engine: the 1x1 / FC layers that run on the bf16 matrix cores with both operands as three bf16 pieces (conv_split.hip:
+    // its own rounding, so a FIXED rule on the layer — its place in the network and K >= 256 —, never a timing). Bit mask of layer
+    // classes (TD_F32_SPLIT; 0 = none, for an A/B on one build): SPLIT_FC the box head's fc1 / fc2, SPLIT_LATERAL the four FPN
+    // laterals, SPLIT_CONV1 / SPLIT_CONV3 / SPLIT_SHORTCUT the 1x1 layers of res3 - res5. Never: layers that also exist inside a
+    // fused kernel or have a bit-identity twin (res2, the RPN head, the box and mask predictors), K < 256, the fp16 engine.
+    // The default is the box head, the class whose gain on the headline was measured; the others are faster in the per-layer table
+    // (profiles/f32_split.txt) but have no headline measurement yet.
+    int f32_split = SPLIT_DEFAULT;
     std::string tune_cache;       // TD_TUNE_CACHE: load / append measured choices (keeps profiled runs free of tuning launches)
     // The tuner times every candidate tile with the L2 (8 x 4 MB) emptied before each launch (a fill of this scratch on the same
     // stream): in the forward a layer's filters and most of its input are NOT in L2 — 50-odd other launches ran since — and a loop of
@@ -242,6 +254,20 @@ td_status upload_frag(td_engine* e, const std::vector<float>& h, ConvLayer& L) {
     return st;
 }
 
+// the split-bf16 bank of a layer of class `cls` (SPLIT_*) when the rule takes that class: fp32 engine, 1x1, K >= 256
+td_status upload_split(td_engine* e, const std::vector<float>& h, ConvLayer& L, int cls) {
+    L.w_split = nullptr;
+    if (e->desc.precision != TD_PRECISION_FP32 || !(e->f32_split & cls) || L.kh != 1 || L.kw != 1 || L.cin < 256 || L.cin % 32 != 0 ||
+        (size_t)L.cout * L.cin != h.size())
+        return TD_OK;
+    std::vector<unsigned char> packed;
+    conv_split_pack(h.data(), L.cout, L.cin, packed);
+    unsigned char* d = nullptr;
+    td_status st = upload(e, packed, &d);
+    L.w_split = d;
+    return st;
+}
+
 using TensorMap = std::map<std::string, HostTensor>;
 
 td_status need(const TensorMap& tm, const std::string& name, int ndim, const HostTensor** out) {
@@ -317,7 +343,7 @@ td_status upload_wino(td_engine* e, const std::vector<float>& w_ohwi, ConvLayer&
     return upload(e, u43, &L.wino_u43);
 }
 
-td_status load_conv_bn(td_engine* e, const TensorMap& tm, const std::string& p, ConvLayer& L) {
+td_status load_conv_bn(td_engine* e, const TensorMap& tm, const std::string& p, ConvLayer& L, int split_cls = 0) {
     const HostTensor* w;
     td_status st = need(tm, p + ".weight", 4, &w);
     if (st < 0) return st;
@@ -328,6 +354,7 @@ td_status load_conv_bn(td_engine* e, const TensorMap& tm, const std::string& p, 
     const std::vector<float> packed = pack_ohwi(*w);
     if ((st = upload_w(e, packed, &L.w)) < 0) return st;
     if ((st = upload_frag(e, packed, L)) < 0) return st;
+    if ((st = upload_split(e, packed, L, split_cls)) < 0) return st;
     if ((st = upload_wino(e, packed, L)) < 0) return st;
     std::vector<float> s, b;
     if ((st = bn_fold(tm, p, L.cout, s, b)) < 0) return st;
@@ -335,7 +362,7 @@ td_status load_conv_bn(td_engine* e, const TensorMap& tm, const std::string& p, 
     return upload(e, b, &L.bias);
 }
 
-td_status load_conv_bias(td_engine* e, const TensorMap& tm, const std::string& p, ConvLayer& L) {
+td_status load_conv_bias(td_engine* e, const TensorMap& tm, const std::string& p, ConvLayer& L, int split_cls = 0) {
     const HostTensor *w, *b;
     td_status st = need(tm, p + ".weight", 4, &w);
     if (st < 0) return st;
@@ -351,6 +378,7 @@ td_status load_conv_bias(td_engine* e, const TensorMap& tm, const std::string& p
     const std::vector<float> packed = pack_ohwi(*w);
     if ((st = upload_w(e, packed, &L.w)) < 0) return st;
     if ((st = upload_frag(e, packed, L)) < 0) return st;
+    if ((st = upload_split(e, packed, L, split_cls)) < 0) return st;
     if ((st = upload_wino(e, packed, L)) < 0) return st;
     L.scale = nullptr;
     return upload(e, std::vector<float>(b->data, b->data + L.cout), &L.bias);
@@ -480,6 +508,7 @@ td_status td_engine_create(const td_model_desc* desc, int device, td_engine** ou
     if (const char* w4 = getenv("TD_WINO43_MIN")) e->wino43_min = atoi(w4);
     if (const char* wf2 = getenv("TD_WINO_FOLD")) e->wino_fold = atoi(wf2);
     if (const char* wc = getenv("TD_WINO_MINC")) e->wino_minc = atoi(wc);
+    if (const char* sp = getenv("TD_F32_SPLIT")) e->f32_split = atoi(sp);
     e->desc = d;
     load_tune_cache(e);
     e->device = device;
@@ -552,11 +581,12 @@ td_status td_engine_load_weights(td_engine* e, const td_tensor_desc* tensors, si
             if (tm.find(p + ".conv1.weight") == tm.end()) break;
             Block blk;
             blk.stride = (bi == 0 && si > 0) ? 2 : 1;
-            if ((st = load_conv_bn(e, tm, p + ".conv1", blk.c1)) < 0) return st;
+            // (the split rule: res3 - res5 only — conv2 / conv3 of res2 also exist inside bottleneck_tail_kernel)
+            if ((st = load_conv_bn(e, tm, p + ".conv1", blk.c1, si > 0 ? SPLIT_CONV1 : 0)) < 0) return st;
             if ((st = load_conv_bn(e, tm, p + ".conv2", blk.c2)) < 0) return st;
-            if ((st = load_conv_bn(e, tm, p + ".conv3", blk.c3)) < 0) return st;
+            if ((st = load_conv_bn(e, tm, p + ".conv3", blk.c3, si > 0 ? SPLIT_CONV3 : 0)) < 0) return st;
             blk.has_sc = tm.find(p + ".shortcut.weight") != tm.end();
-            if (blk.has_sc && (st = load_conv_bn(e, tm, p + ".shortcut", blk.sc)) < 0) return st;
+            if (blk.has_sc && (st = load_conv_bn(e, tm, p + ".shortcut", blk.sc, si > 0 ? SPLIT_SHORTCUT : 0)) < 0) return st;
             e->stages[si].push_back(blk);
         }
         if (e->stages[si].empty()) {
@@ -565,7 +595,7 @@ td_status td_engine_load_weights(td_engine* e, const td_tensor_desc* tensors, si
         }
     }
     for (int l = 0; l < 4; ++l) {
-        if ((st = load_conv_bias(e, tm, "backbone.fpn_lateral" + std::to_string(l + 2), e->lateral[l])) < 0) return st;
+        if ((st = load_conv_bias(e, tm, "backbone.fpn_lateral" + std::to_string(l + 2), e->lateral[l], SPLIT_LATERAL)) < 0) return st;
         if ((st = load_conv_bias(e, tm, "backbone.fpn_output" + std::to_string(l + 2), e->fpn_out[l])) < 0) return st;
     }
     e->fpn_c = e->lateral[0].cout;
@@ -609,6 +639,7 @@ td_status td_engine_load_weights(td_engine* e, const td_tensor_desc* tensors, si
         e->fc_dim = o;
         if ((st = upload_w(e, p, &e->fc1.w)) < 0) return st;
         if ((st = upload_frag(e, p, e->fc1)) < 0) return st;
+        if ((st = upload_split(e, p, e->fc1, SPLIT_FC)) < 0) return st;
         if ((st = upload(e, std::vector<float>(b->data, b->data + o), &e->fc1.bias)) < 0) return st;
     }
     {
@@ -619,6 +650,7 @@ td_status td_engine_load_weights(td_engine* e, const td_tensor_desc* tensors, si
         const std::vector<float> w2v(w->data, w->data + w->numel());
         if ((st = upload_w(e, w2v, &e->fc2.w)) < 0) return st;
         if ((st = upload_frag(e, w2v, e->fc2)) < 0) return st;
+        if ((st = upload_split(e, w2v, e->fc2, SPLIT_FC)) < 0) return st;
         if ((st = upload(e, std::vector<float>(b->data, b->data + e->fc2.cout), &e->fc2.bias)) < 0) return st;
     }
     {
@@ -833,7 +865,9 @@ td_status tuned_cfg(td_engine* e, const std::tuple<int, int, int, int, int>& key
     const int ksteps = a.KH * a.KW * a.Cin / (prec == TD_PRECISION_FP16 ? 64 : 32);
     auto candidate = [&](int id) {
         const ConvTile* t = conv_tile(id);
-        return t && (!t->max_ksteps || ksteps <= t->max_ksteps) && a.Cout >= t->min_cout && (!t->max_cout || a.Cout <= t->max_cout) &&
+        // a launch with the split bank is one of the split rule's layers: it times the TILE_SPLIT ids and nothing else, every other
+        // launch never times one (conv_tile_refusal: no bank) — which rounding a layer gets is the rule's decision, not a timing's
+        return t && (t->family == TILE_SPLIT) == (a.w_split != nullptr) && (!t->max_ksteps || ksteps <= t->max_ksteps) && a.Cout >= t->min_cout && (!t->max_cout || a.Cout <= t->max_cout) &&
                !conv_tile_refusal(id, a, prec);
     };
     static const int forced = getenv("TD_FORCE_CFG") ? atoi(getenv("TD_FORCE_CFG")) : -1;      // diagnostics: one block tile everywhere it applies
@@ -1013,18 +1047,22 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
         const double M = (double)B_ * Ho * Wo, K = (double)L.kh * L.kw * L.cin;
         const double flops = 2.0 * M * L.cout * K;
         const double es = prec_ == TD_PRECISION_FP16 ? 2.0 : 4.0;
-        const double bytes = es * ((double)B_ * H_ * W_ * L.cin / (stride * stride) + M * L.cout * (res_ ? 2.0 : 1.0) + L.cout * K);
-        int cfg = -1, wino_cfg = -1;
+        // the split rule's layers (ConvLayer::w_split; the engine's own precision only, plain output, static rows)
+        const bool split = L.w_split && prec_ == TD_PRECISION_FP32 && out_mode == 0 && !m_dyn && !head && pad == 0;
+        // (their filters cross as three bf16 pieces: 6 bytes per weight)
+        const double bytes = es * ((double)B_ * H_ * W_ * L.cin / (stride * stride) + M * L.cout * (res_ ? 2.0 : 1.0)) + (split ? 6.0 : es) * L.cout * K;
+        int cfg = split ? 34 : -1, wino_cfg = -1;      // (34: the split family's tile without the tuner)
         bool use_wino = false, use_43 = false, use_fold = false;
         td_status st2;
         ConvArgs ca{};          // the direct launch (tuned tile, fused head below)
-        ca.x = x_; ca.w = L.w; ca.w_frag = L.w_frag; ca.scale = L.scale; ca.bias = L.bias; ca.res = res_; ca.y = y_;
+        ca.x = x_; ca.w = L.w; ca.w_frag = L.w_frag; ca.w_split = split ? L.w_split : nullptr; ca.scale = L.scale; ca.bias = L.bias; ca.res = res_; ca.y = y_;
         ca.B = B_; ca.H = H_; ca.W = W_; ca.Cin = L.cin; ca.Cout = L.cout; ca.KH = L.kh; ca.KW = L.kw;
         ca.stride = stride; ca.pad = pad; ca.Ho = Ho; ca.Wo = Wo;
         ca.res_shift = res_shift; ca.relu = relu ? 1 : 0; ca.out_mode = out_mode;
         ca.M = B_ * Ho * Wo; ca.m_dyn = m_dyn; ca.m_mul = m_mul; ca.tile_cfg = -1; ca.out_f32 = L.out_f32 ? 1 : 0;
         if (e->autotune) {
-            const auto key = std::make_tuple(L.cout, L.cin, L.kh * 16 + L.kw, B_ * Ho * Wo, stride * 4 + out_mode * 2 + (res_ ? 1 : 0));
+            // (flag 128: a split layer — tune-cache lines written for its fp32 tiles do not apply)
+            const auto key = std::make_tuple(L.cout, L.cin, L.kh * 16 + L.kw, B_ * Ho * Wo, stride * 4 + out_mode * 2 + (res_ ? 1 : 0) + (split ? 128 : 0));
             auto direct = [&](int c) { ConvArgs a = ca; a.tile_cfg = c; return conv2d_launch(a, prec_, s_); };
             const bool wino_ok = prec_ == TD_PRECISION_FP32 && L.wino_u && e->wino_v && stride == 1 && pad == 1 && !res_ && out_mode == 0 &&
                                  (!m_dyn || ((H_ | W_) & 1) == 0) &&
@@ -1070,7 +1108,8 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
         ProfScope ps(e, s_, m_dyn ? 7 : 0, m_dyn ? 0.0 : flops, m_dyn ? 0.0 : bytes);
         if (e->prof && !m_dyn) {          // category 8: FLOPs the MFMA pipe really executes
             const double padded = use_43 ? (double)(((H_ + 3) / 4) * 4) * (((W_ + 3) / 4) * 4) / ((double)H_ * W_) : 1.0;
-            e->prof_flops[8] += use_43 ? flops * padded * 0.25 : (use_wino ? flops * 4.0 / 9.0 : flops);
+            // (a split launch: six bf16 MFMAs, 192 pipe cycles, per 16 k against 512 for the fp32 MFMAs — its pipe time in units of the fp32 rate)
+            e->prof_flops[8] += use_43 ? flops * padded * 0.25 : (use_wino ? flops * 4.0 / 9.0 : (split ? flops * 6.0 / 16.0 : flops));
             e->prof_launches[8] += use_wino ? 1 : 0;
         }
         if (use_43) {
@@ -1104,7 +1143,7 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
             ClassScope cs(e, s_, cls, flops + hflops, bytes_f);
             return conv2d_launch(ca, prec_, s_);
         }
-        ClassScope cs(e, s_, cls, m_dyn ? 0.0 : flops, m_dyn ? 0.0 : bytes);
+        ClassScope cs(e, s_, cls, m_dyn ? 0.0 : (split ? flops * 6.0 / 16.0 : flops), m_dyn ? 0.0 : bytes);
         return conv2d_launch(ca, prec_, s_);
     };
     // The same 3x3 layer shape on several pyramid levels as ONE launch (conv_pp8_grouped_launch, fp16 engine): the FPN's output
