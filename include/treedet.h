@@ -108,7 +108,8 @@ td_status td_engine_forward(td_engine* e, const void* images, int input_format, 
  * predictor / paste read the mask buffers and row count that phases 3-4 rewrite), so any stream assignment is correct.
  * Optional pre-phase TD_PHASE_STEM (6): stem convolution + max-pool of the NEXT batch (VALU / HBM work, no matrix
  * cores) with the arguments of phase 0; the following phase 0 (images may be NULL) then starts at res2. Run it on a side
- * stream while the previous batch's contractions hold the main stream. */
+ * stream while the previous batch's contractions hold the main stream. "stem" and "pool" of td_engine_tensor are
+ * available after it. */
 #define TD_PHASE_STEM 6
 td_status td_engine_forward_phase(td_engine* e, int phase, const void* images, int input_format, const int32_t* hw_valid,
                                   const int32_t* hw_out, int B, int Hp, int Wp, void* stream, td_detections* out);

@@ -277,3 +277,87 @@ def test_paste_masks_batch_equals_per_image_paste():
     with pytest.raises(_lib.TdError, match="mask words"):
         _lib.check(lib.td_paste_masks_batch(d_probs.data_ptr(), d_boxes.data_ptr(), d_counts.data_ptr(), hw_bad, B, Dn, 0.5,
                                             region.data_ptr(), offset.data_ptr(), bits.data_ptr(), words, _lib.stream_ptr()), "x")
+
+
+def test_resize_tile_wide_filter_pillow_exact():
+    """1700 -> 800: scale 2.125, so the filter has ksize = 7 taps — the generic three-band branch of resize_h_u8 (the dword
+    fast path stops at ksize 5) and seven rows per output in resize_v_u8."""
+    lib = _lib.load()
+    h = w = 1700
+    rng = np.random.default_rng(1700)
+    img = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+    oh, ow = R.resize_shortest_edge_shape(h, w)
+    assert (oh, ow) == (800, 800) and R.pil_bilinear_coeffs(w, ow)[2] == 7
+    ref = R.pil_resize_bilinear_u8(np.ascontiguousarray(img[:, :, ::-1]), oh, ow)
+    src = dev(img)
+    dst = torch.zeros((oh, ow, 3), dtype=torch.uint8, device="cuda")
+    tmp = torch.empty((h * ow * 3,), dtype=torch.uint8, device="cuda")
+    _lib.check(lib.td_resize_tile_u8(src.data_ptr(), h, w, 3, dst.data_ptr(), oh, ow, ow, tmp.data_ptr(), _lib.stream_ptr()),
+               "td_resize_tile_u8")
+    torch.cuda.synchronize()
+    assert np.array_equal(dst.cpu().numpy(), ref)
+
+
+def resize_batch_hip(tiles, offsets, gap, pitch, stride_extra, fill=0xA5):
+    """td_resize_batch_u8 on equal-sized uint8 tiles [h, w, 3] placed `gap` bytes apart plus `offsets[i]` inside ONE device
+    allocation, into a destination filled with `fill` whose rows are `pitch` pixels and whose images lie `stride_extra`
+    bytes further apart than one image → (the whole destination as bytes, image stride, out_h, out_w)."""
+    import ctypes as C
+    lib = _lib.load()
+    n = len(tiles)
+    h, w, c = tiles[0].shape
+    assert c == 3 and all(t.shape == tiles[0].shape for t in tiles)
+    oh, ow = R.resize_shortest_edge_shape(h, w)
+    assert pitch >= ow
+    tile_bytes = h * w * 3
+    slot = tile_bytes + gap
+    arena = torch.zeros((n * slot + 16,), dtype=torch.uint8, device="cuda")
+    assert arena.data_ptr() % 4 == 0
+    ptrs = []
+    for i, t in enumerate(tiles):
+        at = i * slot + offsets[i]
+        arena[at:at + tile_bytes] = torch.from_numpy(np.ascontiguousarray(t).reshape(-1)).cuda()
+        ptrs.append(arena.data_ptr() + at)
+    stride = oh * pitch * 3 + stride_extra
+    dst = torch.full((n * stride,), fill, dtype=torch.uint8, device="cuda")
+    tmp = torch.empty((n * h * ow * 3,), dtype=torch.uint8, device="cuda")
+    _lib.check(lib.td_resize_batch_u8((C.c_void_p * n)(*ptrs), n, h, w, 3, dst.data_ptr(), oh, ow, pitch, stride, tmp.data_ptr(),
+                                      _lib.stream_ptr()), "td_resize_batch_u8")
+    torch.cuda.synchronize()
+    return dst.cpu().numpy(), [p % 4 for p in ptrs], stride, oh, ow
+
+
+def check_resize_batch(tiles, out, stride, oh, ow, pitch, fill=0xA5):
+    """Every image byte-exact against Pillow's bilinear filter on the BGR tile; the pitch padding of every row and the
+    bytes between two images still hold the fill value."""
+    for i, t in enumerate(tiles):
+        img = out[i * stride:i * stride + oh * pitch * 3].reshape(oh, pitch, 3)
+        ref = R.pil_resize_bilinear_u8(np.ascontiguousarray(t[:, :, ::-1]), oh, ow)
+        assert np.array_equal(img[:, :ow], ref), f"image {i}: {(img[:, :ow] != ref).sum()} bytes differ"
+        assert (img[:, ow:] == fill).all(), f"image {i}: pitch padding written"
+        assert (out[i * stride + oh * pitch * 3:(i + 1) * stride] == fill).all(), f"bytes behind image {i} written"
+
+
+def test_resize_batch_unaligned_tiles_pillow_exact():
+    """td_resize_batch_u8 (the Predictor's entry point), n = 3 tiles of 450 x 450 x 3 whose device pointers sit at byte
+    offsets 0, 1 and 2 modulo 4: the dword fast path of resize_h_u8 must stand down for the two unaligned sources (and runs
+    for the aligned one in the same launch). The destination's images lie an odd number of bytes apart, further than one
+    image, with padded rows."""
+    rng = np.random.default_rng(450)
+    tiles = [rng.integers(0, 256, (450, 450, 3), dtype=np.uint8) for _ in range(3)]
+    pitch = 832
+    out, align, stride, oh, ow = resize_batch_hip(tiles, offsets=(0, 1, 2), gap=16, pitch=pitch, stride_extra=4099)
+    assert align == [0, 1, 2] and (oh, ow) == (800, 800) and stride > oh * pitch * 3
+    check_resize_batch(tiles, out, stride, oh, ow, pitch)
+
+
+def test_resize_batch_fast_path_pillow_exact():
+    """n = 2 tiles of 1000 x 1000 x 3 -> 800: ksize 5 on aligned sources, the dword fast path of both passes, in the
+    batched form (blockIdx.z = tile; images a multiple of four bytes apart, further than one image)."""
+    rng = np.random.default_rng(1000)
+    tiles = [rng.integers(0, 256, (1000, 1000, 3), dtype=np.uint8) for _ in range(2)]
+    assert R.pil_bilinear_coeffs(1000, 800)[2] == 5
+    pitch = 832
+    out, align, stride, oh, ow = resize_batch_hip(tiles, offsets=(0, 0), gap=0, pitch=pitch, stride_extra=4096)
+    assert align == [0, 0] and (oh, ow) == (800, 800) and stride % 4 == 0
+    check_resize_batch(tiles, out, stride, oh, ow, pitch)

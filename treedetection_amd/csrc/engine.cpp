@@ -1277,9 +1277,11 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
             }
         }
     }
+    if (PH(0) || PH(6)) {      // the stem pre-phase publishes its two tensors too (a stage test may stop after it)
+        set_named(e, "stem", e->stem_out, B, Hp / 2, Wp / 2, e->stem_c, (int)esz);
+        set_named(e, "pool", e->pool_out, B, Hp / 4, Wp / 4, e->stem_c, (int)esz);
+    }
     if (PH(0)) {
-    set_named(e, "stem", e->stem_out, B, Hp / 2, Wp / 2, e->stem_c, (int)esz);
-    set_named(e, "pool", e->pool_out, B, Hp / 4, Wp / 4, e->stem_c, (int)esz);
     for (int si = 0; si < 4; ++si) {
         const std::string nm = "res" + std::to_string(si + 2);
         set_named(e, nm.c_str(), e->res[si], B, hs[si], wsz[si], e->stages[si][0].c3.cout, (int)esz);
