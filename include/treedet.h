@@ -583,6 +583,29 @@ td_status td_crown_pairs_fill(const float* boxes, const uint16_t* areas_f16, int
 int td_crown_pairs_greedy(const int64_t* row_start, const int32_t* cols, const uint16_t* conf_f16, const uint8_t* self_connected,
                           int n, uint8_t* removed);
 
+/* ---- polygon IoU of crown pairs (clean_crowns: reference helpers.py:602-701, utilities.calc_iou 209-212) ----
+ * For every pair (pairs int32 [n_pairs][2]: a ring index into set A, one into set B) the area of the intersection of the two
+ * simple rings and the two ring areas: out float64 [n_pairs][3] = inter, |area_A|, |area_B|; status int32 [n_pairs]. Rings arrive
+ * open (without the repeated closing vertex), concatenated: xy = (x, y) pairs, start int64 [n + 1] with ring r in
+ * [start[r], start[r + 1]) — non-decreasing from >= 0 and inside xy: the CALLER's guarantee. Exterior rings only, either winding.
+ * Arithmetic (csrc/ring_clip.h, float64, every operation rounded on its own, IEEE division): the fan decomposition about
+ * O = the centre of the intersection of the two rings' float64 bounding boxes — inter = sigma_A sigma_B sum_i sum_j sgn(s_i)
+ * sgn(t_j) area(tri(O, a_i, a_i+1) n tri(O, b_j, b_j+1)) on the vertices v - O, each term a triangle clipped by three half-planes;
+ * term t = i * n_b_vertices + j is added by lane t mod 64 in ascending t and the 64 partial sums meet in a butterfly over xor 32,
+ * 16, 8, 4, 2, 1; the ring areas are the shoelace sums on v - O in the same lane order. A box intersection of non-positive width
+ * or height gives inter = +0 without a clip; inter is clamped to [0, min(|area_A|, |area_B|)].
+ * status 0: computed. status 1 (device only): the two rings together have more than 1 024 vertices, the wave's LDS region — not
+ * computed, out is NaN; td_ring_pairs_area computes such a pair. status 2: refused, out is NaN — a pair index outside [0, n_a) /
+ * [0, n_b) (checked in the kernel: no ring memory is touched), a ring of fewer than 3 vertices, a non-finite coordinate.
+ * td_ring_pairs_area_dev: every pointer is DEVICE memory, xy_a / xy_b 16-byte aligned; one wave per pair, a bounded grid with a
+ * grid-stride loop (any n_pairs is one launch); asynchronous on `stream`. td_ring_pairs_area: HOST memory, host code, the wave's
+ * lanes emulated — its results equal the device's bit for bit; no vertex cap. Both return TD_ERR_INVALID (with a message, before
+ * anything runs) for a null pointer, a negative count or a misaligned xy; n_pairs = 0 returns TD_OK and launches nothing. */
+td_status td_ring_pairs_area_dev(const double* xy_a, const int64_t* start_a, int n_a, const double* xy_b, const int64_t* start_b,
+                                 int n_b, const int32_t* pairs, int64_t n_pairs, double* out, int32_t* status, void* stream);
+td_status td_ring_pairs_area(const double* xy_a, const int64_t* start_a, int n_a, const double* xy_b, const int64_t* start_b, int n_b,
+                             const int32_t* pairs, int64_t n_pairs, double* out, int32_t* status);
+
 #ifdef __cplusplus
 }
 #endif

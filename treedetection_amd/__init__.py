@@ -1,11 +1,13 @@
 """treedetection_amd — MI355X-native drop-in for the prediction stage of Jonetz/TreeDetection.
 
 Public surface mirrors the reference package (TreeDetection/__init__.py:3-9): process_files, preprocess_files,
-predict_tiles, postprocess_files, predict_on_model, Predictor, get_config, setup_model_cfg. The model forward runs in
+predict_tiles, postprocess_files, predict_on_model, Predictor, get_config, setup_model_cfg, clean_crowns. The model forward runs in
 libtreedet_hip.so (hand-written HIP for gfx950) behind the C ABI of include/treedet.h; there is no CPU fallback.
 """
 __version__ = "0.1.0"
 
+from .cleaning import (candidate_pairs, candidate_pairs_host, clean_crowns, clean_crowns_file,  # noqa: F401
+                       ring_pairs_iou)
 from .config import Config, get_config, setup_model_cfg  # noqa: F401
 from .detection import (cleanup_files, postprocess_files, predict_on_model, predict_tiles,  # noqa: F401
                         preprocess_files, process_files)

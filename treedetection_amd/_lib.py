@@ -22,6 +22,7 @@ ERR_UNSUPPORTED = -6  # TD_ERR_UNSUPPORTED
 JPEG_TABSET_BYTES = 11904  # TD_JPEG_TABSET_BYTES: one table set of td_tiff_jpeg_plan
 SAMPLE_U8, SAMPLE_F32 = 0, 1                          # TD_SAMPLE_*: source of td_resample_gdal_dev
 RESAMPLE_MODES = {"f32": 0, "u8": 1, "ndvi": 2}       # TD_RESAMPLE_*: its output modes
+RING_PAIR_CAP, RING_PAIR_WPB, RING_PAIR_GRID = 1024, 4, 2048   # ringiou.hip: vertices of a pair in LDS, waves per workgroup, workgroups per launch
 
 
 class TdError(RuntimeError):
@@ -95,6 +96,10 @@ SIGNATURES = {
                                        C.c_void_p]),
     "td_crown_pairs_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_uint16, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "td_crown_pairs_greedy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "td_ring_pairs_area_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+    "td_ring_pairs_area": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
+                                     C.c_void_p]),
     "td_trace_contours_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                         C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "td_find_contours": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),

@@ -8,7 +8,8 @@ are one launch of ``td_crown_stats`` per raster (libtreedet_hip.so; a workgroup 
 box, same membership arithmetic); the N x N box filters and the selection rules are small host numpy, written to follow
 the reference line by line *including* its quirks, which are listed in DESIGN.md §7 and marked ``# ref:`` below; with
 ``device_filters: true`` the pair tests of the two box filters run on the GPU and only the sparse result comes back
-(``td_crown_pairs_count`` / ``td_crown_pairs_fill``, crownpairs.hip; same arithmetic, same results).
+(``td_crown_pairs_count`` / ``td_crown_pairs_fill``, crownpairs.hip; same arithmetic, same results); with ``clean_crowns: true`` the
+layer is first thinned by the IoU of the crown OUTLINES (:mod:`treedetection_amd.cleaning`; off by default: same files).
 GDAL's bilinear decimation of the rasters (``ndvi_scaling_factor`` 0.2 in the example config) is restated from its
 published algorithm (:func:`resample_bilinear_gdal`, both directions); with ``device_decode: true`` the rasters are decoded in
 HBM and the same taps are applied there, NDVI included (:func:`resample_on_device`, ``td_resample_gdal_dev``). Not reproduced: fiona's
@@ -645,10 +646,16 @@ COLUMNS = ("Confidence_score", "poly_id", "Area", "TreeHeight", "Centroid", "Dia
 def process_single_file(file_path, processed_file_path, height_data_path, rgbi_data_path, device_id=0, config=None):
     """postprocessing.py:876-943: one stitched layer → ``processed_<name>.gpkg``; returns ``file_path`` or None on error
     (printed, like the reference)."""
+    from .cleaning import clean_crowns, clean_crowns_setting
+    thin = clean_crowns_setting((config or {}).get("clean_crowns", False))      # (a bad value is refused, not printed)
     try:
         layer = read_layer(file_path)
         scores = layer.columns.get("Confidence_score", [None] * len(layer))
-        feats = process_layer(layer.rings(), scores, config, height_data_path, rgbi_data_path,
+        layer_rings = layer.rings()
+        if thin:        # ``clean_crowns: true``: the layer is thinned by polygon IoU first, rings and scores together (host functions)
+            kept = clean_crowns(layer_rings, scores, iou_threshold=0.7, confidence=0, area_threshold=0, device=None)
+            layer_rings, scores = [layer_rings[i] for i in kept], [scores[i] for i in kept]
+        feats = process_layer(layer_rings, scores, config, height_data_path, rgbi_data_path,
                               int(str(device_id).replace("cuda:", "") or 0) if str(device_id) != "cpu" else 0)
         rings = [f["ring"] for f in feats]
         cols = {c: [f["properties"][c] for f in feats] for c in COLUMNS}
