@@ -228,6 +228,18 @@ td_status td_conv2d_nhwc(const void* x, const void* w, const float* scale, const
                          const void* residual, int res_shift, void* y, int B, int H, int W, int Cin,
                          int Cout, int KH, int KW, int stride, int pad, int relu, int precision,
                          void* stream);
+/* td_conv2d_nhwc at stride 1 without residual, with the two launch properties only the mask head uses (tests only: the op-level
+ * door to what phase 4 of the forward launches). out_mode 0: y [B,Ho,Wo,Cout]. out_mode 1 (the 2x2 / stride 2 deconvolution
+ * written as a 1x1 layer with a pixel-shuffle store; Cout a multiple of 32): y [B,2Ho,2Wo,Cq], Cq = Cout/4, filter row
+ * n = (dy*2+dx)*Cq + co lands at y[b, 2h+dy, 2w+dx, co], and scale / bias hold Cq entries indexed by co = n % Cq.
+ * rows_dyn (DEVICE int32 scalar, or NULL): the kernels read it and compute only the first min(B*Ho*Wo, *rows_dyn * rows_mul)
+ * output rows (rows_mul = Ho*Wo turns an image count into rows); nothing past them is written and no input row at or past
+ * them contributes to a row below them. `precision` carries the same bits as in td_conv2d_nhwc (forced tile id, strict
+ * selection, float16 tensors with float32 y); strict selection refuses a tile that cannot run the out_mode or a device row
+ * count (the fp16 ping-pong tile and the filter-direct tiles: out_mode 0 only; the filter-stationary tile: no device count). */
+td_status td_conv2d_rows_nhwc(const void* x, const void* w, const float* scale, const float* bias, void* y, int B, int H, int W,
+                              int Cin, int Cout, int KH, int KW, int pad, int relu, int out_mode, const int32_t* rows_dyn,
+                              int rows_mul, int precision, void* stream);
 /* A 256-channel float16 convolution (stride 1, + bias, ReLU) whose output feeds ONLY a 1x1 head (reference: detectron2's
  * StandardRPNHead behind prediction.py:183 — conv3x3 + ReLU, then the objectness / anchor-delta 1x1 layers, SURVEY.md
  * Appendix A item 5): the head is contracted from the finished tile inside the same launch and only

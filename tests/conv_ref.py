@@ -9,6 +9,11 @@ unwritten). Inputs (x, residual) sit inside allocations filled with quiet NaN: a
 stored output turns that output into NaN. All checks are torch ops on the tensors' device; only counts and the sampled
 rows reach the host.
 
+Launches with a device row count (td_conv2d_rows_nhwc; the mask head): `check(..., live_rows=n)` compares only conv rows
+below n, and every element of y that belongs to a row at or past n must still hold the sentinel. With out_mode 1 (the 2x2
+deconvolution's pixel-shuffle store) the reference is laid out as y is stored: y[b, 2h+dy, 2w+dx, co] comes from filter row
+(dy*2+dx)*Cq + co of conv row (b, h, w), with the scale and bias of co.
+
 Reference. For a sample of output pixels (every image's corners, the borders of a few images, the first and last row
 of 256-row M blocks at the start, middle and end, the whole ragged last M tile, and >= 2048 seeded random pixels; every
 output channel of each), the input patches are gathered on the device and converted to float64 on the host:
@@ -83,7 +88,9 @@ class Guarded:
 
 @dataclasses.dataclass(frozen=True)
 class Conv:
-    """One convolution launch: x [B,H,W,Cin] -> y [B,Ho,Wo,Cout]; res 0 none / 1 same size / 2 nearest-2x upsampled."""
+    """One convolution launch: x [B,H,W,Cin] -> y [B,Ho,Wo,Cout]; res 0 none / 1 same size / 2 nearest-2x upsampled.
+    out_mode 1 (the 2x2 deconvolution as a 1x1 layer with a pixel-shuffle store): y [B,2Ho,2Wo,Cq], Cq = Cout/4, filter
+    row (dy*2+dx)*Cq + co lands at y[b, 2h+dy, 2w+dx, co]; scale and bias have Cq entries."""
     name: str
     Cin: int
     Cout: int
@@ -97,6 +104,7 @@ class Conv:
     res: int = 0
     relu: bool = True
     out_f32: bool = False
+    out_mode: int = 0
 
     @property
     def Ho(self):
@@ -110,6 +118,16 @@ class Conv:
     def K(self):
         return self.k * self.k * self.Cin
 
+    @property
+    def Cy(self):
+        """Channels of a pixel of y as stored."""
+        return self.Cout // 4 if self.out_mode == 1 else self.Cout
+
+    @property
+    def y_shape(self):
+        """(rows, columns) of one image of y as stored."""
+        return (2 * self.Ho, 2 * self.Wo) if self.out_mode == 1 else (self.Ho, self.Wo)
+
 
 def make_inputs(L: Conv, fp16: bool, B: int, device, seed: int) -> dict:
     """Seeded inputs generated on `device` (fp16 tensors are generated as fp16: the reference reads the kernel's bits).
@@ -122,8 +140,8 @@ def make_inputs(L: Conv, fp16: bool, B: int, device, seed: int) -> dict:
     x.t.abs_()
     x.t.mul_((torch.rand(x.t.shape, generator=g, dtype=dt, device=device) > 0.15).to(dt))
     w = torch.randn((L.Cout, L.k, L.k, L.Cin), generator=g, dtype=torch.float32, device=device).mul_(1.0 / math.sqrt(L.K)).to(dt)
-    scale = torch.rand(L.Cout, generator=g, device=device).add_(0.5) if L.scale else None
-    bias = torch.randn(L.Cout, generator=g, device=device).mul_(0.5) if L.bias else None
+    scale = torch.rand(L.Cy, generator=g, device=device).add_(0.5) if L.scale else None
+    bias = torch.randn(L.Cy, generator=g, device=device).mul_(0.5) if L.bias else None
     res = None
     if L.res:
         sh = (B, L.Ho, L.Wo, L.Cout) if L.res == 1 else (B, L.Ho >> 1, L.Wo >> 1, L.Cout)
@@ -137,16 +155,26 @@ def out_dtype(L: Conv, fp16: bool):
 
 
 def new_output(L: Conv, inp: dict) -> Guarded:
-    return Guarded((inp["B"], L.Ho, L.Wo, L.Cout), out_dtype(L, inp["fp16"]), inp["x"].t.device)
+    return Guarded((inp["B"],) + L.y_shape + (L.Cy,), out_dtype(L, inp["fp16"]), inp["x"].t.device)
 
 
-def launch(L: Conv, inp: dict, y: Guarded, tile_cfg: int = -1, strict: bool = True, B: int = None, W: int = None, H: int = None):
-    """td_conv2d_nhwc on the guarded buffers (B / H / W override the map size: the 4 GB refusal). Raises on a refused launch."""
+def launch(L: Conv, inp: dict, y: Guarded, tile_cfg: int = -1, strict: bool = True, B: int = None, W: int = None, H: int = None,
+           count: torch.Tensor = None, rows_mul: int = None, rows_entry: bool = False):
+    """td_conv2d_nhwc on the guarded buffers (B / H / W override the map size: the 4 GB refusal). Raises on a refused launch.
+    `count` (a device int32 scalar: the kernels compute min(M, count * rows_mul) rows; rows_mul defaults to Ho * Wo, a count
+    of images), an out_mode 1 layer or `rows_entry` go through td_conv2d_rows_nhwc (stride 1, no residual)."""
     from treedetection_amd import _lib
     from tests.gpu_util import STRICT
     lib = _lib.load()
     p = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
     prec = (1 if inp["fp16"] else 0) | ((tile_cfg + 1) << 8) | (0x10000 if L.out_f32 else 0) | (STRICT if strict else 0)
+    if count is not None or L.out_mode or rows_entry:
+        assert L.stride == 1 and not L.res and (count is None or (count.dtype == torch.int32 and count.is_cuda and count.numel() == 1))
+        st = lib.td_conv2d_rows_nhwc(p(inp["x"]), p(inp["w"]), p(inp["scale"]), p(inp["bias"]), p(y), B or inp["B"], H or L.H, W or L.W,
+                                     L.Cin, L.Cout, L.k, L.k, L.pad, int(L.relu), L.out_mode, p(count),
+                                     (rows_mul or L.Ho * L.Wo) if count is not None else 1, prec, _lib.stream_ptr())
+        _lib.check(st, "td_conv2d_rows_nhwc")
+        return
     st = lib.td_conv2d_nhwc(p(inp["x"]), p(inp["w"]), p(inp["scale"]), p(inp["bias"]), p(inp["res"]), 1 if L.res == 2 else 0, p(y),
                             B or inp["B"], H or L.H, W or L.W, L.Cin, L.Cout, L.k, L.k, L.stride, L.pad, int(L.relu), prec,
                             _lib.stream_ptr())
@@ -211,22 +239,44 @@ def _residual_rows(L: Conv, res: torch.Tensor, rows: torch.Tensor) -> torch.Tens
 
 @dataclasses.dataclass
 class Reference:
-    rows: torch.Tensor
-    y64: torch.Tensor        # [S, Cout] float64 (host)
+    rows: torch.Tensor       # pixel indices of y AS STORED (out_mode 0: the conv rows; out_mode 1: four shuffled pixels per conv row)
+    y64: torch.Tensor        # [S, Cy] float64 (host)
     bound: torch.Tensor      # per-element bound
     norm2: torch.Tensor      # per-element RMS normaliser squared
     A: torch.Tensor          # |scale| S (1 + gamma_K) + |bias| + |residual| (the Winograd bound's scale)
 
 
+def stored_rows(L: Conv, rows: torch.Tensor) -> torch.Tensor:
+    """Pixel indices of y as stored for conv rows `rows`: [S] for out_mode 0, [S, 4] (q = dy*2+dx) for the pixel shuffle."""
+    if L.out_mode != 1:
+        return rows
+    b, rem = rows // (L.Ho * L.Wo), rows % (L.Ho * L.Wo)
+    h, w = rem // L.Wo, rem % L.Wo
+    q = torch.arange(4)
+    return (b[:, None] * 2 * L.Ho + 2 * h[:, None] + (q >> 1)[None]) * (2 * L.Wo) + 2 * w[:, None] + (q & 1)[None]
+
+
+def conv_row_of_pixel(L: Conv, px: torch.Tensor) -> torch.Tensor:
+    """The conv row that writes pixel `px` of y as stored (the inverse of stored_rows)."""
+    if L.out_mode != 1:
+        return px
+    H2, W2 = L.y_shape
+    b, rem = px // (H2 * W2), px % (H2 * W2)
+    return (b * L.Ho + (rem // W2) // 2) * L.Wo + (rem % W2) // 2
+
+
 def reference(L: Conv, inp: dict, rows: torch.Tensor) -> Reference:
-    """The sampled float64 reference, its per-element bound and RMS normaliser (see the module docstring)."""
+    """The sampled float64 reference, its per-element bound and RMS normaliser (see the module docstring). `rows` are conv
+    rows; with out_mode 1 filter row n = (dy*2+dx)*Cq + co of conv row (b,h,w) is y[b, 2h+dy, 2w+dx, co], with scale / bias of co."""
     P = _patches(L, inp["x"].t, rows).cpu().double()
     Wm = inp["w"].reshape(L.Cout, -1).cpu().double()
     y0 = P @ Wm.T
     S = P.abs() @ Wm.abs().T
     Q = ((P * P) @ (Wm * Wm).T).sqrt()
-    sc = inp["scale"].cpu().double() if inp["scale"] is not None else torch.ones(L.Cout, dtype=torch.float64)
-    bi = inp["bias"].cpu().double() if inp["bias"] is not None else torch.zeros(L.Cout, dtype=torch.float64)
+    sc = inp["scale"].cpu().double() if inp["scale"] is not None else torch.ones(L.Cy, dtype=torch.float64)
+    bi = inp["bias"].cpu().double() if inp["bias"] is not None else torch.zeros(L.Cy, dtype=torch.float64)
+    if L.out_mode == 1:                                                        # n = q*Cq + co takes the scale / bias of co
+        sc, bi = sc.repeat(4), bi.repeat(4)
     rr = _residual_rows(L, inp["res"].t, rows).cpu().double() if inp["res"] is not None else torch.zeros_like(y0)
     y = y0 * sc + bi + rr
     if L.relu:
@@ -237,7 +287,8 @@ def reference(L: Conv, inp: dict, rows: torch.Tensor) -> Reference:
     uo = U16 if out_dtype(L, inp["fp16"]) == torch.float16 else 0.0
     bound = bound + (uo * (y.abs() + bound) + 2.0 ** -25 if uo else 0.0)       # (+ half the fp16 subnormal spacing)
     norm2 = (U32 * sc.abs() * Q * math.sqrt(L.K)) ** 2 + (U32 * A) ** 2 + (uo * y) ** 2
-    return Reference(rows, y, bound, norm2, A)
+    sh = lambda t: t.reshape(-1, L.Cy)                                         # noqa: E731  ([S, 4*Cq] -> [4S, Cq], q-major per row)
+    return Reference(stored_rows(L, rows).reshape(-1), sh(y), sh(bound), sh(norm2), sh(A))
 
 
 @dataclasses.dataclass
@@ -248,27 +299,49 @@ class Verdict:
     rms: float
 
 
-def check(L: Conv, y: Guarded, ref: Reference) -> Verdict:
-    """Guards, leftover sentinel, finiteness, the per-element bound and the RMS criterion for one launch's output."""
+def check(L: Conv, y: Guarded, ref: Reference, live_rows: int = None) -> Verdict:
+    """Guards, leftover sentinel, finiteness, the per-element bound and the RMS criterion for one launch's output.
+    `live_rows` (a launch with a device row count): only conv rows below it are compared, none of their elements may hold
+    the sentinel, and EVERY element of y that belongs to a conv row at or past it must still hold the sentinel bit pattern."""
     if not y.guards_intact():
         return Verdict(False, "a guard zone around y was written", math.inf, math.inf)
-    left = y.pattern_count()
+    C = L.Cy
+    flat = y.t.reshape(-1, C)
+    dev = flat.device
+    is_pat = flat.view(y.ity) == y.pattern
+    keep = None
+    if live_rows is None:
+        left, live_vals = int(is_pat.sum().item()), flat
+    else:
+        live = conv_row_of_pixel(L, torch.arange(flat.shape[0], device=dev)) < live_rows
+        touched = (~is_pat).any(1) & ~live
+        if bool(touched.any().item()):
+            bad = touched.nonzero()[:8, 0].tolist()
+            return Verdict(False, f"{int(touched.sum())} pixels of y at or past the row count ({live_rows} rows) were written: pixels {bad}",
+                           math.inf, math.inf)
+        left, live_vals = int((is_pat & live[:, None]).sum().item()), flat[live]
+        keep = live[ref.rows.to(dev)].cpu()
     if left:
         return Verdict(False, f"{left} elements of y were never written (sentinel left)", math.inf, math.inf)
-    if not bool(torch.isfinite(y.t).all().item()):
-        bad = (~torch.isfinite(y.t.reshape(-1, L.Cout))).any(1).nonzero()[:8, 0].tolist()
+    if not bool(torch.isfinite(live_vals).all().item()):
+        bad = (~torch.isfinite(flat)).any(1).nonzero()[:8, 0].tolist()
         return Verdict(False, f"non-finite outputs at rows {bad}", math.inf, math.inf)
-    got = y.t.reshape(-1, L.Cout)[ref.rows.to(y.t.device)].cpu().double()
-    err = (got - ref.y64).abs()
-    ratio = err / ref.bound.clamp_min(1e-300)
+    rows, y64, bnd, norm2 = ref.rows, ref.y64, ref.bound, ref.norm2
+    if keep is not None:
+        rows, y64, bnd, norm2 = rows[keep], y64[keep], bnd[keep], norm2[keep]
+    if len(rows) == 0:
+        return Verdict(True, "", 0.0, 0.0)
+    got = flat[rows.to(dev)].cpu().double()
+    err = (got - y64).abs()
+    ratio = err / bnd.clamp_min(1e-300)
     worst = float(ratio.max())
-    rms = math.sqrt(float((err * err).sum()) / max(float(ref.norm2.sum()), 1e-300))
+    rms = math.sqrt(float((err * err).sum()) / max(float(norm2.sum()), 1e-300))
     if worst > 1.0:
         i = int(ratio.argmax())
-        r, c = int(ref.rows[i // L.Cout]), i % L.Cout
+        r, c = int(rows[i // C]), i % C
         n = int((ratio > 1).sum())
         return Verdict(False, f"{n} sampled outputs over the fp64 bound; worst err/bound {worst:.3g} at row {r} channel {c} "
-                              f"(got {float(got.reshape(-1)[i]):.9g}, fp64 {float(ref.y64.reshape(-1)[i]):.9g})", worst, rms)
+                              f"(got {float(got.reshape(-1)[i]):.9g}, fp64 {float(y64.reshape(-1)[i]):.9g})", worst, rms)
     if rms > RMS_MAX[y.t.dtype]:
         return Verdict(False, f"RMS error {rms:.3g} x the fp32-accumulation scale > RMS_MAX {RMS_MAX[y.t.dtype]}", worst, rms)
     return Verdict(True, "", worst, rms)
@@ -298,24 +371,27 @@ def _bd_ok(L: Conv, fp16: bool) -> bool:
     return L.Cin % ke == 0 and L.k * L.k <= 32 and -(-L.Cout // 32) * L.k * L.k * (L.Cin // ke) * 4096 < _LIM
 
 
-def tile_runs(cfg: int, L: Conv, fp16: bool, B: int) -> bool:
-    """Whether td_conv2d_nhwc in strict mode runs tile `cfg` on this launch (conv2d_launch's rules)."""
+def tile_runs(cfg: int, L: Conv, fp16: bool, B: int, dyn: bool = False) -> bool:
+    """Whether td_conv2d_nhwc / td_conv2d_rows_nhwc in strict mode runs tile `cfg` on this launch (conv_tile_refusal's rules;
+    `dyn`: the launch carries a device row count). The fp16 ping-pong tile, the plane tiles and the filter-direct family
+    store plain rows only (no out_mode 1); the filter-stationary tile takes neither out_mode 1 nor a device count."""
     if cfg in (21, 22, 28) or not 0 <= cfg <= 33:
         return False
     if cfg == 17:
-        return fp16
+        return fp16 and L.out_mode == 0
     if 18 <= cfg <= 20:
-        return _plane_ok(L, fp16, B)
+        return _plane_ok(L, fp16, B) and L.out_mode == 0
     if cfg == 33:
-        return _bs_ok(L, fp16, B)
+        return _bs_ok(L, fp16, B) and L.out_mode == 0 and not dyn
     if 23 <= cfg <= 27 or cfg in (29, 30):
-        return _bd_ok(L, fp16)
+        return _bd_ok(L, fp16) and L.out_mode == 0
     return True
 
 
-def tuner_ids(L: Conv, fp16: bool, B: int) -> list:
+def tuner_ids(L: Conv, fp16: bool, B: int, dyn: bool = False) -> list:
     """The ids the engine's tuned_cfg times for this layer shape (engine.cpp: the direct-conv candidates of one layer with
-    a fragment-ordered filter copy — every engine layer whose Cin is a multiple of the k-chunk has one)."""
+    a fragment-ordered filter copy — every engine layer whose Cin is a multiple of the k-chunk has one). A candidate that
+    conv_tile_refusal refuses for the launch's out_mode or device row count (`dyn`) is never timed."""
     ksteps = L.K // (64 if fp16 else 32)
     plane = _plane_ok(L, fp16, B)
     bd = L.Cin % (64 if fp16 else 32) == 0 and L.k * L.k <= 32
@@ -332,6 +408,10 @@ def tuner_ids(L: Conv, fp16: bool, B: int) -> list:
         if c == 33 and not (L.k == 1 and L.stride == 1 and L.Cout >= 128 and ksteps <= 4 and ksteps != 3):
             continue
         if c in (31, 32) and L.Cout > 32:
+            continue
+        if L.out_mode != 0 and (c == 17 or 18 <= c <= 20 or 23 <= c <= 27 or c in (29, 30, 33)):
+            continue
+        if dyn and c == 33:
             continue
         out.append(c)
     return out

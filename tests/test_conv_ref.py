@@ -130,3 +130,97 @@ def test_fp16_accumulation_is_caught_by_the_rms_criterion_alone():
     exact, bad = cr.check(L, emulate(L, inp), ref), cr.check(L, emulate(L, inp, "fp16_accumulation"), ref)
     assert exact.rms <= cr.RMS_MAX[torch.float16] / 3
     assert bad.rms > 1.4 * cr.RMS_MAX[torch.float16], bad.rms
+
+
+# ---- launches with a device row count and the pixel-shuffle store (td_conv2d_rows_nhwc; the mask head's phase 4) ----
+ROWS_SHAPES = {
+    # (layer, fp16): B = 4 reserved RoIs of 14 x 14, 3 live: 588 live rows end inside the 256-row block 512..767
+    "fp32_conv": (cr.Conv("mc32", 64, 64, 3, 1, 1, 14, 14, scale=False), False),
+    "fp16_conv": (cr.Conv("mc16", 64, 64, 3, 1, 1, 14, 14, scale=False), True),
+    "fp32_deconv": (cr.Conv("md32", 64, 128, 1, 1, 0, 14, 14, scale=False, out_mode=1), False),
+    "fp16_deconv": (cr.Conv("md16", 64, 128, 1, 1, 0, 14, 14, out_mode=1), True),
+}
+ROWS_B, ROWS_COUNT = 4, 3
+ROWS_MUTANTS = ["shuffle_dy_dx_swapped", "bias_at_n", "last_live_roi_unwritten", "row_past_count", "halo_from_next_roi"]
+
+
+def emulate_rows(L, inp, count, mutant=None):
+    """The first `count` RoIs in float64, rounded once, stored as the launch stores them; everything else keeps the sentinel."""
+    HW, Cq = L.Ho * L.Wo, L.Cy
+    x, w = _nchw(inp["x"].t[:count]), _nchw(inp["w"])
+    y = F.conv2d(x, w, padding=L.pad)                                           # [count, Cout, Ho, Wo]
+    if mutant == "halo_from_next_roi":          # one pixel of RoI 0's last row: the taps below it read RoI 1's first row, not padding
+        ow = 5
+        patch = torch.zeros(x.shape[1], 3, 3, dtype=torch.float64)
+        patch[:, :2] = x[0, :, L.H - 2:, ow - 1:ow + 2]
+        patch[:, 2] = x[1, :, 0, ow - 1:ow + 2]
+        y[0, :, L.Ho - 1, ow] = (w * patch[None]).sum((1, 2, 3))
+    sc = inp["scale"].double() if inp["scale"] is not None else torch.ones(Cq, dtype=torch.float64)
+    bi = inp["bias"].double() if inp["bias"] is not None else torch.zeros(Cq, dtype=torch.float64)
+    if L.out_mode == 1:
+        sc = sc.repeat(4)
+        bi = torch.cat([bi, torch.zeros(3 * Cq, dtype=torch.float64)]) if mutant == "bias_at_n" else bi.repeat(4)
+    y = (y * sc[None, :, None, None] + bi[None, :, None, None]).clamp_min(0).permute(0, 2, 3, 1)     # [count, Ho, Wo, Cout]
+    out = cr.new_output(L, inp)
+    if L.out_mode == 1:
+        y = y.reshape(count, L.Ho, L.Wo, 2, 2, Cq)                              # [.., dy, dx, co]
+        if mutant == "shuffle_dy_dx_swapped":
+            y = y.transpose(3, 4)
+        y = y.permute(0, 1, 3, 2, 4, 5).reshape(count, 2 * L.Ho, 2 * L.Wo, Cq)
+    n = count - 1 if mutant == "last_live_roi_unwritten" else count
+    out.t[:n] = y[:n].to(out.t.dtype)
+    if mutant == "row_past_count":              # conv row count * HW (the first dead one, inside the last live 256-row block)
+        assert (count * HW) % cr.BLOCK_ROWS != 0
+        px = cr.stored_rows(L, torch.tensor([count * HW])).reshape(-1)[0]
+        out.t.reshape(-1, Cq)[px] = 0.5
+    return out
+
+
+def _rows_setup(key):
+    L, fp16 = ROWS_SHAPES[key]
+    inp = cr.make_inputs(L, fp16, ROWS_B, "cpu", seed=17)
+    ref = cr.reference(L, inp, torch.arange(ROWS_B * L.Ho * L.Wo))            # every row of every reserved RoI, once
+    qi, qv = cr.QNAN[inp["x"].t.dtype]
+    inp["x"].t[ROWS_COUNT:].view(qi).fill_(qv)                                 # dead RoIs: quiet NaN
+    return L, inp, ref
+
+
+@pytest.mark.parametrize("key", list(ROWS_SHAPES))
+def test_exact_live_rows_pass_and_the_reference_shuffles(key):
+    L, inp, ref = _rows_setup(key)
+    live = ROWS_COUNT * L.Ho * L.Wo
+    v = cr.check(L, emulate_rows(L, inp, ROWS_COUNT), ref, live_rows=live)
+    print(f"\n[exact rows {key}] err/bound {v.err_over_bound:.3g}, RMS {v.rms:.3g}")
+    assert v.ok, v.why
+    assert cr.check(L, cr.new_output(L, inp), ref, live_rows=0).ok               # count 0: an untouched y is right
+    assert not cr.check(L, emulate_rows(L, inp, ROWS_COUNT), ref, live_rows=live - 1).ok     # and the count is exact
+    assert not cr.check(L, emulate_rows(L, inp, ROWS_COUNT), ref).ok             # a static launch leaves no sentinel
+    if L.out_mode == 1:                                                        # the stated layout, element by element
+        px = cr.stored_rows(L, torch.tensor([L.Wo + 2]))                        # RoI 0, h = 1, w = 2
+        assert px.tolist() == [[2 * 28 + 4, 2 * 28 + 5, 3 * 28 + 4, 3 * 28 + 5]]
+        assert torch.equal(cr.conv_row_of_pixel(L, px.reshape(-1)), torch.full((4,), L.Wo + 2))
+
+
+@pytest.mark.parametrize("key,mutant", [(k, m) for k in ROWS_SHAPES for m in ROWS_MUTANTS
+                                         if not (m in ("shuffle_dy_dx_swapped", "bias_at_n") and ROWS_SHAPES[k][0].out_mode == 0)
+                                         and not (m == "halo_from_next_roi" and ROWS_SHAPES[k][0].k == 1)])
+def test_rows_mutant_is_rejected(key, mutant):
+    L, inp, ref = _rows_setup(key)
+    v = cr.check(L, emulate_rows(L, inp, ROWS_COUNT, mutant), ref, live_rows=ROWS_COUNT * L.Ho * L.Wo)
+    print(f"\n[rows mutant {mutant} on {key}] rejected: {v.why}")
+    assert not v.ok, f"{mutant} passed the checker (err/bound {v.err_over_bound:.3g}, RMS {v.rms:.3g})"
+
+
+def test_rows_predicates_match_the_library_rules():
+    """conv_tile_refusal on out_mode and a device count: PP8 and the filter-direct family refuse the shuffle, the
+    filter-stationary tile refuses both, the plain igemm tiles take everything."""
+    conv = cr.Conv("mask.conv", 256, 256, 3, 1, 1, 14, 14, scale=False)
+    dec = cr.Conv("mask.deconv", 256, 1024, 1, 1, 0, 14, 14, scale=False, out_mode=1)
+    one = cr.Conv("one", 128, 1024, 1, 1, 0, 14, 14, scale=False)
+    for fp16 in (False, True):
+        assert all(cr.tile_runs(c, dec, fp16, 8, dyn) == (c <= 16 or c in (31, 32)) for c in cr.SWEEP_IDS for dyn in (False, True))
+        assert cr.tile_runs(33, one, fp16, 8) and not cr.tile_runs(33, one, fp16, 8, dyn=True)
+        assert cr.tile_runs(23, conv, fp16, 8, dyn=True) and cr.tile_runs(17, conv, fp16, 8, dyn=True) == fp16
+        assert not {17, 23, 24, 25, 26, 27, 29, 30, 33} & set(cr.tuner_ids(dec, fp16, 8, dyn=True))
+        assert 33 in cr.tuner_ids(one, fp16, 8) and 33 not in cr.tuner_ids(one, fp16, 8, dyn=True)
+        assert set(cr.tuner_ids(dec, fp16, 8, dyn=True)) <= {c for c in cr.SWEEP_IDS if cr.tile_runs(c, dec, fp16, 8, True)}

@@ -77,6 +77,7 @@ SIGNATURES = {
     "td_resize_shape": (None, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "td_conv2d_nhwc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
                        + [C.c_int] * 11 + [C.c_void_p]),
+    "td_conv2d_rows_nhwc": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 10 + [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "td_conv2d_head_nhwc": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 9 + [C.c_void_p]),
     "td_conv2d_winograd_head_nhwc": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 5 + [C.c_void_p]),
     "td_conv2d_winograd_nhwc": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 6 + [C.c_void_p]),

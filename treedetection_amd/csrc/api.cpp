@@ -54,6 +54,27 @@ td_status td_conv2d_nhwc(const void* x, const void* w, const float* scale, const
     return conv2d_api(a, precision, stream);
 }
 
+td_status td_conv2d_rows_nhwc(const void* x, const void* w, const float* scale, const float* bias, void* y, int B, int H, int W,
+                              int Cin, int Cout, int KH, int KW, int pad, int relu, int out_mode, const int32_t* rows_dyn,
+                              int rows_mul, int precision, void* stream) {
+    TD_REQUIRE(x && w && y, "td_conv2d_rows_nhwc: null pointer");
+    TD_REQUIRE(KH >= 1 && KW >= 1 && B >= 1, "td_conv2d_rows_nhwc: bad geometry");
+    TD_REQUIRE(out_mode == 0 || out_mode == 1, "td_conv2d_rows_nhwc: out_mode %d (0 plain, 1 pixel shuffle)", out_mode);
+    TD_REQUIRE(!rows_dyn || rows_mul >= 1, "td_conv2d_rows_nhwc: rows_mul %d with a device row count", rows_mul);
+    ConvArgs a{};
+    a.x = x; a.w = w; a.scale = scale; a.bias = bias; a.y = y;
+    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.KH = KH; a.KW = KW;
+    a.stride = 1; a.pad = pad;
+    a.Ho = H + 2 * pad - KH + 1;
+    a.Wo = W + 2 * pad - KW + 1;
+    a.relu = relu; a.out_mode = out_mode;
+    a.M = B * a.Ho * a.Wo; a.m_dyn = rows_dyn; a.m_mul = rows_dyn ? rows_mul : 1;
+    a.out_f32 = (precision & 0x10000) && (precision & 0xff) == TD_PRECISION_FP16 ? 1 : 0;
+    a.tile_cfg = ((precision >> 8) & 0xff) - 1;
+    a.tile_strict = (precision & 0x20000) ? 1 : 0;
+    return conv2d_api(a, precision, stream);
+}
+
 td_status td_conv2d_head_nhwc(const void* x, const void* w, const float* bias, const void* head_w, const float* head_b,
                               float* head_y, int B, int H, int W, int Cin, int KH, int KW, int pad, int head_n, int precision,
                               void* stream) {

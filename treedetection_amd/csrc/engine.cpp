@@ -1448,6 +1448,10 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
     }
     if ((st = run_conv(e->deconv, mx, mrows, 14, 14, 1, 0, true, e->deconv_out, nullptr, 0, s, prec, e->total_rows, 196, 1)) < 0) return st;
     }
+    // (stage tests: the device row count every launch above reads, and the last two layers' outputs as stored)
+    set_named(e, "mask_total_rows", e->total_rows, 1);
+    set_named(e, "mask_fcn3", e->mbuf0, mrows, 14, 14, e->fpn_c, (e->desc.precision == TD_PRECISION_FP16 ? 2 : 4));
+    set_named(e, "mask_fcn4", e->mbuf1, mrows, 14, 14, e->fpn_c, (e->desc.precision == TD_PRECISION_FP16 ? 2 : 4));
     // pixel-shuffle store of the deconv (conv_tiles.h, out_mode 1): [rows, 28, 28, C / 4]
     set_named(e, "mask_deconv", e->deconv_out, mrows, 28, 28, e->deconv.cout / 4, (e->desc.precision == TD_PRECISION_FP16 ? 2 : 4));
     }   // phase 4
