@@ -221,7 +221,7 @@ td_status td_bottleneck_tail_nhwc(const void* x, const void* w2, const float* sc
  * (18-20) off a plain fp32 1x1 / stride-1 layer, the filter-stationary tile (33) where conv_bs_ok fails, a filter-direct
  * tile where conv_bd_ok fails — returns TD_ERR_INVALID with a message naming the id and the condition, instead of running
  * the heuristic tile in its place.
- * Tile ids 34-36 (float32 tensors, 1x1 without padding, Cin a multiple of 32 only) contract on the bf16 matrix cores with both
+ * Tile ids 34-37 (float32 tensors, 1x1 without padding, Cin a multiple of 32 only) contract on the bf16 matrix cores with both
  * operands written as three bf16 pieces (six piece products per 16 k into the float32 accumulator, conv_split.hip): float32 in
  * and out, another rounding than ids 0-33 (inside the same float64 bound), bit-identical to each other. */
 td_status td_conv2d_nhwc(const void* x, const void* w, const float* scale, const float* bias,

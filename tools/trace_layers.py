@@ -119,7 +119,7 @@ def main(path, depth=50, fp32=False):
             assert "bottleneck_tail" in kn, (name, kn)
         kern = label if label else ("pp8 grouped" if "grouped" in name else "pp8" if "conv_pp8" in kn else "bottleneck_tail" if "bottleneck_tail" in kn else
                                     "conv_sk" if "conv_sk" in kn else "conv_bs (filter-stationary)" if "conv_bs" in kn else
-                                    ("conv_split 64x256" if "Li2ELi4ELi1ELi2" in kn or "<2, 4, 1, 2" in kn else "conv_split 128x128" if "Li2ELi2ELi2ELi2" in kn or "<2, 2, 2, 2" in kn else
+                                    ("conv_split 64x256" if "Li2ELi4ELi1ELi2" in kn or "<2, 4, 1, 2" in kn else "conv_split 64x128" if "Li2ELi2ELi1ELi2" in kn or "<2, 2, 1, 2" in kn else "conv_split 128x128" if "Li2ELi2ELi2ELi2" in kn or "<2, 2, 2, 2" in kn else
                                      "conv_split 128x256") if "conv_split" in kn else ("conv_bd 64x256" if "Li2ELi2ELi4" in kn or "2, 2, 4" in kn else "conv_bd 128x256" if "Li4ELi2ELi4" in kn or "4, 2, 4" in kn else
                                                  "conv_bd 128x128" if "Li4ELi1ELi4" in kn or "4, 1, 4" in kn else "conv_bd 64x128") if "conv_bd" in kn else
                                     "plane_gemm" + kn.split("plane_gemm_kernel")[1].split("(")[0][:12] if "plane_gemm" in kn else

@@ -145,9 +145,10 @@ inline constexpr ConvTile TD_CONV_TILES[] = {
     {TILE_IGEMM,   0, TILE_ANY, false, false, 15, 0,   0, 32},     // 31: 256x32, 4 x 1 waves (the thin heads)
     {TILE_IGEMM,   0, TILE_ANY, false, false, 17, 0,   0, 32},     // 32: 128x32
     {TILE_BS,      0, TILE_ANY, false, true,   0, 4, 128,  0},     // 33: conv_bs_kernel (its other tuning rules: conv_bs_ok)
-    {TILE_SPLIT,   0, TILE_F32, false, false, 21, 0,   0,  0},     // 34: conv_split_kernel 128x256 (ranks 21 - 23: timed for launches with w_split only,
+    {TILE_SPLIT,   0, TILE_F32, false, false, 21, 0,   0,  0},     // 34: conv_split_kernel 128x256 (ranks 21 - 24: timed for launches with w_split only,
     {TILE_SPLIT,   1, TILE_F32, false, false, 22, 0,   0,  0},     // 35: 128x128               and then nothing else is — tuned_cfg filters by family)
     {TILE_SPLIT,   2, TILE_F32, false, false, 23, 0,   0,  0},     // 36: 64x256
+    {TILE_SPLIT,   3, TILE_F32, false, false, 24, 0,   0,  0},     // 37: 64x128, 2 waves (the M = 5 000 layers: twice the blocks of 35)
 };
 static inline const ConvTile* conv_tile(int id) { return id >= 0 && id < (int)(sizeof TD_CONV_TILES / sizeof *TD_CONV_TILES) ? &TD_CONV_TILES[id] : nullptr; }
 static inline bool conv_head_capable(int id, int precision) { return precision == TD_PRECISION_FP16 && conv_tile(id) && conv_tile(id)->head; }
@@ -165,7 +166,7 @@ td_status conv_bd_launch(const ConvArgs& a, int precision, int variant, hipStrea
 // filter-stationary form (conv_bstat.hip, tile id 33)
 bool conv_bs_ok(const ConvArgs& a, int precision);
 td_status conv_bs_launch(const ConvArgs& a, int precision, hipStream_t stream);
-// split-bf16 form (conv_split.hip, tile ids 34 - 36): w [cout][cin] fp32 → the three-piece fragment bank (6 bytes per weight)
+// split-bf16 form (conv_split.hip, tile ids 34 - 37): w [cout][cin] fp32 → the three-piece fragment bank (6 bytes per weight)
 void conv_split_pack(const float* w, int cout, int cin, std::vector<unsigned char>& out);
 bool conv_split_ok(const ConvArgs& a, int precision);
 td_status conv_split_launch(const ConvArgs& a, int variant, hipStream_t stream);

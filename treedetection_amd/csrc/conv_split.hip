@@ -1,4 +1,4 @@
-// conv_split_kernel: fp32 1x1 / FC contractions on the bf16 matrix cores (tile ids 34 - 36, family TILE_SPLIT), fp32 in and out.
+// conv_split_kernel: fp32 1x1 / FC contractions on the bf16 matrix cores (tile ids 34 - 37, family TILE_SPLIT), fp32 in and out.
 //
 // Why: the fp32 engine's 1x1 and FC layers run v_mfma_f32_32x32x2_f32 at 65 - 83 % of its 157 TFLOP/s; no fp32 tile moves that
 // ceiling. v_mfma_f32_32x32x16_bf16 occupies the pipe for 32 cycles (the fp32 MFMA: 64) and contracts 16 k instead of 2. So every fp32 operand is
@@ -11,7 +11,7 @@
 // (tests/test_conv_split_ref.py: RMS 0.11 - 0.15 of the fp32-accumulation scale; dropping one more product is rejected).
 // Six bf16 MFMAs replace the eight fp32 MFMAs of 16 k: 192 cycles against 512, an MFMA floor of 157 x 16 / 6 = 419 TFLOP/s.
 // Another rounding than the fp32 tiles: NOT bit-identical to ids 0 - 33, so a fixed rule on the layer picks it (engine.cpp),
-// never the tuner; ids 34 - 36 are bit-identical to EACH OTHER (same pieces, same product order inside a slice, slices and
+// never the tuner; ids 34 - 37 are bit-identical to EACH OTHER (same pieces, same product order inside a slice, slices and
 // k-chunks ascending, same epilogue), the tuner chooses among them. Non-finite activations: inf - inf makes the second piece NaN.
 //
 // Block skeleton: conv_bd_kernel's.
@@ -30,10 +30,10 @@
 // 24 filter fragments (24 KB; the two waves of a block column read the same ones, the second through the vector L1).
 // Registers of that tile: 128 accumulators (AGPRs) + 3 x 48 filter registers + 16 A + 2 x 24 pieces: 211 VGPRs + 128 AGPRs, one
 // wave per SIMD, no scratch; the 64 x 64 wave tile: 198 registers, two waves per SIMD. LDS: 3 x BM x 128 B of stages (49 152 B at
-// 128 rows), re-used by the epilogue's fp32 wave-row staging (64 x 260 x 4 B = 66 560 B for the 256-column tiles).
-// Measured (profiles/f32_split.txt, batch 8): fc1 (8000 x 1024 x 12544) 1 549 -> 900 us = 228 TFLOP/s, fc2 137 -> 89 us; the 1x1
-// layers of res3 - res5 and the FPN laterals (8 - 64 k-chunks per block) 3.27 -> 2.86 ms in the layer table, headline not measured:
-// off by default.
+// 128 rows), re-used by the epilogue's fp32 wave-row staging (64 x 260 x 4 B = 66 560 B for the 256-column tiles, 33 792 B for 64 x 128).
+// Measured (profiles/f32_split.txt, batch 8): fc1 (8000 x 1024 x 12544) 1 549 -> 900 us = 228 TFLOP/s, fc2 137 -> 89 us. conv1 and the
+// shortcuts of res3 - res5 and the FPN laterals (8 - 64 k-chunks per block; profiles/f32_split_backbone.txt): 2.41 -> 1.95 ms in the layer
+// table, headline 697.6 -> 726.2 tiles/s: on by default with the box head (engine.cpp SPLIT_DEFAULT); conv3 ties on its fp32 tiles: off.
 #include "common.h"
 #include "conv_tiles.h"
 
@@ -299,6 +299,7 @@ bool conv_split_ok(const ConvArgs& a, int precision) {
 td_status conv_split_launch(const ConvArgs& a, int variant, hipStream_t stream) {
     TD_REQUIRE(conv_split_ok(a, TD_PRECISION_FP32), "split-bf16 contraction: unsupported launch (fp32 1x1 without padding, split filter bank)");
     switch (variant) {
+        case 3: return launch_split<2, 2, 1, 2, 2>(a, stream);     // 64 x 128: 1 x 2 waves of 64 x 64 (M = 5 000 with N <= 512: 158 - 316 blocks, not 80 - 160)
         case 2: return launch_split<2, 4, 1, 2, 1>(a, stream);     // 64 x 256: 1 x 2 waves of 64 x 128 (row counts that leave the 128-row grid short)
         case 1: return launch_split<2, 2, 2, 2, 2>(a, stream);     // 128 x 128: 2 x 2 waves of 64 x 64, two blocks per CU
         default: return launch_split<2, 4, 2, 2, 1>(a, stream);    // 128 x 256: 2 x 2 waves of 64 x 128, one wave per SIMD

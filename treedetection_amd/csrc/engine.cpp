@@ -32,7 +32,8 @@ struct HostTensor {
     }
 };
 
-enum { SPLIT_FC = 1, SPLIT_LATERAL = 2, SPLIT_CONV1 = 4, SPLIT_CONV3 = 8, SPLIT_SHORTCUT = 16, SPLIT_DEFAULT = SPLIT_FC };
+enum { SPLIT_FC = 1, SPLIT_LATERAL = 2, SPLIT_CONV1 = 4, SPLIT_CONV3 = 8, SPLIT_SHORTCUT = 16,
+       SPLIT_DEFAULT = SPLIT_FC | SPLIT_LATERAL | SPLIT_CONV1 | SPLIT_SHORTCUT };
 
 struct ConvLayer {
     int cout = 0, cin = 0, kh = 1, kw = 1;
@@ -149,8 +150,9 @@ struct td_engine {
     // classes (TD_F32_SPLIT; 0 = none, for an A/B on one build): SPLIT_FC the box head's fc1 / fc2, SPLIT_LATERAL the four FPN
     // laterals, SPLIT_CONV1 / SPLIT_CONV3 / SPLIT_SHORTCUT the 1x1 layers of res3 - res5. Never: layers that also exist inside a
     // fused kernel or have a bit-identity twin (res2, the RPN head, the box and mask predictors), K < 256, the fp16 engine.
-    // The default is the box head, the class whose gain on the headline was measured; the others are faster in the per-layer table
-    // (profiles/f32_split.txt) but have no headline measurement yet.
+    // The default is the box head, the FPN laterals, conv1 and the shortcuts (23): the classes whose gain on the headline was
+    // measured (profiles/f32_split.txt, profiles/f32_split_backbone.txt). conv3 stays off: res4 ties or loses in the per-layer table.
+    // Cost: the split banks, 6 B per weight, about 48 MB per fp32 engine beside the fp32 filters.
     int f32_split = SPLIT_DEFAULT;
     std::string tune_cache;       // TD_TUNE_CACHE: load / append measured choices (keeps profiled runs free of tuning launches)
     // The tuner times every candidate tile with the L2 (8 x 4 MB) emptied before each launch (a fill of this scratch on the same
