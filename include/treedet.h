@@ -392,6 +392,28 @@ int64_t td_tiff_inflate(const uint8_t* src, int64_t n, uint8_t* dst, int64_t cap
  * after the last DEFLATE block (bytes behind it are ignored, as zlib leaves them unused). Accepts exactly the streams zlib's inflate
  * accepts; TD_ERR_INVALID for a corrupt stream, a wrong checksum or a missing trailer, TD_ERR_CAPACITY. */
 int64_t td_tiff_inflate_verified(const uint8_t* src, int64_t n, uint8_t* dst, int64_t cap);
+/* Zstandard (RFC 8878; TIFF compression 50000, GDAL's COMPRESS=ZSTD; zstd_core.h). One strip or tile → dst: every frame of the stream
+ * in turn, skippable frames skipped, a content checksum (XXH64, low 32 bits) verified. Returns the bytes produced, TD_ERR_INVALID for a
+ * corrupt stream, a dictionary id, a wrong checksum or bytes that begin no frame, TD_ERR_CAPACITY when the stream regenerates more
+ * than cap bytes. The tile reader's block decoder; libzstd is used nowhere on the reading side. */
+int64_t td_tiff_zstd_decode(const uint8_t* src, int64_t n, uint8_t* dst, int64_t cap);
+/* What a Zstandard stream is made of (fixture generator, coverage test): counters int64 [TD_ZSTD_STATS], in this order — frames,
+ * block_raw, block_rle, block_comp, max_blocks_per_frame, lit_raw, lit_rle, lit_huff, lit_treeless, lit_streams_1, lit_streams_4,
+ * hufw_direct, hufw_fse, seq0, LL_predef, LL_rle, LL_fse, LL_repeat, OF_predef, OF_rle, OF_fse, OF_repeat, ML_predef, ML_rle, ML_fse,
+ * ML_repeat, window_desc, single_segment, checksum, seq_long (3-byte sequence count), seq_2byte, skippable. Returns the bytes the stream
+ * decodes to or a negative status. */
+#define TD_ZSTD_STATS 32
+int64_t td_zstd_stream_stats(const uint8_t* src, int64_t n, int64_t* counters);
+/* Zstandard blocks on the GPU, one wave per block (zstddecode.hip): arguments and launch shape as td_tiff_inflate_dev (comp padded by
+ * >= 8 bytes, waves share workgroups, one workgroup per CU at most, blocks by a per-launch counter, asynchronous on `stream`). status
+ * int32 [nblocks]: 0 ok, 1 corrupt, 2 more than block_cap bytes (decoded[b] then says how far the decoder got, the bytes that fit are
+ * right), 4 declined — a content checksum, a second frame or a skippable frame in the block: the host reader takes such a raster.
+ * scratch: DEVICE memory of td_tiff_zstd_scratch_bytes(nblocks) bytes (the literal buffers of the resident decoder waves), to be kept
+ * until the launch has ended. */
+td_status td_tiff_zstd_decode_dev(const uint8_t* comp, const int64_t* block_off, const int64_t* block_nbytes, int nblocks,
+                                  uint8_t* blocks_out, int64_t block_cap, int64_t* decoded, int32_t* status, uint8_t* scratch,
+                                  int64_t scratch_bytes, void* stream);
+int64_t td_tiff_zstd_scratch_bytes(int nblocks);
 /* Decoded blocks (strips: block_w = width; tiles: full padded tiles, row-major grid blocks_across x blocks_down) → the raster
  * image [height][width][spp] uint8 (DEVICE), predictor 2 undone per block row on the way (td_tiff_unpredict's arithmetic).
  * spp <= 4. Asynchronous on `stream`. */

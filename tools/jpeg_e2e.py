@@ -1,5 +1,5 @@
 """Files-to-files Predictor rate on a JPEG-in-TIFF raster, device decoder on ("auto" / true) against the host reader (false):
-python tools/jpeg_e2e.py [side=9000] [tile=256] [quality=90] [subsampling=2] [layout=complete|gdal] [restart=0] [precision=fp16]
+python tools/jpeg_e2e.py [codec=jpeg | zstd [level=9] | lzw | deflate, the three with [predictor=2]] [side=9000] [tile=256] [quality=90] [subsampling=2] [layout=complete|gdal] [restart=0] [precision=fp16]
 [batch=16] [images=3] [modes=true,false] [bands=3|4] [device_decode_long_jpeg=false|true]
 The raster (side x side x bands uint8, synthetic orthophoto tiles; bands=4 adds the green band again as a near-infrared band: RGBI,
 of which the tile loop reads bands 0 - 2) is cut into the reference's 450 x 450 px tiles; every mode predicts
@@ -41,9 +41,13 @@ try:
             img[:, r * S:(r + 1) * S, c * S:(c + 1) * S] = t if bands == 3 else np.concatenate([t, t[1:2]])
     img = np.ascontiguousarray(img[:, :side, :side])
     tif = f"{root}/rgb/324125000.tif"
-    write_geotiff(tif, img, (0.2, 0.0, 412000.0, 0.0, -0.2, 5318000.0 + side * 0.2), 25832, compression="jpeg", tile=(tile, tile),
-                  jpeg_quality=int(args.get("quality", 90)), jpeg_subsampling=int(args.get("subsampling", 2)),
-                  jpeg_tables=args.get("layout", "complete") == "gdal", jpeg_restart=int(args.get("restart", 0)))
+    codec = args.get("codec", "jpeg")
+    if codec == "jpeg":
+        ckw = dict(jpeg_quality=int(args.get("quality", 90)), jpeg_subsampling=int(args.get("subsampling", 2)),
+                   jpeg_tables=args.get("layout", "complete") == "gdal", jpeg_restart=int(args.get("restart", 0)))
+    else:                                                          # a lossless codec of the block decoders
+        ckw = dict(predictor=int(args.get("predictor", 2)), **({"zstd_level": int(args.get("level", 9))} if codec == "zstd" else {}))
+    write_geotiff(tif, img, (0.2, 0.0, 412000.0, 0.0, -0.2, 5318000.0 + side * 0.2), 25832, compression=codec, tile=(tile, tile), **ckw)
     del img
     tile_data([tif], f"{root}/tiles", buffer=0, tile_width=90, tile_height=90)
     tjson = f"{root}/tiles/324125000.json"
@@ -54,7 +58,7 @@ try:
         os.link(tjson, f"{root}/tiles/{nm}.json")
     sd = make_synthetic_state_dict(int(args.get("depth", 50)), seed=0)
     cfg = T.setup_model_cfg(update_model="synthetic", device="0")
-    res = {"raster": f"{side}x{side}x{bands} uint8 JPEG, {tile}x{tile} tiles", "tiles_per_image": ntiles, "file_bytes": os.path.getsize(tif),
+    res = {"raster": f"{side}x{side}x{bands} uint8 {codec.upper()}, {tile}x{tile} tiles", "tiles_per_image": ntiles, "file_bytes": os.path.getsize(tif),
            "precision": args.get("precision", "fp16"), "device_decode_long_jpeg": long_jpeg}
     outs = {}
     for dd in modes:

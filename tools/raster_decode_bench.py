@@ -1,5 +1,5 @@
 """Decode rate of LZW / DEFLATE / JPEG rasters on the GPU (tiffdecode.hip, jpegdecode.hip): python tools/raster_decode_bench.py
-[codec=lzw|deflate|jpeg] [side=9000] [tile=256|strip=N] [predictor=2] [data=tiles|noise|flat]
+[codec=lzw|deflate|jpeg|zstd [level=9]] [side=9000] [tile=256|strip=N] [predictor=2] [data=tiles|noise|flat]
 JPEG (predictor ignored): [bands=3 | 4 (RGB + near-infrared: four components as stored, subsampling ignored) | 1] [quality=90] [subsampling=2 (4:2:0) | 1 (4:2:2) | 0 (4:4:4)] [layout=complete|gdal] [restart=MCUs]
 [long=1 [subseq=256] [threshold=32768]: a raster with entropy-coded segments above GeoTiff.JPEG_DEVICE_MAX_SEGMENT (no restart markers),
 which otherwise "stays with the host reader", is decoded on the device with a wave per long segment (decode_to_device(long_segments=True));
@@ -11,7 +11,7 @@ call file → pinned → device → decoded raster in HBM, and the kernels alone
 per-kernel durations land in profiles/r06_decode_kernel_stats.csv.
 DEFLATE: the blocks' Adler-32 check is a launch of its own behind the inflate kernel; "inflate_ms" and "checksum_ms" time the two
 separately (HIP events around td_tiff_inflate_dev and around td_tiff_adler32_blocks_dev, the raster's blocks already on the device).
-samples=f32 [codec=deflate|lzw] [side=9000] [tile=256|strip=N] [predictors=1,2,3]: the float32 height raster of the post-processing
+samples=f32 [codec=deflate|lzw|zstd [level=9]] [side=9000] [tile=256|strip=N] [predictors=1,2,3]: the float32 height raster of the post-processing
 stage (a synthetic nDSM, one band) — per predictor one JSON line with the compressed size, the block decoder's launch and the scatter /
 predictor kernel apart (HIP events on the stream they ran on, median of 7 warm runs; the scatter's GB/s counts one read and one
 write of the raster), the wall time from the file to a raster td_crown_stats can read for the device path (decode_to_device +
@@ -70,6 +70,8 @@ def f32_main():
             out.append((time.perf_counter() - t0) * 1e3)
         return out[1:]
 
+    if codec == "zstd":
+        kw["zstd_level"] = int(args.get("level", 9))
     for pred in [int(v) for v in args.get("predictors", "1,2,3").split(",")]:
         try:
             write_geotiff(path, img, (1.0, 0, 412000.0, 0, -1.0, 5318000.0 + side), 25832, compression=codec, predictor=pred, **kw)
@@ -113,6 +115,10 @@ def f32_main():
             if codec == "lzw":
                 decode_ms = timed(lambda: lib.td_tiff_lzw_decode_dev(*head, sp))
                 plain_ms = None
+            elif codec == "zstd":
+                lits = torch.empty((int(lib.td_tiff_zstd_scratch_bytes(nb)),), dtype=torch.uint8, device="cuda")
+                decode_ms = timed(lambda: lib.td_tiff_zstd_decode_dev(*head, lits.data_ptr(), lits.numel(), sp))
+                plain_ms = None
             else:
                 plain_ms = timed(lambda: lib.td_tiff_inflate_dev(*head, sp))
                 decode_ms = timed(lambda: lib.td_tiff_inflate_verified_dev(*head, ends.data_ptr(), sp))
@@ -124,11 +130,11 @@ def f32_main():
             r3 = lambda v: None if v is None else [round(t, 3) for t in v]
             print(json.dumps({"samples": "f32", "codec": codec, "raster": f"{side}x{side}x1", "layout": kw, "predictor": pred, "blocks": nb,
                               "raw_mb": raw / 1e6, "file_mb": os.path.getsize(path) / 1e6,
-                              "inflate_ms" if codec != "lzw" else "lzw_ms": r3(plain_ms if codec != "lzw" else decode_ms),
-                              "inflate_verified_ms": r3(decode_ms) if codec != "lzw" else None,
+                              {"lzw": "lzw_ms", "zstd": "zstd_ms"}.get(codec, "inflate_ms"): r3(plain_ms if plain_ms is not None else decode_ms),
+                              "inflate_verified_ms": r3(decode_ms) if plain_ms is not None else None,
                               "scatter_ms": r3(scatter_ms), "scatter_median_ms": round(median(scatter_ms), 3),
                               "scatter_gb_per_s_read_plus_write": 2 * raw / (median(scatter_ms) * 1e-3) / 1e9,
-                              "decoder_median_ms": round(median(plain_ms if codec != "lzw" else decode_ms), 3),
+                              "decoder_median_ms": round(median(plain_ms if plain_ms is not None else decode_ms), 3),
                               "device_path_wall_ms": r3(device_ms), "device_path_median_ms": round(median(device_ms), 1),
                               "host_block_reader_plus_h2d_ms": r3(host_ms), "host_block_reader_median_ms": round(median(host_ms), 1),
                               "host_pillow_whole_image_plus_h2d_ms": r3(pillow_ms),
@@ -162,6 +168,8 @@ else:
             img[:3, r * 1000:(r + 1) * 1000, c * 1000:(c + 1) * 1000] = t.transpose(2, 0, 1)
             img[3, r * 1000:(r + 1) * 1000, c * 1000:(c + 1) * 1000] = t[..., 1]
     img = np.ascontiguousarray(img[:, :side, :side])
+if codec == "zstd":
+    kw["zstd_level"] = int(args.get("level", 9))
 if codec == "jpeg":
     img, pred = np.ascontiguousarray(img[:int(args.get("bands", 3))]), 1
     kw.update(jpeg_quality=int(args.get("quality", 90)), jpeg_subsampling=int(args.get("subsampling", 2)),
@@ -239,6 +247,78 @@ try:
         extra = {"inflate_ms": [round(t, 3) for t in inflate_ms], "inflate_verified_ms": [round(t, 3) for t in verified_ms],
                  "checksum_ms": [round(t, 3) for t in checksum_ms], "checksum_share_of_inflate": min(checksum_ms) / min(inflate_ms)}
         del comp, meta, blocks, dec, ends, status
+    if codec == "zstd":
+        # the launches apart (the decoder, the scatter / predictor kernel), the host reader on host_threads threads (every block through
+        # GeoTiff._decode_block: td_tiff_zstd_decode + the predictor), and — once — the whole file through Pillow: how such a file was read before
+        from treedetection_amd import _lib
+        lib = _lib.load()
+        offs, cnts = np.asarray(g._offs, dtype=np.int64), np.asarray(g._counts, dtype=np.int64)
+        lo, nb = int(offs.min()), g._nx * g._ny
+        span = int((offs + cnts).max()) - lo
+        cap = g._bw * g._bh * g.count * g.dtype.itemsize
+        comp = torch.zeros((span + 16,), dtype=torch.uint8)
+        comp[:span] = torch.from_numpy(np.fromfile(path, dtype=np.uint8, count=span, offset=lo))
+        comp = comp.cuda()
+        meta = torch.from_numpy(np.stack([offs - lo, cnts])).cuda()
+        blocks = torch.empty((nb, cap), dtype=torch.uint8, device="cuda")
+        dec = torch.empty((nb,), dtype=torch.int64, device="cuda")
+        status = torch.empty((nb,), dtype=torch.int32, device="cuda")
+        lits = torch.empty((int(lib.td_tiff_zstd_scratch_bytes(nb)),), dtype=torch.uint8, device="cuda")
+        image = torch.empty((g.height, g.width, g.count), dtype=torch.uint8, device="cuda")
+        sp = _lib.stream_ptr()
+
+        def timed(fn):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            _lib.check(fn(), "launch")
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1)
+        zstd_ms = [timed(lambda: lib.td_tiff_zstd_decode_dev(comp.data_ptr(), meta[0].data_ptr(), meta[1].data_ptr(), nb, blocks.data_ptr(), cap,
+                                                             dec.data_ptr(), status.data_ptr(), lits.data_ptr(), lits.numel(), sp)) for _ in range(5)]
+        assert int((status != 0).sum()) == 0
+        scatter_ms = [timed(lambda: lib.td_tiff_blocks_to_image_dev(blocks.data_ptr(), cap, g._bw, g._bh, g._nx, g._ny, g.count, g._predictor,
+                                                                    image.data_ptr(), g.width, g.height, sp)) for _ in range(5)]
+        assert np.array_equal(image.cpu().numpy().transpose(2, 0, 1), img)
+        del comp, meta, blocks, dec, status, lits, image
+        nth = int(args.get("host_threads", 16))
+        keys = [(0, by, bx) for by in range(g._ny) for bx in range(g._nx)]
+        host_s, host_decode_s = [], []                             # blocks + stitch + copy / the blocks alone: what the JPEG branch times
+        for k in range(3):
+            h = GeoTiff(path)
+            h._setup_blocks()
+            t0 = time.perf_counter()
+            with ThreadPoolExecutor(max_workers=nth) as hp:
+                blks = list(hp.map(lambda key: h._decode_block(*key), keys))
+            host_decode_s.append(time.perf_counter() - t0)
+            ref = np.empty((side, side, img.shape[0]), np.uint8)
+            for (_, by, bx), blk in zip(keys, blks):
+                r0, c0 = by * h._bh, bx * h._bw
+                piece = blk[:min(blk.shape[0], side - r0), :min(h._bw, side - c0)]
+                ref[r0:r0 + piece.shape[0], c0:c0 + piece.shape[1]] = piece
+            dev_ref = torch.from_numpy(ref).cuda()
+            torch.cuda.synchronize()
+            host_s.append(time.perf_counter() - t0)
+            if k == 0:
+                assert np.array_equal(ref.transpose(2, 0, 1), img), "host reader differs from what was written"
+            del blks, dev_ref
+            h.close()
+        pillow_s = None
+        if args.get("pillow", "1") == "1":
+            from PIL import Image
+            Image.MAX_IMAGE_PIXELS = None
+            t0 = time.perf_counter()
+            try:
+                arr = np.asarray(Image.open(path))
+                torch.from_numpy(np.ascontiguousarray(arr)).cuda()
+                torch.cuda.synchronize()
+                pillow_s = time.perf_counter() - t0
+            except Exception as e:                                  # (whether Pillow's TIFF plugin opens the layout at all)
+                pillow_s = f"failed: {e}"
+        extra = {"level": kw["zstd_level"], "zstd_decode_ms": [round(t, 3) for t in zstd_ms], "scatter_ms": [round(t, 3) for t in scatter_ms],
+                 "host_threads": nth, "host_reader_ms": [round(t * 1e3, 1) for t in host_decode_s],
+                 "host_reader_plus_stitch_plus_h2d_ms": [round(t * 1e3, 1) for t in host_s],
+                 "pillow_whole_file_plus_h2d_ms": round(pillow_s * 1e3, 1) if isinstance(pillow_s, float) else pillow_s}
     if codec == "jpeg":
         # the host reader on the same raster: every block through GeoTiff._decode_block (Pillow's libjpeg) on host_threads threads
         nth = int(args.get("host_threads", 16))

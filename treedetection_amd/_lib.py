@@ -22,6 +22,9 @@ ERR_UNSUPPORTED = -6  # TD_ERR_UNSUPPORTED
 JPEG_TABSET_BYTES = 11904  # TD_JPEG_TABSET_BYTES: one table set of td_tiff_jpeg_plan
 SAMPLE_U8, SAMPLE_F32 = 0, 1                          # TD_SAMPLE_*: source of td_resample_gdal_dev
 RESAMPLE_MODES = {"f32": 0, "u8": 1, "ndvi": 2}       # TD_RESAMPLE_*: its output modes
+ZSTD_STATS = ("frames block_raw block_rle block_comp max_blocks_per_frame lit_raw lit_rle lit_huff lit_treeless lit_streams_1 lit_streams_4 "
+              "hufw_direct hufw_fse seq0 LL_predef LL_rle LL_fse LL_repeat OF_predef OF_rle OF_fse OF_repeat ML_predef ML_rle ML_fse ML_repeat "
+              "window_desc single_segment checksum seq_long seq_2byte skippable").split()   # TD_ZSTD_STATS counters of td_zstd_stream_stats, in order
 RING_PAIR_CAP, RING_PAIR_WPB, RING_PAIR_GRID = 1024, 4, 2048   # ringiou.hip: vertices of a pair in LDS, waves per workgroup, workgroups per launch
 
 
@@ -114,6 +117,11 @@ SIGNATURES = {
     "td_tiff_inflate_verified": (C.c_int64, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
     "td_tiff_inflate_verified_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p]),
+    "td_tiff_zstd_decode": (C.c_int64, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
+    "td_zstd_stream_stats": (C.c_int64, [C.c_void_p, C.c_int64, C.c_void_p]),
+    "td_tiff_zstd_decode_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_int64, C.c_void_p]),
+    "td_tiff_zstd_scratch_bytes": (C.c_int64, [C.c_int]),
     "td_tiff_adler32_blocks_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                              C.c_void_p]),
     "td_adler32_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),

@@ -10,7 +10,7 @@ Optional extra keys (defaults preserve the reference's behaviour): ``precision``
 are at least as many images as ranks, detection.resolve_shard_by), ``eager_stitch`` (true: every image is stitched as soon as
 its tile files are complete, while the next one predicts), ``fp16_min_batch`` (0 = off: a larger batch for the fp16 engine only,
 detection.engine_batch_size), ``device_contours`` ("auto" | true | false: mask borders followed on the GPU while the host epilogue,
-not the GPU, sets the batch period; same files), ``device_decode`` ("auto" | false | "all": LZW, DEFLATE and JPEG rasters decoded on the GPU, tile windows cut
+not the GPU, sets the batch period; same files), ``device_decode`` ("auto" | false | "all": LZW, DEFLATE, ZSTD and JPEG rasters decoded on the GPU, tile windows cut
 in HBM — "all": uncompressed rasters are kept in HBM too; same pixels), ``device_decode_long_jpeg`` (true | false, default false: JPEG
 rasters whose blocks have no restart markers are decoded on the GPU too, a wave per entropy-coded segment; same pixels), ``device_filters`` ("auto" | true | false: the crown stage's
 box-IoU de-duplication and containment pair tests on the GPU, sparse result only — "auto" keeps the host functions; same features),

@@ -3,13 +3,13 @@
 The reference reads rasters through rasterio/GDAL (``rasterio.open`` + ``rasterio.mask.mask(img, shapes, crop=True)``,
 TreeDetection/prediction.py:61,164); neither is installed here. The tile loader needs windowed reads of classic or
 BigTIFF rasters — strips or tiles, pixel-interleaved or planar, 8/16/32-bit integer or float samples, uncompressed or
-DEFLATE (zlib) / LZW / PackBits (td_tiff_*_decode in libtreedet_hip.so), horizontal-differencing predictor — plus the
+DEFLATE (zlib) / LZW / ZSTD / PackBits (td_tiff_*_decode in libtreedet_hip.so), horizontal-differencing predictor — plus the
 three geo tags (ModelPixelScale / ModelTiepoint / GeoKeyDirectory). JPEG-in-TIFF (compression 7, 8-bit, one, three or four bands —
 RGB + near-infrared as GDAL writes it: RGB with one extra sample, four components stored as they are)
 is windowed too: a block's abbreviated stream + the JPEGTables tag form one JPEG stream, decoded by Pillow's libjpeg block by
 block (GDAL does the same through libtiff). The floating-point predictor (predictor 3, TIFF Technical Note 3) of float32 rasters
 is undone block by block (td_tiff_unpredict_float). Other codecs (old-style JPEG, predictor 3 on float64, ...): whole image through Pillow.
-Whole rasters can instead be decoded on the GPU and kept in HBM (``decode_to_device``): LZW and DEFLATE (tiffdecode.hip; uint8 and
+Whole rasters can instead be decoded on the GPU and kept in HBM (``decode_to_device``): LZW, DEFLATE and ZSTD (tiffdecode.hip, zstddecode.hip; uint8 and
 native-order uint16 samples; native-order float32 height rasters, predictors 1 - 3, for callers that ask for them) and sequential-Huffman
 JPEG (jpegdecode.hip, byte-identical to the Pillow path) — see ``device_decodable``.
 """
@@ -174,7 +174,7 @@ class GeoTiff:
         if self.compression == 7 and self._jpeg_blocks_ok():
             tb = bytes(bytearray(int(v) for v in t.get(347, [])))
             self._jpeg_tables = tb if len(tb) >= 4 and tb[:2] == b"\xff\xd8" and tb[-2:] == b"\xff\xd9" else b""
-        elif self.compression not in (1, 5, 8, 32946, 32773) or not (self._predictor in (1, 2) or self._float_predictor()):
+        elif self.compression not in (1, 5, 8, 32946, 32773, 50000) or not (self._predictor in (1, 2) or self._float_predictor()):
             self._pil_fallback()
         self._blocks_ready = True
 
@@ -292,8 +292,11 @@ class GeoTiff:
             lib = _lib.load()
             src = np.ascontiguousarray(raw)
             buf = np.empty(nbytes, dtype=np.uint8)
-            fn = lib.td_tiff_lzw_decode if comp == 5 else lib.td_tiff_packbits_decode
+            fn = {5: lib.td_tiff_lzw_decode, 50000: lib.td_tiff_zstd_decode}.get(comp, lib.td_tiff_packbits_decode)
             n = fn(src.ctypes.data, src.size, buf.ctypes.data, nbytes)
+            if comp == 50000 and n < 0:                    # corrupt, or more than the block's bytes (libtiff would stop reading there: DESIGN.md §7)
+                raise ValueError(f"{self.path}: block ({plane},{by},{bx}) does not decode to its {nbytes} bytes: "
+                                 f"{lib.td_last_error().decode('utf-8', 'replace')}")
             _lib.check(n, "tiff block decode")
             buf = buf[:n]
         if buf.size < nbytes:
@@ -377,11 +380,11 @@ class GeoTiff:
 
     # -- compressed raster → HBM (tiffdecode.hip) --------------------------------------------------------------------------
     def device_decodable(self, float_samples: bool = False, long_segments: bool = False) -> bool:
-        """True when the raster's blocks can be decoded on the GPU: LZW or DEFLATE (zlib) strips or tiles of pixel-interleaved
+        """True when the raster's blocks can be decoded on the GPU: LZW, DEFLATE (zlib) or ZSTD strips or tiles of pixel-interleaved
         uint8 or native-order (little-endian) uint16 samples (<= 4 per pixel), predictor 1 or 2; JPEG (compression 7) grey,
         three-band or four-band blocks when the host plan (td_tiff_jpeg_plan: sequential Huffman, 8-bit, 4:4:4 / 4:2:2 / 4:2:0, four
         components all 1x1 and stored as they are) accepts every one of them. ``float_samples=True`` (the height raster of the post-processing stage; the tile loop never asks) also admits
-        native-order float32 samples in the same LZW / DEFLATE layouts, predictor 1, 2 or 3 (floating-point predictor). Everything
+        native-order float32 samples in the same LZW / DEFLATE / ZSTD layouts, predictor 1, 2 or 3 (floating-point predictor). Everything
         else keeps the host reader: big-endian and planar files, PackBits, int16 / int32 and float64 samples, 12-bit JPEG — and JPEG
         rasters with an entropy-coded segment beyond JPEG_DEVICE_MAX_SEGMENT (blocks without restart markers), unless
         ``long_segments=True``: ``decode_to_device(long_segments=True)`` decodes such segments with a whole wave each."""
@@ -392,7 +395,7 @@ class GeoTiff:
             plan = self._jpeg_plan()
             return plan is not None and (long_segments or int(plan[1][:, 1].max()) <= self.JPEG_DEVICE_MAX_SEGMENT)
         f32 = float_samples and self.dtype.kind == "f" and self.dtype.itemsize == 4 and self.dtype.isnative
-        return (self.compression in (5, 8, 32946) and self.planar == 1 and (self._device_samples() or f32) and 1 <= self.count <= 4
+        return (self.compression in (5, 8, 32946, 50000) and self.planar == 1 and (self._device_samples() or f32) and 1 <= self.count <= 4
                 and self._predictor in ((1, 2, 3) if f32 else (1, 2)) and self._counts is not None and self._pil is None
                 and self._bw * self._bh * self.count * self.dtype.itemsize < (1 << 31))
 
@@ -442,7 +445,7 @@ class GeoTiff:
     def decode_to_device(self, device, stream=None, pinned=None, pool=None, long_segments: bool = False, long_threshold: Optional[int] = None,
                          subseq_bytes: Optional[int] = None):
         """The whole raster decoded in HBM: the compressed blocks are read as they lie in the file (one pread of the span that
-        holds them, into pinned memory), copied to the device once, decoded one wave per block (td_tiff_lzw_decode_dev /
+        holds them, into pinned memory), copied to the device once, decoded one wave per block (td_tiff_lzw_decode_dev / td_tiff_zstd_decode_dev /
         td_tiff_inflate_verified_dev, which also checks every DEFLATE block's Adler-32 trailer as zlib does; JPEG: one lane per
         entropy-coded segment, td_tiff_jpeg_decode_dev, planned once by td_tiff_jpeg_plan) and
         laid out as [height, width, bands] uint8 — or torch.uint16 for 16-bit rasters, torch.float32 for float32 rasters — with
@@ -509,11 +512,17 @@ class GeoTiff:
             blocks = torch.empty((nb, block_cap), dtype=torch.uint8, device=dev)
             decoded = torch.empty((nb,), dtype=torch.int64, device=dev)
             status = torch.empty((2 * nb + 1,), dtype=torch.int32, device=dev)      # [nb] status + scratch of the wide-table pass
-            ends = torch.empty((nb,), dtype=torch.int64, device=dev) if self.compression != 5 else None      # DEFLATE: where each trailer begins
+            ends = torch.empty((nb,), dtype=torch.int64, device=dev) if self.compression in (8, 32946) else None      # DEFLATE: where each trailer begins
+            lits = None
+            if self.compression == 50000:                       # ZSTD: the literal buffers of the resident decoder waves
+                lits = torch.empty((max(int(lib.td_tiff_zstd_scratch_bytes(nb)), 1),), dtype=torch.uint8, device=dev)
             k0.record()
             if self.compression == 5:
                 _lib.check(lib.td_tiff_lzw_decode_dev(comp.data_ptr(), meta[0].data_ptr(), meta[1].data_ptr(), nb, blocks.data_ptr(), block_cap,
                                                       decoded.data_ptr(), status.data_ptr(), st), "td_tiff_lzw_decode_dev")
+            elif self.compression == 50000:
+                _lib.check(lib.td_tiff_zstd_decode_dev(comp.data_ptr(), meta[0].data_ptr(), meta[1].data_ptr(), nb, blocks.data_ptr(), block_cap,
+                                                       decoded.data_ptr(), status.data_ptr(), lits.data_ptr(), lits.numel(), st), "td_tiff_zstd_decode_dev")
             else:
                 _lib.check(lib.td_tiff_inflate_verified_dev(comp.data_ptr(), meta[0].data_ptr(), meta[1].data_ptr(), nb, blocks.data_ptr(), block_cap,
                                                             decoded.data_ptr(), status.data_ptr(), ends.data_ptr(), st), "td_tiff_inflate_verified_dev")
@@ -531,7 +540,7 @@ class GeoTiff:
             st_h.copy_(status[:nb], non_blocking=True)
             copied = torch.cuda.Event(blocking=True)
             copied.record()
-        keep = [pin, comp, meta, blocks, decoded, status, ends]     # alive until check() has run: the kernels read them
+        keep = [pin, comp, meta, blocks, decoded, status, ends, lits]     # alive until check() has run: the kernels read them
 
         def check():
             copied.synchronize()
@@ -542,8 +551,10 @@ class GeoTiff:
             bad = np.nonzero((st_h.numpy() != 0) | (produced != expect))[0]
             if bad.size:
                 b = int(bad[0])
-                if self.compression != 5 and int(st_h[b]) == 3:
+                if self.compression in (8, 32946) and int(st_h[b]) == 3:
                     raise ValueError(f"{self.path}: block {b}: Adler-32 mismatch (status 3): its {int(produced[b])} decoded bytes do not sum to the stream's trailer")
+                if self.compression == 50000 and int(st_h[b]) == 4:
+                    raise ValueError(f"{self.path}: block {b}: declined by the device decoder (status 4): a content checksum, a second frame or a skippable frame")
                 raise ValueError(f"{self.path}: block {b} decodes to {int(produced[b])} bytes (status {int(st_h[b])}), expected {int(expect[b])}")
             return image
         check.event = done
@@ -859,16 +870,62 @@ def _jpeg_split(stream: bytes) -> Tuple[bytes, bytes]:
     return b"".join(tables) + b"\xff\xd9", b"".join(rest)
 
 
+_zstd_compress = None
+
+
+def _libzstd_compressor():
+    """→ compress(raw, level) by libzstd's ZSTD_compress, loaded on first use through ctypes: the system's library, else the copy
+    bundled with Pillow. The writer's only; ValueError when neither loads."""
+    global _zstd_compress
+    if _zstd_compress is not None:
+        return _zstd_compress
+    import ctypes
+    import ctypes.util
+    import glob
+    names = [ctypes.util.find_library("zstd")]
+    try:
+        import PIL
+        names += sorted(glob.glob(os.path.join(os.path.dirname(os.path.dirname(PIL.__file__)), "pillow.libs", "libzstd*.so*")))
+    except ImportError:
+        pass
+    z = None
+    for name in names:
+        try:
+            # (RTLD_DEEPBIND: its internal calls stay inside it whatever other libzstd build the process has in its global scope)
+            z = ctypes.CDLL(name, mode=os.RTLD_LOCAL | os.RTLD_DEEPBIND) if name else None
+            if z is not None and all(hasattr(z, f) for f in ("ZSTD_compress", "ZSTD_compressBound", "ZSTD_isError")):
+                break
+            z = None
+        except OSError:
+            z = None
+    if z is None:
+        raise ValueError("compression='zstd': libzstd was not found (neither a system library nor Pillow's bundled copy loads)")
+    z.ZSTD_compressBound.restype, z.ZSTD_compressBound.argtypes = ctypes.c_size_t, [ctypes.c_size_t]
+    z.ZSTD_isError.restype, z.ZSTD_isError.argtypes = ctypes.c_uint, [ctypes.c_size_t]
+    z.ZSTD_compress.restype = ctypes.c_size_t
+    z.ZSTD_compress.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int]
+
+    def compress(raw: bytes, level: int) -> bytes:
+        out = ctypes.create_string_buffer(z.ZSTD_compressBound(len(raw)))
+        n = z.ZSTD_compress(out, len(out), raw, len(raw), level)
+        if z.ZSTD_isError(n):
+            raise ValueError(f"ZSTD_compress failed at level {level}")
+        return out.raw[:n]
+    _zstd_compress = compress
+    return compress
+
+
 def write_geotiff(path: str, data: np.ndarray, transform: Sequence[float], epsg: int = 25832, *,
                   tile: Optional[Tuple[int, int]] = None, rows_per_strip: Optional[int] = None,
                   compression: Optional[str] = None, predictor: int = 1, planar: bool = False,
                   nodata: Optional[float] = None, jpeg_tables: bool = False, jpeg_restart: int = 0,
-                  jpeg_quality: int = 90, jpeg_subsampling: int = 2) -> None:
+                  jpeg_quality: int = 90, jpeg_subsampling: int = 2, zstd_level: int = 9) -> None:
     """Classic little-endian TIFF with the GeoTIFF tags the reader understands. data: [bands, rows, cols] or
     [rows, cols]; uint8 / uint16 / float32. Defaults: one uncompressed pixel-interleaved strip (what the tile reader
     maps without copying). Options: ``tile=(tile_rows, tile_cols)`` (multiples of 16) or ``rows_per_strip``,
     ``compression`` None / "deflate" / "lzw" (td_tiff_lzw_encode, blocks encoded on host threads) / "jpeg" (lossy; Pillow's encoder per
-    block), ``predictor`` 1 / 2 (horizontal differencing; float32 samples are differenced as uint32, modulo 2^32, which is what libtiff's
+    block) / "zstd" (test rasters and the bench only: libzstd's one-shot ZSTD_compress at ``zstd_level`` through ctypes, the system's
+    library or the copy bundled with Pillow; ValueError when neither loads — the reader never touches libzstd), ``predictor`` 1 / 2 (horizontal differencing; float32 samples are differenced as uint32, modulo 2^32, which is what libtiff's
     32-bit accumulator undoes) / 3 (floating-point predictor, TIFF Technical Note 3: float32 only), ``planar`` (one block grid per band). JPEG: ``jpeg_tables`` writes the GDAL / libtiff
     layout (the quantisation and Huffman tables once, in the JPEGTables tag; abbreviated blocks without JFIF) instead of complete
     streams; ``jpeg_restart`` > 0 puts a restart marker every that many MCUs; ``jpeg_quality``, ``jpeg_subsampling`` (2 = 4:2:0,
@@ -879,8 +936,8 @@ def write_geotiff(path: str, data: np.ndarray, transform: Sequence[float], epsg:
         arr = arr[None]
     C, H, W = arr.shape
     fmt = {np.dtype(np.uint8): (1, 8), np.dtype(np.uint16): (1, 16), np.dtype(np.float32): (3, 32)}[arr.dtype]
-    if compression not in (None, "deflate", "lzw", "jpeg"):
-        raise ValueError("compression must be None, 'deflate', 'lzw' or 'jpeg'")
+    if compression not in (None, "deflate", "lzw", "jpeg", "zstd"):
+        raise ValueError("compression must be None, 'deflate', 'lzw', 'jpeg' or 'zstd'")
     if predictor not in (1, 2, 3):
         raise ValueError("predictor must be 1, 2 or 3")
     if predictor == 3 and fmt != (3, 32):
@@ -938,6 +995,9 @@ def write_geotiff(path: str, data: np.ndarray, transform: Sequence[float], epsg:
             return dst[:n].tobytes()
         with ThreadPoolExecutor(max_workers=max(1, min(16, len(os.sched_getaffinity(0))))) as ex:
             blocks = list(ex.map(enc, blocks))
+    if compression == "zstd":
+        compress = _libzstd_compressor()
+        blocks = [compress(raw, int(zstd_level)) for raw in blocks]
     a, _, c, _, e, f = (float(v) for v in transform[:6])
     entries = []   # (tag, type, count, payload bytes)
 
@@ -952,7 +1012,7 @@ def write_geotiff(path: str, data: np.ndarray, transform: Sequence[float], epsg:
     add(256, 4, [W])
     add(257, 4, [H])
     add(258, 3, [fmt[1]] * C)
-    add(259, 3, [{"deflate": 8, "lzw": 5, "jpeg": 7}.get(compression, 1)])
+    add(259, 3, [{"deflate": 8, "lzw": 5, "jpeg": 7, "zstd": 50000}.get(compression, 1)])
     add(262, 3, [(6 if compression == "jpeg" and C == 3 else 2) if C >= 3 else 1])
     add(277, 3, [C])
     add(284, 3, [2 if planar else 1])

@@ -454,7 +454,7 @@ def _height_on_device(hg: GeoTiff, h_scale: float, config, device: int):
     """The height raster decoded in HBM (GeoTiff.decode_to_device → float32 CUDA tensor [rows, cols], which td_crown_stats reads
     where it lies: no inflate on the host, no copy of the array) and, when ``height_scaling_factor`` shrinks it, decimated there
     (:func:`resample_on_device`, mode "f32"); or None when the host reader has to serve it: ``device_decode``
-    is not explicitly true / "all" (the default "auto" keeps the host reader for this raster: DESIGN.md §7), the raster is not a single-band native float32 LZW / DEFLATE raster (``device_decodable(float_samples=True)``), the
+    is not explicitly true / "all" (the default "auto" keeps the host reader for this raster: DESIGN.md §7), the raster is not a single-band native float32 LZW / DEFLATE / ZSTD raster (``device_decodable(float_samples=True)``), the
     scaling factor enlarges it (a factor above 1 stays host numpy), or a block turns out corrupt (printed, like the prediction stage)."""
     if not _device_decode_on(config):
         return None

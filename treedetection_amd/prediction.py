@@ -376,7 +376,7 @@ class Predictor:
 
     # -- compressed rasters decoded on the GPU -------------------------------------------------------------------
     def prefetch(self, tifpath) -> None:
-        """Starts, on a thread of its own, what the NEXT image needs before its first batch can be cut: an LZW, DEFLATE or JPEG raster's
+        """Starts, on a thread of its own, what the NEXT image needs before its first batch can be cut: an LZW, DEFLATE, ZSTD or JPEG raster's
         compressed blocks read into pinned memory, copied to the device and decoded there (GeoTiff.decode_to_device), or an uncompressed
         raster's bytes copied to the device in large sequential pieces (GeoTiff.upload_to_device) — while the current image
         predicts. ``detection.walk_images`` calls it with the path after the one it submits. uint8 and little-endian uint16 rasters
