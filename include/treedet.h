@@ -261,6 +261,23 @@ td_status td_conv2d_winograd_nhwc(const float* x, const float* w, const float* s
  * Bit-identical to td_conv2d_winograd_nhwc (TD_WINO_TILE=4) followed by a 1x1 td_conv2d_nhwc. */
 td_status td_conv2d_winograd_head_nhwc(const float* x, const float* w, const float* bias, const float* head_w, const float* head_b,
                                        float* head_y, int B, int H, int W, int Cin, int head_n, void* stream);
+/* Diagnostic (tests, tools; host only, needs no engine and no GPU): which form the engine gives one convolution of the forward —
+ * the one rule its every contraction asks. The forms differ in rounding, so the answer depends on the layer's own shape and the
+ * rules only, never on the batch or a timing.
+ *   rules[8]  = precision, winograd, wino_fused, wino_minc, wino43_min, wino_fold, wino_slab, fuse_head (the engine's defaults for
+ *               TD_PRECISION_FP32: 0, 1, 1, 128, 12, 39, 0, 1); a negative entry after the precision = what an engine created
+ *               now would use, its default or the TD_* diagnostic switch of the environment. wino_elems = floats in each
+ *               Winograd workspace plane (td_engine_reserve: 16 x the largest [tiles of 2x2 outputs] x [channels] of the 3x3
+ *               layers, which never runs short for the engine's own layers; 0 for the fp16 engine)
+ *   layer[9]  = cout, cin, kh, kw, has a scale, writes float32, and which banks it has: F(2x2) filters, F(4x4) filters, split-bf16
+ *   call[10]  = B, H, W, stride, pad, relu, has a residual, out_mode, device-side row count, rows_mul
+ *   head[9]   = the same facts of a 1x1 layer that is this layer's only consumer, or NULL
+ *   out[10]   = form (0 direct, 1 split-bf16, 2 Winograd F(2x2), 3 F(4x4) in three launches, 4 F(4x4) folded),
+ *               head (0 a launch of its own, 1 inside the F(4x4) output transform, 2 inside the direct launch if the measured tile
+ *               owns all 256 output channels), 1 if a block tile is measured for the form, the five fields of its tune key
+ *               (TD_TUNE_CACHE lines: cout, cin, kh*16+kw, rows, flags), tiles per F(2x2) slab, images per fold group */
+td_status td_conv_path(const int32_t* rules, int64_t wino_elems, const int32_t* layer, const int32_t* call, const int32_t* head,
+                       int32_t* out);
 /* Greedy NMS of n boxes (dev [n,4], scores dev [n]); keep_idx dev int32 [n] receives the kept
  * indices in descending-score order (ties: lower index first), *keep_count (dev) their number. */
 td_status td_nms(const float* boxes, const float* scores, int n, float iou_thresh, int32_t* keep_idx,

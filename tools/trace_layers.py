@@ -1,7 +1,10 @@
 """Per-layer view of a rocprofv3 --kernel-trace CSV of bench.py: pairs the conv_igemm launches of the LAST forward
 with the engine's layer schedule (R50/R101, B x Hp x Wp) and prints GFLOP, µs and TFLOP/s per launch."""
 import csv
+import os
 import sys
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))      # treedetection_amd._lib: the engine's path rule
 
 
 def schedule(depth=50, B=8, Hp=800, Wp=800, P=1000, fp32=False, fuse_tail=True, fused_heads=(), grouped=False):
@@ -50,32 +53,30 @@ def schedule(depth=50, B=8, Hp=800, Wp=800, P=1000, fp32=False, fuse_tail=True, 
     return L
 
 
-def launches_of(name, M, N, K, fp32, B=8, min43=12):
-    """fp32 engine (engine.cpp run_conv): 3x3 stride-1 layers with >= 128 channels on both sides take a Winograd path —
-    F(4x4,3x3) on maps of at least `min43` pixels a side: three launches (wino43_input_kernel, the batched conv_igemm launch,
-    wino43_output_kernel); F(2x2,3x3) otherwise: two (wino_gemm_kernel + wino_output_kernel). → (launch count, label)"""
+def conv3x3_path(N, cin, B, side, dyn=False, head=False, relu=True):
+    """What the fp32 engine's path rule (td_conv_path: csrc/conv_path.h) answers for a 3x3 / stride 1 / pad 1 layer cin -> N on
+    B maps of side x side, under the engine's defaults and the TD_* switches of this environment. The layer is given every
+    filter bank the rule lets it use and a workspace with room (td_engine_reserve's never runs short for the engine's own layers)."""
+    from treedetection_amd import _lib
+    return _lib.conv_path([0] + [-1] * 7, 1 << 62, [N, cin, 3, 3, 0, 0, 1, 1, 0], [B, side, side, 1, 1, int(relu), 0, 0, int(dyn), side * side],
+                          [15, N, 1, 1, 0, 1, 0, 0, 0] if head else None)
+
+
+def launches_of(name, M, N, K, fp32, B=8):
+    """Launches of one schedule entry. fp32 engine: a 3x3 stride-1 layer may take a Winograd form — F(4x4,3x3) in three launches
+    (wino43_input_kernel, the batched plane contraction, wino43_output_kernel), folded in two (wino43_input_kernel +
+    wino43_fused_kernel), or F(2x2,3x3) in two (wino_gemm_kernel + wino_output_kernel). → (launch count, label)"""
     three = ("conv2" in name or "fpn_output" in name or "rpn_conv" in name or "mask_fcn" in name)
-    if not (fp32 and three and N >= 128 and K // 9 >= 128):
+    if not (fp32 and three):
         return 1, None
-    side = int(round((M / B) ** 0.5)) if M else 14          # M = 0: the mask head's 14 x 14 RoIs (device-side row count)
-    if min43 > 0 and side >= min43:
-        # round 4: the fold rule of engine.cpp (TD_WINO_FOLD, default 7): never the RPN layers (their head rides in the three-launch
-        # form's output transform); 256 channels from 80 x 80, 128 channels from 80 x 80, the mask head → input transform + wino43_fused_kernel
-        import os
-        wf = int(os.environ.get("TD_WINO_FOLD", "39"))
-        cin = K // 9
-        rpn_fold = "rpn_conv p" in name and (wf & 1) and (wf & 32) and cin == 256 and side >= 160      # head as a launch of its own
-        fold = rpn_fold or "rpn" not in name and (((wf & 1) and M and ((cin == 256 and side >= 160) or (cin == 128 and side >= 80))) or ((wf & 2) and not M) or
-                                      ((wf & 4) and M and cin == 256 and side >= 80) or ((wf & 8) and M and side >= 40) or ((wf & 16) and M))
-        if fold and cin in (128, 256, 512) and N % 64 == 0:
-            return 2, "winograd F(4x4) folded"
-        return 3, "winograd F(4x4)"
-    return 2, "winograd F(2x2)"
+    # M = 0: the mask head's 14 x 14 RoIs (device-side row count over the reserved 100 per image)
+    side, nb = (int(round((M / B) ** 0.5)), B) if M else (14, B * 100)
+    form = conv3x3_path(N, K // 9, nb, side, dyn=not M, head="rpn_conv" in name, relu="fpn_output" not in name)["form"]
+    return {"winograd F(4x4)": 3, "winograd F(4x4) folded": 2, "winograd F(2x2)": 2}.get(form, 1), form if "winograd" in form else None
 
 
-def main(path, depth=50, fp32=False):
-    import os
-    min43 = int(os.environ.get("TD_WINO43_MIN", "12"))
+def main(path, depth=50, fp32=False, B=8, size=800):
+    """B images of size x size (padded network input; square: launches_of reads a map's side off its row count)"""
     fam = ("conv_igemm", "conv_pp8", "plane_gemm", "wino_gemm", "wino_output", "wino_input", "wino43_input", "wino43_output", "wino43_fused", "bottleneck_tail", "conv_sk", "conv_bd", "conv_bs", "conv_split")
     # launch order = start order on the one stream of the plain loop (the CSV itself is not written in that order)
     rows = sorted(csv.DictReader(open(path)), key=lambda r: int(r["Start_Timestamp"]))
@@ -95,20 +96,19 @@ def main(path, depth=50, fp32=False):
             else:
                 fused_heads.add(l)
                 i -= 1
-    if fp32 and os.environ.get("TD_FUSE_HEAD", "1") != "0":
-        # fp32 engine: a fixed rule — every RPN level that takes the F(4x4) path carries its head in the output transform
-        hs = [800 >> (l + 2) for l in range(4)]
+    if fp32:
+        # fp32 engine: where the head goes is the path rule's answer (a fixed rule on the level's shape)
+        hs = [size >> (l + 2) for l in range(4)]
         hs.append((hs[3] - 1) // 2 + 1)
-        wf = int(os.environ.get("TD_WINO_FOLD", "39"))
-        fused_heads = {l for l in range(5) if min43 > 0 and hs[l] >= min43 and not ((wf & 1) and (wf & 32) and hs[l] >= 160)}
-    L = schedule(depth, fp32=fp32, fuse_tail=fuse_tail, fused_heads=fused_heads, grouped=grouped)
-    need = sum(launches_of(e[0], e[1], e[2], e[3], fp32, 8, min43)[0] for e in L)
+        fused_heads = {l for l in range(5) if conv3x3_path(256, 256, B, hs[l], head=True)["head"] == "in the output transform"}
+    L = schedule(depth, B, size, size, fp32=fp32, fuse_tail=fuse_tail, fused_heads=fused_heads, grouped=grouped)
+    need = sum(launches_of(e[0], e[1], e[2], e[3], fp32, B)[0] for e in L)
     last = rows[-need:]
     tot_f = tot_t = 0.0
     i = 0
     for ent in L:
         name, M, N, K = ent[:4]
-        k, label = launches_of(name, M, N, K, fp32, 8, min43)
+        k, label = launches_of(name, M, N, K, fp32, B)
         rs = last[i:i + k]
         i += k
         ts = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rs]
@@ -140,4 +140,5 @@ def main(path, depth=50, fp32=False):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1], int(sys.argv[2]) if len(sys.argv) > 2 else 50, len(sys.argv) > 3 and sys.argv[3] == "fp32")
+    # trace.csv [depth] [fp32|fp16] [batch] [size]
+    main(sys.argv[1], int(sys.argv[2]) if len(sys.argv) > 2 else 50, len(sys.argv) > 3 and sys.argv[3] == "fp32", *map(int, sys.argv[4:6]))

@@ -84,6 +84,8 @@ SIGNATURES = {
     "td_conv2d_head_nhwc": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 9 + [C.c_void_p]),
     "td_conv2d_winograd_head_nhwc": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 5 + [C.c_void_p]),
     "td_conv2d_winograd_nhwc": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 6 + [C.c_void_p]),
+    "td_conv_path": (C.c_int, [C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                               C.POINTER(C.c_int32)]),
     "td_nms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "td_roi_align": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_int,
                                C.c_void_p, C.c_int, C.c_void_p]),
@@ -196,6 +198,21 @@ def check(status: int, what: str = "") -> None:
     if status < 0:
         msg = load().td_last_error().decode("utf-8", "replace")
         raise TdError(f"{what or 'libtreedet_hip'} failed ({status}): {msg}")
+
+
+CONV_FORMS = ("direct", "split", "winograd F(2x2)", "winograd F(4x4)", "winograd F(4x4) folded")   # ConvForm (csrc/conv_path.h), in order
+CONV_HEADS = ("own launch", "in the output transform", "if the tile owns 256 channels")            # ConvHead, in order
+
+
+def conv_path(rules, wino_elems, layer, call, head=None) -> dict:
+    """td_conv_path (include/treedet.h) on integer sequences: which form the engine gives one convolution. No engine, no GPU.
+    → {"form", "head" (names above), "key" (the tune-key tuple, or None when nothing is measured), "slab_tiles", "fold_group"}"""
+    arr = lambda v, n: (C.c_int32 * n)(*[int(x) for x in v])
+    out = (C.c_int32 * 10)()
+    check(load().td_conv_path(arr(rules, 8), int(wino_elems), arr(layer, 9), arr(call, 10), arr(head, 9) if head is not None else None, out),
+          "td_conv_path")
+    return {"form": CONV_FORMS[out[0]], "head": CONV_HEADS[out[1]], "key": tuple(out[3:8]) if out[2] else None,
+            "slab_tiles": out[8], "fold_group": out[9]}
 
 
 def stream_ptr() -> int:

@@ -186,32 +186,16 @@ static td_status wino_api(const float* x, const float* w, const float* scale, co
     const bool fold = f43 && !head_w && folde && atoi(folde) != 0;
     if (fold) TD_REQUIRE(wino43_fused_ok(B, H, W, Cin, Cout), "td_conv2d_winograd_nhwc: TD_WINO_FOLD needs Cin %% 128 == 0, Cout %% 64 == 0");
     const char* fenv = getenv("TD_WINO_FUSED");           // tests compare the two forms of the contraction (bit-identical)
-    const bool fused = !f43 && (!fenv || atoi(fenv) != 0);
-    ConvArgs a{};
-    a.w = U; a.y = Mb;
-    a.Cin = Cin; a.Cout = Cout; a.KH = a.KW = 1; a.stride = 1; a.pad = 0;
-    a.M = (int)T; a.m_mul = 1; a.tile_cfg = -1;
-    a.w_bs = (long long)Cout * Cin; a.y_bs = (long long)T * Cout;
-    if (fused) {
-        a.x = x; a.B = B; a.H = H; a.W = W;
-        st = wino_gemm_launch(a, s);
-    } else {
-        st = f43 ? wino43_input_launch(x, B, H, W, Cin, static_cast<float*>(V), nullptr, s)
-                 : wino_input_launch(x, B, H, W, Cin, static_cast<float*>(V), nullptr, 1, 0, (int)T, s);
-        if (st == TD_OK && fold) {
-            st = wino43_fused_launch(static_cast<float*>(V), static_cast<float*>(U), B, H, W, Cin, Cout, scale, bias, relu, y, nullptr, s);
-        } else if (st == TD_OK) {
-            a.x = V; a.B = 1; a.H = 1; a.W = (int)T; a.Ho = 1; a.Wo = (int)T;
-            a.batch_count = P; a.x_bs = (long long)T * Cin;
-            st = conv2d_launch(a, TD_PRECISION_FP32, s);
-        }
-    }
-    if (fold) {
-    } else if (st == TD_OK && head_w)
-        st = wino43_output_head_launch(static_cast<float*>(Mb), B, H, W, Cout, scale, bias, relu, head_w, head_b, head_y, head_n, s);
-    else if (st == TD_OK)
-        st = f43 ? wino43_output_launch(static_cast<float*>(Mb), B, H, W, Cout, scale, bias, relu, y, nullptr, s)
-                 : wino_output_launch(static_cast<float*>(Mb), B, H, W, Cout, scale, bias, relu, y, nullptr, 1, 0, (int)T, s);
+    // the sequence the engine runs (wino_seq.cpp): the whole layer as one slab / the whole batch as one fold group, heuristic tile
+    WinoRun r{};
+    r.form = fold ? CONV_WINO43_FOLD : f43 ? CONV_WINO43 : CONV_WINO22;
+    r.fused_input = !fenv || atoi(fenv) != 0;
+    r.slab_tiles = (int)T; r.fold_group = B;
+    r.x = x; r.U = static_cast<float*>(U); r.scale = scale; r.bias = bias; r.y = y;
+    r.B = B; r.H = H; r.W = W; r.cin = Cin; r.cout = Cout; r.relu = relu;
+    r.V = static_cast<float*>(V); r.M = static_cast<float*>(Mb); r.m_mul = 1; r.gemm_cfg = -1;
+    r.head_w = head_w; r.head_b = head_b; r.head_y = head_y; r.head_n = head_n;
+    st = wino_run(r, s);
     hipError_t herr = hipStreamSynchronize(s);
     (void)hipFree(U); (void)hipFree(V); (void)hipFree(Mb);
     if (st < 0) return st;

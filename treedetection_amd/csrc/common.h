@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <cstddef>
 #include "../../include/treedet.h"
+#include "conv_path.h"
 #include <string>
 #include <vector>
 
@@ -199,8 +200,8 @@ void wino_filter_transform(const float* w_ohwi, int N, int C, float* U);     // 
 // (m_dyn: optional device-side image count <= B, the mask head's live RoIs)
 td_status wino43_input_launch(const float* x, int B, int H, int W, int C, float* V, const int* m_dyn, hipStream_t s);
 // F(4x4,3x3) contraction + output transform in ONE launch (wino_fused.hip): V [36][T][C] x U [36][N][C] → y, the M planes never
-// reach memory. Another association of the transform sums than wino43_output_launch: a fixed rule picks the layers (engine.cpp).
-bool wino43_fused_ok(int B, int H, int W, int C, int N);
+// reach memory. Another association of the transform sums than wino43_output_launch: a fixed rule picks the layers (conv_path.h,
+// which also declares wino43_fused_ok, the shapes it runs).
 td_status wino43_fused_launch(const float* V, const float* U, int B, int H, int W, int C, int N, const float* scale, const float* bias,
                               int relu, float* y, const int* m_dyn, hipStream_t s);
 td_status wino43_output_launch(const float* Mb, int B, int H, int W, int N, const float* scale, const float* bias, int relu,
@@ -210,6 +211,35 @@ td_status wino43_output_launch(const float* Mb, int B, int H, int W, int N, cons
 td_status wino43_output_head_launch(const float* Mb, int B, int H, int W, int N, const float* scale, const float* bias, int relu,
                                     const float* head_w, const float* head_b, float* head_y, int head_n, hipStream_t s);
 void wino43_filter_transform(const float* w_ohwi, int N, int C, float* U);   // host: U [36][N][C]
+// ---- the Winograd launch sequences of one layer (wino_seq.cpp), each written once over the entries above: F(2x2) with the input
+// transform fused into the contraction or per slab, F(4x4) in three launches, with the head in its output transform, or folded
+struct WinoRun {
+    int form;                  // CONV_WINO22 / CONV_WINO43 / CONV_WINO43_FOLD (conv_path.h)
+    bool fused_input;          // F(2x2): wino_gemm_kernel transforms the input in its A staging, V never exists in memory
+    int slab_tiles;            // F(2x2): tiles per slab
+    int fold_group;            // folded F(4x4): images per launch pair
+    const float *x, *U, *scale, *bias;      // U: the layer's filter bank of the form, [16] or [36][cout][cin]
+    float* y;
+    int B, H, W, cin, cout, relu;
+    float *V, *M;              // workspace planes
+    const int* m_dyn;          // optional device-side count (rows for F(2x2) with m_mul rows per image, images for F(4x4))
+    int m_mul;
+    int gemm_cfg;              // block tile of the batched plane contraction (-1 = heuristic)
+    const float *head_w, *head_b;           // F(4x4) in three launches only: the 1x1 head in the output transform, y is not written
+    float* head_y;
+    int head_n;
+};
+ConvArgs wino_plane_args(const WinoRun& r, int n, long long t0);      // what the tuner times: the launch shapes of the plane contractions
+ConvArgs wino43_plane_args(const WinoRun& r);
+// Optional books of a caller around every launch (the engine's profiling): n = tiles of the slab (F(2x2)) or images of the launch
+// (F(4x4)). A null hook costs a null check per launch.
+enum { WINO_STEP_INPUT, WINO_STEP_GEMM, WINO_STEP_OUTPUT };
+struct WinoHook {
+    void* ctx;
+    void (*begin)(void* ctx, int step, long long n);
+    void (*end)(void* ctx);
+};
+td_status wino_run(const WinoRun& r, hipStream_t s, const WinoHook* hook = nullptr);
 
 // ---- stem / pooling / resize (stem.hip) ---------------------------------------------------------
 struct ImgSizes {           // per-image valid sizes, passed by value (B <= TD_MAX_BATCH)

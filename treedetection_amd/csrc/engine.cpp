@@ -116,11 +116,12 @@ struct td_engine {
 
     std::map<std::string, NamedTensor> named;
 
-    // measured block-tile choice per (layer weights, rows, stride): filled lazily by the first forward of a shape
-    bool autotune = true;
     int backbone_subbatch = 0;    // 0 = whole batch; else images per backbone pass (TD_BACKBONE_SUBBATCH)
-    // key: (cout, cin, kh*16+kw, rows, stride*4 + out_mode*2 + has_residual) — layers of identical shape share it
+    // measured block-tile choice per launch shape, filled lazily by the first forward of a shape; key (ConvPath::key): (cout, cin,
+    // kh*16+kw, rows, stride*4 + out_mode*2 + has_residual + flag) — layers of identical shape share it
     std::map<std::tuple<int, int, int, int, int>, int> tuned;
+    // winograd, wino_fused, wino_slab, wino_minc, wino43_min, wino_fold and fuse_head below, with the precision and wino_elems, are
+    // the rules of conv_path (conv_path.h): which form a layer takes is that function's answer and nothing else's.
     bool winograd = true;         // TD_WINOGRAD=0 disables the Winograd path (diagnostics)
     float *wino_v = nullptr, *wino_m = nullptr;
     size_t wino_elems = 0;
@@ -129,7 +130,11 @@ struct td_engine {
     bool fuse_tail = true;        // TD_FUSE_TAIL=0: conv2 / conv3 of res2 as two launches (diagnostics, tests); 2: fuse the fp16 engine's res3 too
     bool fuse_tail_fp16 = false;
     bool wino_fused = true;       // TD_WINO_FUSED=0: separate input-transform kernel + batched conv_igemm launch (diagnostics)
-    int wino_slab = 0;            // TD_WINO_SLAB: tiles per slab (diagnostics); 0 = sized for the Infinity Cache
+    // TD_WINO_SLAB: tiles per F(2x2) slab (diagnostics). A layer can be walked in slabs of tiles whose V and M planes would stay inside
+    // the 256 MiB Infinity Cache; measured on the bench (round 2, fp32, 3 batches in flight): 4096-tile slabs 425 tiles/s, 8192 441,
+    // whole layers 456 — the shorter launches lose more to their tails and boundaries than the on-die hand-over of V / M saves, so
+    // the default (0) is one slab = the whole layer.
+    int wino_slab = 0;
     int wino_minc = 128;          // fewest channels (both sides) of a 3x3 layer on the Winograd path (TD_WINO_MINC: experiments)
     int wino43_min = 12;          // maps at least this large on both sides take F(4x4,3x3) (TD_WINO43_MIN; 0 = never)
     // F(4x4) layers whose plane contractions and output transform run as ONE launch (wino43_fused_kernel: the M planes never reach
@@ -139,11 +144,11 @@ struct td_engine {
     // on 100 x 100 (res3 conv2) 103 -> 95 us; it loses where its 64-tile x 64-channel blocks cannot fill the chip (res4 / res5,
     // p3 - p6: 88 - 316 blocks on 256 CUs) and on the RPN layers, whose head rides in the three-launch form's output transform.
     // TD_WINO_FOLD (bit mask): 1 = 256 channels from 160 x 160 and 128 channels from 80 x 80 (isolated winners), 2 = the mask head
-    // (device-side RoI count), 4 = 256-channel maps from 80 x 80 (FPN output 3) — the default 7: with three forwards in flight the
-    // fold also pays where its isolated time ties, it frees HBM bandwidth for the other streams (bench, fp32 tiles/s: 0 → 638,
-    // 1 → 650, 3 → 655, 7 → 656) —, 8 = every map from 40 x 40 and 16 = every layer the kernel can run: 660 - 661 under the
-    // stream schedule but 574 → 545 one forward at a time (88-block launches on 256 CUs), not taken.
-    // 32 = the RPN conv on the 160 x 160+ maps folds too (its head becomes a launch of its own).
+    // (device-side RoI count), 4 = 256-channel maps from 80 x 80 (FPN output 3): with three forwards in flight the fold also pays
+    // where its isolated time ties, it frees HBM bandwidth for the other streams (bench, fp32 tiles/s: 0 → 638, 1 → 650, 3 → 655,
+    // 7 → 656) —, 8 = every map from 40 x 40 and 16 = every layer the kernel can run: 660 - 661 under the stream schedule but
+    // 574 → 545 one forward at a time (88-block launches on 256 CUs), not taken.
+    // 32 = the RPN conv on the 160 x 160+ maps folds too (its head becomes a launch of its own). The default is 39 = 1 + 2 + 4 + 32.
     int wino_fold = 39;
     // fp32 engine: the 1x1 / FC layers that run on the bf16 matrix cores with both operands as three bf16 pieces (conv_split.hip:
     // its own rounding, so a FIXED rule on the layer — its place in the network and K >= 256 —, never a timing). Bit mask of layer
@@ -322,16 +327,7 @@ td_status bn_fold(const TensorMap& tm, const std::string& p, int c, std::vector<
     return TD_OK;
 }
 
-// Tiles per Winograd slab. A layer can be walked in slabs of tiles whose V and M planes would stay inside the 256 MiB
-// Infinity Cache (TD_WINO_SLAB = tiles per slab); measured on the bench (round 2, fp32, 3 batches in flight): 4096-tile
-// slabs 425 tiles/s, 8192 441, whole layers 456 — the shorter launches lose more to their tails and boundaries than the
-// on-die hand-over of V / M saves, so the default is one slab = the whole layer.
-int wino_slab_tiles(const td_engine* e, const ConvLayer& L) {
-    (void)L;
-    return e->wino_slab > 0 ? e->wino_slab : (1 << 30);
-}
-
-// fp32 engine: Winograd F(2x2,3x3) filter bank of a 3x3 layer (used where the engine measures it faster, run_conv)
+// fp32 engine: the Winograd filter banks of a 3x3 layer (which form uses them where: conv_path)
 td_status upload_wino(td_engine* e, const std::vector<float>& w_ohwi, ConvLayer& L) {
     L.wino_u = nullptr;
     if (e->desc.precision != TD_PRECISION_FP32 || !e->winograd || L.kh != 3 || L.kw != 3 || L.cin % 32 != 0 || L.cout % 4 != 0)
@@ -481,6 +477,21 @@ void free_pool(std::vector<void*>& pool) {
     pool.clear();
 }
 
+// The diagnostic switches on the rules of conv_path (an engine reads them once, at creation)
+void read_rule_switches(td_engine* e) {
+    if (const char* wg = getenv("TD_WINOGRAD")) e->winograd = atoi(wg) != 0;
+    if (const char* ws = getenv("TD_WINO_SLAB")) e->wino_slab = atoi(ws);
+    if (const char* wf = getenv("TD_WINO_FUSED")) e->wino_fused = atoi(wf) != 0;
+    if (const char* fh = getenv("TD_FUSE_HEAD")) e->fuse_head = atoi(fh) != 0;
+    if (const char* w4 = getenv("TD_WINO43_MIN")) e->wino43_min = atoi(w4);
+    if (const char* wf2 = getenv("TD_WINO_FOLD")) e->wino_fold = atoi(wf2);
+    if (const char* wc = getenv("TD_WINO_MINC")) e->wino_minc = atoi(wc);
+}
+
+ConvRules conv_rules(const td_engine* e) {
+    return {e->desc.precision, e->winograd, e->wino_fused, e->wino_minc, e->wino43_min, e->wino_fold, e->wino_slab, e->fuse_head, e->wino_elems};
+}
+
 }  // namespace
 
 extern "C" {
@@ -501,17 +512,11 @@ td_status td_engine_create(const td_model_desc* desc, int device, td_engine** ou
     td_engine* e = new td_engine();
     if (const char* sbenv = getenv("TD_BACKBONE_SUBBATCH")) e->backbone_subbatch = atoi(sbenv);
     if (const char* tc = getenv("TD_TUNE_CACHE")) e->tune_cache = tc;
-    if (const char* wg = getenv("TD_WINOGRAD")) e->winograd = atoi(wg) != 0;
-    if (const char* ws = getenv("TD_WINO_SLAB")) e->wino_slab = atoi(ws);
-    if (const char* wf = getenv("TD_WINO_FUSED")) e->wino_fused = atoi(wf) != 0;
-    if (const char* fh = getenv("TD_FUSE_HEAD")) e->fuse_head = atoi(fh) != 0;
     if (const char* gl = getenv("TD_GROUP_LEVELS")) e->group_levels = atoi(gl) != 0;
     if (const char* ft = getenv("TD_FUSE_TAIL")) { e->fuse_tail = atoi(ft) != 0; e->fuse_tail_fp16 = atoi(ft) == 2; }
-    if (const char* w4 = getenv("TD_WINO43_MIN")) e->wino43_min = atoi(w4);
-    if (const char* wf2 = getenv("TD_WINO_FOLD")) e->wino_fold = atoi(wf2);
-    if (const char* wc = getenv("TD_WINO_MINC")) e->wino_minc = atoi(wc);
     if (const char* sp = getenv("TD_F32_SPLIT")) e->f32_split = atoi(sp);
     e->desc = d;
+    read_rule_switches(e);
     load_tune_cache(e);
     e->device = device;
     *out = e;
@@ -530,6 +535,31 @@ void td_engine_destroy(td_engine* e) {
     for (auto ev : e->phase_ev) if (ev) (void)hipEventDestroy(ev);
     if (e->prev5_ev) (void)hipEventDestroy(e->prev5_ev);
     delete e;
+}
+
+td_status td_conv_path(const int32_t* rules, int64_t wino_elems, const int32_t* layer, const int32_t* call, const int32_t* head, int32_t* out) {
+    TD_REQUIRE(rules && layer && call && out && wino_elems >= 0, "td_conv_path: bad argument");
+    TD_REQUIRE(call[0] >= 1 && call[1] >= 1 && call[2] >= 1 && call[3] >= 1 && layer[2] >= 1 && layer[3] >= 1, "td_conv_path: bad geometry");
+    td_engine fresh;              // (a plain object: nothing of it touches the GPU) — the rules an engine created now would run by
+    fresh.desc.precision = rules[0];
+    fresh.wino_elems = (size_t)wino_elems;
+    read_rule_switches(&fresh);
+    ConvRules r = conv_rules(&fresh);
+    if (rules[1] >= 0) r.winograd = rules[1] != 0;
+    if (rules[2] >= 0) r.wino_fused = rules[2] != 0;
+    if (rules[3] >= 0) r.wino_minc = rules[3];
+    if (rules[4] >= 0) r.wino43_min = rules[4];
+    if (rules[5] >= 0) r.wino_fold = rules[5];
+    if (rules[6] >= 0) r.wino_slab = rules[6];
+    if (rules[7] >= 0) r.fuse_head = rules[7] != 0;
+    auto facts = [](const int32_t* f) { return ConvLayerFacts{f[0], f[1], f[2], f[3], f[4] != 0, f[5] != 0, f[6] != 0, f[7] != 0, f[8] != 0}; };
+    const ConvSite s{facts(layer), call[0], call[1], call[2], call[3], call[4], call[5] != 0, call[6] != 0, call[7], call[8] != 0, call[9],
+                     head != nullptr, head ? facts(head) : ConvLayerFacts{}};
+    const ConvPath p = conv_path(r, s);
+    out[0] = p.form; out[1] = p.head; out[2] = p.tune ? 1 : 0;
+    for (int i = 0; i < 5; ++i) out[3 + i] = p.tune ? p.key[i] : 0;
+    out[8] = p.slab_tiles; out[9] = p.fold_group;
+    return TD_OK;
 }
 
 td_status td_engine_load_weights(td_engine* e, const td_tensor_desc* tensors, size_t n) {
@@ -914,32 +944,126 @@ td_status tuned_cfg(td_engine* e, const std::tuple<int, int, int, int, int>& key
     return TD_OK;
 }
 
-// The 16 plane contractions of Winograd F(2x2,3x3) slab [t0, t0 + n) of layer L: V [16][n][cin] x U [16][cout][cin] -> M as ONE
-// batched launch, or (wino_fused) the contraction that reads the layer input x [B,H,W,cin] and transforms it in its A staging
-ConvArgs wino_plane_args(const td_engine* e, const ConvLayer& L, const void* x, int B, int H, int W, int n, long long t0,
-                         const int* m_dyn, int m_mul) {
-    ConvArgs a{};
-    a.w = L.wino_u; a.y = e->wino_m;
-    a.Cin = L.cin; a.Cout = L.cout; a.KH = a.KW = 1; a.stride = 1; a.pad = 0;
-    a.M = n; a.m_dyn = m_dyn; a.m_mul = m_dyn ? m_mul / 4 : 1;    // even H, W with a device row count: tiles = rows / 4
-    a.m_off = (int)t0;
-    a.w_bs = (long long)L.cout * L.cin; a.y_bs = (long long)n * L.cout;
-    if (e->wino_fused) { a.x = x; a.B = B; a.H = H; a.W = W; }
-    else { a.x = e->wino_v; a.B = 1; a.H = 1; a.W = n; a.Ho = 1; a.Wo = n; a.batch_count = 16; a.x_bs = (long long)n * L.cin; }
-    return a;
+// The engine's books of every launch of a Winograd sequence (wino_run's hook): its speed-of-light class, the FLOPs it executes and
+// the bytes it moves. Model: P = 16 or 36 plane products of [T x cin] x [cin x cout]; V / M are P T rows (F(2x2): 4x the input /
+// output, F(4x4): 2.25x the padded ones), each crossing HBM once per direction. A device row count: the mask-head class, time only.
+struct WinoBooks {
+    td_engine* e;
+    hipStream_t s;
+    const WinoRun& r;
+    std::optional<ClassScope> cs;
+    static void begin(void* ctx, int step, long long n) {
+        WinoBooks& k = *static_cast<WinoBooks*>(ctx);
+        const WinoRun& r = k.r;
+        if (r.m_dyn) {
+            k.cs.emplace(k.e, k.s, TD_CLS_MASK_HEAD, 0.0, 0.0);
+            return;
+        }
+        const bool f22 = r.form == CONV_WINO22;
+        const double P = f22 ? 16.0 : 36.0;
+        const double T = f22 ? (double)n : (double)r.B * ((r.H + 3) / 4) * ((r.W + 3) / 4);     // F(2x2): the slab's tiles
+        const double share = f22 ? 1.0 : (double)n / r.B;                                         // folded F(4x4): the image group's part
+        const double px = (double)r.B * r.H * r.W;
+        const double xb = 4.0 * px * r.cin, yb = 4.0 * px * r.cout, ub = 4.0 * P * r.cout * r.cin;
+        const double vb = 4.0 * P * T * r.cin, mb = 4.0 * P * T * r.cout, pf = 2.0 * P * T * (double)r.cin * r.cout;
+        if (step == WINO_STEP_INPUT) {
+            k.cs.emplace(k.e, k.s, TD_CLS_WINO_XFORM, 0.0, (xb + vb) * share);
+        } else if (step == WINO_STEP_GEMM) {
+            // (folded: V and U in, y out; F(2x2) with the input transform inside: x in place of V)
+            k.cs.emplace(k.e, k.s, TD_CLS_WINO_GEMM, pf * share,
+                         r.form == CONV_WINO43_FOLD ? (vb + yb) * share + ub : (f22 && r.fused_input ? xb : vb) + ub + mb);
+        } else if (r.head_w) {
+            k.cs.emplace(k.e, k.s, TD_CLS_WINO_XFORM, 2.0 * px * r.head_n * r.cout, mb + (4.0 * px * r.head_n + 4.0 * r.head_n * r.cout));
+        } else {
+            k.cs.emplace(k.e, k.s, TD_CLS_WINO_XFORM, 0.0, mb + yb);
+        }
+    }
+    static void end(void* ctx) { static_cast<WinoBooks*>(ctx)->cs.reset(); }
+};
+
+td_status run_wino(td_engine* e, const WinoRun& r, hipStream_t s) {
+    if (!e->prof) return wino_run(r, s);
+    WinoBooks books{e, s, r, std::nullopt};
+    const WinoHook hook{&books, WinoBooks::begin, WinoBooks::end};
+    return wino_run(r, s, &hook);
 }
 
-// The 36 plane contractions of Winograd F(4x4,3x3) over a whole layer as ONE batched launch: V [36][T][cin] x U -> M [36][T][cout]
-ConvArgs wino43_plane_args(const td_engine* e, const ConvLayer& L, int B, int H, int W, const int* m_dyn) {
-    const int tiles_img = ((H + 3) / 4) * ((W + 3) / 4);
-    const long long T = (long long)B * tiles_img;
-    ConvArgs a{};
-    a.x = e->wino_v; a.w = L.wino_u43; a.y = e->wino_m;
-    a.Cin = L.cin; a.Cout = L.cout; a.KH = a.KW = 1; a.stride = 1; a.pad = 0;
-    a.B = 1; a.H = 1; a.W = (int)T; a.Ho = 1; a.Wo = (int)T;
-    a.M = (int)T; a.m_dyn = m_dyn; a.m_mul = m_dyn ? tiles_img : 1;
-    a.batch_count = 36; a.x_bs = T * L.cin; a.w_bs = (long long)L.cout * L.cin; a.y_bs = T * L.cout;
-    return a;
+ConvLayerFacts layer_facts(const ConvLayer& L) {
+    return {L.cout, L.cin, L.kh, L.kw, L.scale != nullptr, L.out_f32, L.wino_u != nullptr, L.wino_u43 != nullptr, L.w_split != nullptr};
+}
+
+// One contraction of the forward: ask conv_path which form the layer takes, measure the block tile of the launch shape it names,
+// book the launch, launch. head (optional): the 1x1 layer that is this layer's only consumer — *head_fused tells the caller
+// whether it rode along (head_y written, y_ not) or still needs a launch of its own.
+td_status run_conv(td_engine* e, const ConvLayer& L, const void* x_, int B_, int H_, int W_, int stride, int pad, bool relu, void* y_,
+                   const void* res_, int res_shift, hipStream_t s_, const int* m_dyn = nullptr, int m_mul = 1, int out_mode = 0,
+                   const ConvLayer* head = nullptr, float* head_y = nullptr, bool* head_fused = nullptr) {
+    const int prec_ = e->desc.precision;
+    const ConvSite site{layer_facts(L), B_, H_, W_, stride, pad, relu, res_ != nullptr, out_mode, m_dyn != nullptr, m_mul,
+                        head != nullptr, head ? layer_facts(*head) : ConvLayerFacts{}};
+    const ConvPath path = conv_path(conv_rules(e), site);
+    const bool split = path.form == CONV_SPLIT, use_wino = path.form >= CONV_WINO22, use_43 = path.form >= CONV_WINO43;
+    const int Ho = (H_ + 2 * pad - L.kh) / stride + 1, Wo = (W_ + 2 * pad - L.kw) / stride + 1;
+    const double M = (double)B_ * Ho * Wo, K = (double)L.kh * L.kw * L.cin;
+    const double flops = 2.0 * M * L.cout * K;
+    const double es = prec_ == TD_PRECISION_FP16 ? 2.0 : 4.0;
+    // (a split layer's filters cross as three bf16 pieces: 6 bytes per weight)
+    const double bytes = es * ((double)B_ * H_ * W_ * L.cin / (stride * stride) + M * L.cout * (res_ ? 2.0 : 1.0)) + (split ? 6.0 : es) * L.cout * K;
+    td_status st2;
+    ConvArgs ca{};          // the direct launch (tuned tile, fused head below)
+    ca.x = x_; ca.w = L.w; ca.w_frag = L.w_frag; ca.w_split = split ? L.w_split : nullptr; ca.scale = L.scale; ca.bias = L.bias; ca.res = res_; ca.y = y_;
+    ca.B = B_; ca.H = H_; ca.W = W_; ca.Cin = L.cin; ca.Cout = L.cout; ca.KH = L.kh; ca.KW = L.kw;
+    ca.stride = stride; ca.pad = pad; ca.Ho = Ho; ca.Wo = Wo;
+    ca.res_shift = res_shift; ca.relu = relu ? 1 : 0; ca.out_mode = out_mode;
+    ca.M = B_ * Ho * Wo; ca.m_dyn = m_dyn; ca.m_mul = m_mul; ca.tile_cfg = -1; ca.out_f32 = L.out_f32 ? 1 : 0;
+    WinoRun wr{};           // the Winograd sequence (wino_seq.cpp)
+    if (use_wino) {
+        wr.form = path.form; wr.fused_input = e->wino_fused; wr.slab_tiles = path.slab_tiles; wr.fold_group = path.fold_group;
+        wr.x = static_cast<const float*>(x_); wr.U = use_43 ? L.wino_u43 : L.wino_u; wr.scale = L.scale; wr.bias = L.bias; wr.y = static_cast<float*>(y_);
+        wr.B = B_; wr.H = H_; wr.W = W_; wr.cin = L.cin; wr.cout = L.cout; wr.relu = relu ? 1 : 0;
+        wr.V = e->wino_v; wr.M = e->wino_m; wr.m_dyn = m_dyn; wr.m_mul = m_mul; wr.gemm_cfg = -1;
+    }
+    if (path.tune) {
+        const auto key = std::make_tuple(path.key[0], path.key[1], path.key[2], path.key[3], path.key[4]);
+        if (use_wino) {     // the batched plane contraction is a launch shape of its own; timed inside the whole sequence, head apart
+            auto wino = [&](int c) { WinoRun q = wr; q.gemm_cfg = c; return run_wino(e, q, s_); };
+            st2 = tuned_cfg(e, key, prec_, use_43 ? wino43_plane_args(wr) : wino_plane_args(wr, path.key[3], 0), s_, wino, &wr.gemm_cfg);
+        } else {
+            auto direct = [&](int c) { ConvArgs a = ca; a.tile_cfg = c; return conv2d_launch(a, prec_, s_); };
+            st2 = tuned_cfg(e, key, prec_, ca, s_, direct, &ca.tile_cfg);
+        }
+        if (st2 < 0) return st2;
+    }
+    // the head rides along: by the rule, or (bit-identical either way) when the measured tile owns all 256 output channels. Its
+    // FLOPs / bytes join this launch's; its own input read and this layer's output write disappear.
+    const bool fuse_head = path.head == HEAD_IN_TRANSFORM || (path.head == HEAD_IF_TILE_OWNS_256 && conv_head_capable(ca.tile_cfg, prec_));
+    if (head_fused) *head_fused = fuse_head;
+    const double hflops = fuse_head ? 2.0 * M * head->cout * L.cout : 0.0, hbytes = fuse_head ? 4.0 * M * head->cout + es * head->cout * L.cout : 0.0;
+    ProfScope ps(e, s_, m_dyn ? 7 : 0, m_dyn ? 0.0 : flops, m_dyn ? 0.0 : bytes);
+    if (e->prof && !m_dyn) {          // category 8: FLOPs the MFMA pipe really executes
+        const double padded = use_43 ? (double)(((H_ + 3) / 4) * 4) * (((W_ + 3) / 4) * 4) / ((double)H_ * W_) : 1.0;
+        // (a split launch: six bf16 MFMAs, 192 pipe cycles, per 16 k against 512 for the fp32 MFMAs — its pipe time in units of the fp32 rate)
+        e->prof_flops[8] += use_43 ? flops * padded * 0.25 : (use_wino ? flops * 4.0 / 9.0 : (split ? flops * 6.0 / 16.0 : flops));
+        e->prof_launches[8] += use_wino ? 1 : 0;
+    }
+    if (e->prof && fuse_head) {
+        e->prof_flops[0] += hflops;
+        e->prof_flops[8] += hflops;
+        e->prof_launches[0] += 1;          // two layers of the reference in one launch: "launches" keeps counting layers
+        e->prof_bytes[0] += hbytes + es * M * L.cout;       // the unfused pair's algorithmic bytes (every tensor of every layer once)
+    }
+    if (use_wino) {
+        if (fuse_head) { wr.head_w = static_cast<const float*>(head->w); wr.head_b = head->bias; wr.head_y = head_y; wr.head_n = head->cout; }
+        return run_wino(e, wr, s_);
+    }
+    const int cls = m_dyn ? TD_CLS_MASK_HEAD : (H_ == 1 && W_ == 1 ? TD_CLS_FC : (L.kh == 1 && L.kw == 1 ? TD_CLS_CONV1X1 : TD_CLS_CONV3X3));
+    if (fuse_head) {
+        ca.head_w = head->w; ca.head_b = head->bias; ca.head_y = head_y; ca.head_n = head->cout;
+        ClassScope cs(e, s_, cls, flops + hflops, bytes - es * M * L.cout + hbytes);
+        return conv2d_launch(ca, prec_, s_);
+    }
+    ClassScope cs(e, s_, cls, m_dyn ? 0.0 : (split ? flops * 6.0 / 16.0 : flops), m_dyn ? 0.0 : bytes);
+    return conv2d_launch(ca, prec_, s_);
 }
 
 // The forward in six phases. Contractions (0 trunk: stem..RPN heads, 2 box-head FCs, 4 mask-head convs) and the
@@ -957,197 +1081,6 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
     auto PH = [&](int k) { return (phase_mask >> k) & 1u; };
     if (PH(0)) e->named.clear();
     td_status st;
-    // Winograd F(2x2,3x3) path of a stride-1 3x3 layer (fp32 engine): input transform → ONE batched launch of the 16
-    // plane contractions through conv_igemm_kernel → output transform with the layer's scale / bias / ReLU (winograd.hip)
-    auto run_wino = [&](const ConvLayer& L, const void* x_, int B_, int H_, int W_, bool relu, void* y_, hipStream_t s_,
-                        const int* m_dyn, int m_mul, int gemm_cfg) -> td_status {
-        const long long T = (long long)B_ * ((H_ + 1) / 2) * ((W_ + 1) / 2);
-        const int Ts = wino_slab_tiles(e, L);                 // tiles per slab: V + M of a slab stay in the Infinity Cache
-        for (long long t0 = 0; t0 < T; t0 += Ts) {
-            const int n = (int)std::min<long long>(Ts, T - t0);
-            td_status st2;
-            ConvArgs a = wino_plane_args(e, L, x_, B_, H_, W_, n, t0, m_dyn, m_mul);
-            // speed-of-light model (static row counts only): 16 plane products of [n x cin] x [cin x cout]; V = 4x the input,
-            // M = 4x the output, each crossing HBM once per direction
-            const double xb = 4.0 * B_ * H_ * W_ * L.cin, yb = 4.0 * B_ * H_ * W_ * L.cout, ub = 4.0 * 16 * L.cout * L.cin;
-            const double vb = 4.0 * 16 * n * L.cin, mb = 4.0 * 16 * n * L.cout, pf = 2.0 * 16 * n * (double)L.cin * L.cout;
-            const bool dyn = m_dyn != nullptr;
-            if (e->wino_fused) {
-                // input transform fused into the contraction's A staging (wino_gemm_kernel): V never exists in memory
-                ClassScope cs(e, s_, dyn ? TD_CLS_MASK_HEAD : TD_CLS_WINO_GEMM, dyn ? 0.0 : pf, dyn ? 0.0 : xb + ub + mb);
-                if ((st2 = wino_gemm_launch(a, s_)) < 0) return st2;
-            } else {
-                { ClassScope cs(e, s_, dyn ? TD_CLS_MASK_HEAD : TD_CLS_WINO_XFORM, 0.0, dyn ? 0.0 : xb + vb);
-                if ((st2 = wino_input_launch(static_cast<const float*>(x_), B_, H_, W_, L.cin, e->wino_v, m_dyn, m_mul, t0, n, s_)) < 0) return st2; }
-                a.tile_cfg = gemm_cfg;
-                ClassScope cs(e, s_, dyn ? TD_CLS_MASK_HEAD : TD_CLS_WINO_GEMM, dyn ? 0.0 : pf, dyn ? 0.0 : vb + ub + mb);
-                if ((st2 = conv2d_launch(a, TD_PRECISION_FP32, s_)) < 0) return st2;
-            }
-            ClassScope cs(e, s_, dyn ? TD_CLS_MASK_HEAD : TD_CLS_WINO_XFORM, 0.0, dyn ? 0.0 : mb + yb);
-            if ((st2 = wino_output_launch(e->wino_m, B_, H_, W_, L.cout, L.scale, L.bias, relu ? 1 : 0, static_cast<float*>(y_), m_dyn,
-                                          m_mul, t0, n, s_)) < 0) return st2;
-        }
-        return TD_OK;
-    };
-    // Winograd F(4x4,3x3) of a whole layer: x → V [36][T][cin] → 36 batched plane contractions → M → y. m_dyn = device-side
-    // image count (the mask head's live RoIs): the planes keep the stride of the full batch, only the live tiles are computed.
-    auto run_wino43 = [&](const ConvLayer& L, const void* x_, int B_, int H_, int W_, bool relu, void* y_, hipStream_t s_,
-                          const int* m_dyn, int gemm_cfg, const ConvLayer* head = nullptr, float* head_y = nullptr, bool fold = false) -> td_status {
-        const int tiles_img = ((H_ + 3) / 4) * ((W_ + 3) / 4);
-        const long long T = (long long)B_ * tiles_img;
-        td_status st2;
-        // speed-of-light model: 36 plane products of [T x cin] x [cin x cout]; V / M = 36 T rows (2.25x the padded input / output)
-        const bool dyn = m_dyn != nullptr;
-        const double xb = 4.0 * B_ * H_ * W_ * L.cin, yb = 4.0 * B_ * H_ * W_ * L.cout, ub = 4.0 * 36 * L.cout * L.cin;
-        const double vb = 4.0 * 36 * T * L.cin, mb = 4.0 * 36 * T * L.cout, pf = 2.0 * 36 * T * (double)L.cin * L.cout;
-        if (fold) {
-            // contraction + output transform in one launch: V and U in, y out (wino_fused.hip). Its 32-bit plane offsets hold
-            // 4 GB of V: a larger batch runs in image groups, so the layer takes the SAME form at every batch size (batch invariance)
-            const unsigned long long per_img = 36ull * tiles_img * (unsigned long long)std::max(L.cin, L.cout) * 4ull;
-            const int gmax = (int)std::max<unsigned long long>(1ull, std::min<unsigned long long>((0xfffffff0ull - (2u << 20)) / per_img,
-                                                                                                 (0xfffffff0ull - (2u << 20)) / (16ull * tiles_img * L.cout * 4ull)));
-            for (int b0 = 0; b0 < B_; b0 += gmax) {
-                const int Bg = dyn ? B_ : std::min(gmax, B_ - b0);       // (device-side RoI count: one group — 800 RoIs of 14 x 14 are 0.5 GB)
-                const float* xg = static_cast<const float*>(x_) + (size_t)b0 * H_ * W_ * L.cin;
-                float* yg = static_cast<float*>(y_) + (size_t)b0 * H_ * W_ * L.cout;
-                const double share = (double)Bg / B_;
-                { ClassScope cs(e, s_, dyn ? TD_CLS_MASK_HEAD : TD_CLS_WINO_XFORM, 0.0, dyn ? 0.0 : (xb + vb) * share);
-                if ((st2 = wino43_input_launch(xg, Bg, H_, W_, L.cin, e->wino_v, m_dyn, s_)) < 0) return st2; }
-                ClassScope cs(e, s_, dyn ? TD_CLS_MASK_HEAD : TD_CLS_WINO_GEMM, dyn ? 0.0 : pf * share, dyn ? 0.0 : (vb + yb) * share + ub);
-                if ((st2 = wino43_fused_launch(e->wino_v, static_cast<const float*>(L.wino_u43), Bg, H_, W_, L.cin, L.cout, L.scale, L.bias, relu ? 1 : 0,
-                                               yg, m_dyn, s_)) < 0) return st2;
-                if (dyn) break;
-            }
-            return TD_OK;
-        }
-        { ClassScope cs(e, s_, dyn ? TD_CLS_MASK_HEAD : TD_CLS_WINO_XFORM, 0.0, dyn ? 0.0 : xb + vb);
-        if ((st2 = wino43_input_launch(static_cast<const float*>(x_), B_, H_, W_, L.cin, e->wino_v, m_dyn, s_)) < 0) return st2; }
-        ConvArgs a = wino43_plane_args(e, L, B_, H_, W_, m_dyn);
-        a.tile_cfg = gemm_cfg;
-        { ClassScope cs(e, s_, dyn ? TD_CLS_MASK_HEAD : TD_CLS_WINO_GEMM, dyn ? 0.0 : pf, dyn ? 0.0 : vb + ub + mb);
-        if ((st2 = conv2d_launch(a, TD_PRECISION_FP32, s_)) < 0) return st2; }
-        if (head) {        // the 1x1 head contracted inside the output transform (wino43_output_head_kernel): y_ is not written
-            const double hflops = 2.0 * B_ * H_ * W_ * (double)head->cout * L.cout, hb = 4.0 * B_ * H_ * W_ * head->cout + 4.0 * head->cout * L.cout;
-            if (e->prof) {
-                e->prof_flops[0] += hflops;
-                e->prof_flops[8] += hflops;
-                e->prof_launches[0] += 1;          // two layers of the reference in one launch: "launches" keeps counting layers
-                e->prof_bytes[0] += hb + yb;       // the unfused pair's algorithmic bytes
-            }
-            ClassScope cs(e, s_, TD_CLS_WINO_XFORM, hflops, mb + hb);
-            return wino43_output_head_launch(e->wino_m, B_, H_, W_, L.cout, L.scale, L.bias, relu ? 1 : 0, static_cast<const float*>(head->w),
-                                             head->bias, head_y, head->cout, s_);
-        }
-        ClassScope cs(e, s_, dyn ? TD_CLS_MASK_HEAD : TD_CLS_WINO_XFORM, 0.0, dyn ? 0.0 : mb + yb);
-        return wino43_output_launch(e->wino_m, B_, H_, W_, L.cout, L.scale, L.bias, relu ? 1 : 0, static_cast<float*>(y_), m_dyn, s_);
-    };
-    auto run_conv = [&](const ConvLayer& L, const void* x_, int B_, int H_, int W_, int stride, int pad, bool relu,
-                        void* y_, const void* res_, int res_shift, hipStream_t s_, int prec_,
-                        const int* m_dyn = nullptr, int m_mul = 1, int out_mode = 0,
-                        const ConvLayer* head = nullptr, float* head_y = nullptr, bool* head_fused = nullptr) -> td_status {
-        const int Ho = (H_ + 2 * pad - L.kh) / stride + 1, Wo = (W_ + 2 * pad - L.kw) / stride + 1;
-        const double M = (double)B_ * Ho * Wo, K = (double)L.kh * L.kw * L.cin;
-        const double flops = 2.0 * M * L.cout * K;
-        const double es = prec_ == TD_PRECISION_FP16 ? 2.0 : 4.0;
-        // the split rule's layers (ConvLayer::w_split; the engine's own precision only, plain output, static rows)
-        const bool split = L.w_split && prec_ == TD_PRECISION_FP32 && out_mode == 0 && !m_dyn && !head && pad == 0;
-        // (their filters cross as three bf16 pieces: 6 bytes per weight)
-        const double bytes = es * ((double)B_ * H_ * W_ * L.cin / (stride * stride) + M * L.cout * (res_ ? 2.0 : 1.0)) + (split ? 6.0 : es) * L.cout * K;
-        int cfg = split ? 34 : -1, wino_cfg = -1;      // (34: the split family's tile without the tuner)
-        bool use_wino = false, use_43 = false, use_fold = false;
-        td_status st2;
-        ConvArgs ca{};          // the direct launch (tuned tile, fused head below)
-        ca.x = x_; ca.w = L.w; ca.w_frag = L.w_frag; ca.w_split = split ? L.w_split : nullptr; ca.scale = L.scale; ca.bias = L.bias; ca.res = res_; ca.y = y_;
-        ca.B = B_; ca.H = H_; ca.W = W_; ca.Cin = L.cin; ca.Cout = L.cout; ca.KH = L.kh; ca.KW = L.kw;
-        ca.stride = stride; ca.pad = pad; ca.Ho = Ho; ca.Wo = Wo;
-        ca.res_shift = res_shift; ca.relu = relu ? 1 : 0; ca.out_mode = out_mode;
-        ca.M = B_ * Ho * Wo; ca.m_dyn = m_dyn; ca.m_mul = m_mul; ca.tile_cfg = -1; ca.out_f32 = L.out_f32 ? 1 : 0;
-        if (e->autotune) {
-            // (flag 128: a split layer — tune-cache lines written for its fp32 tiles do not apply)
-            const auto key = std::make_tuple(L.cout, L.cin, L.kh * 16 + L.kw, B_ * Ho * Wo, stride * 4 + out_mode * 2 + (res_ ? 1 : 0) + (split ? 128 : 0));
-            auto direct = [&](int c) { ConvArgs a = ca; a.tile_cfg = c; return conv2d_launch(a, prec_, s_); };
-            const bool wino_ok = prec_ == TD_PRECISION_FP32 && L.wino_u && e->wino_v && stride == 1 && pad == 1 && !res_ && out_mode == 0 &&
-                                 (!m_dyn || ((H_ | W_) & 1) == 0) &&
-                                 (size_t)16 * std::min<long long>((long long)B_ * ((H_ + 1) / 2) * ((W_ + 1) / 2), wino_slab_tiles(e, L)) *
-                                         (size_t)std::max(L.cin, L.cout) <= e->wino_elems;
-            if (wino_ok) {
-                // the batched plane contraction is a launch shape of its own (1x1, rows = tiles, flag 32 = batched x16)
-                const int T = (int)std::min<long long>((long long)B_ * ((H_ + 1) / 2) * ((W_ + 1) / 2), wino_slab_tiles(e, L));
-                const auto wkey = std::make_tuple(L.cout, L.cin, 1 * 16 + 1, T, 4 + 32);
-                auto wino = [&](int c) { return run_wino(L, x_, B_, H_, W_, relu, y_, s_, m_dyn, m_mul, c); };
-                // Which path a layer takes must not depend on a measurement: the two differ in rounding, and a timing
-                // decision would make the results vary between processes (sharded ranks, resumed runs). The rule is the
-                // measured outcome on the R50/R101 layer set (profiles/r02_tile_choices.txt): every 3x3 layer with at least
-                // 128 channels on both sides is faster through Winograd at every map size from 13x13 to 200x200
-                // (1.3-1.9x); 64 -> 64 (res2) is HBM-bound on the transforms and stays direct.
-                use_wino = L.cin >= e->wino_minc && L.cout >= e->wino_minc;
-                // F(4x4,3x3) on the large maps (another fixed rule: map size and channels only): 2.25 multiplies per output
-                // instead of 4; the 36 plane contractions are one batched launch whose block tile is measured (flag 64)
-                const long long T43 = (long long)B_ * ((H_ + 3) / 4) * ((W_ + 3) / 4);
-                use_43 = use_wino && L.wino_u43 && e->wino43_min > 0 && H_ >= e->wino43_min && W_ >= e->wino43_min &&
-                         (size_t)36 * T43 * (size_t)std::max(L.cin, L.cout) <= e->wino_elems && T43 * std::max(L.cin, L.cout) < (1ll << 31);
-                // the fold rule: layer shape only (see td_engine::wino_fold)
-                const int hw_ = H_ * W_, wf_ = e->wino_fold;
-                // (a layer with a 1x1 head — the RPN conv — folds only on the 160 x 160+ maps, bit 32: its head then runs as a launch
-                // of its own on the stored map, 1 000 + ~70 us against 1 280 us for the three-launch form with the head in its
-                // output transform; on the smaller maps that form wins)
-                // (device-side RoI count: ALL B_ reserved RoIs are one group below, so its 32-bit plane offsets must hold them — about
-                // 7 279 RoIs of 14 x 14 x 256; past that the layer keeps the three-launch form. Still a rule on reserved shapes only.)
-                use_fold = use_43 && wf_ > 0 && wino43_fused_ok(m_dyn ? B_ : 1, H_, W_, L.cin, L.cout) &&
-                           (((wf_ & 1) && !m_dyn && (!head || (wf_ & 32)) && ((L.cin == 256 && hw_ >= 160 * 160) || (L.cin == 128 && hw_ >= 80 * 80))) ||
-                            ((wf_ & 2) && m_dyn && !head) || ((wf_ & 4) && !m_dyn && !head && L.cin == 256 && hw_ >= 80 * 80) ||
-                            ((wf_ & 8) && !m_dyn && !head && hw_ >= 40 * 40) || ((wf_ & 16) && !m_dyn && !head));
-                if (use_43 && !use_fold) {
-                    const auto key43 = std::make_tuple(L.cout, L.cin, 1 * 16 + 1, (int)T43, 4 + 64);
-                    auto w43 = [&](int c) { return run_wino43(L, x_, B_, H_, W_, relu, y_, s_, m_dyn, c); };
-                    if ((st2 = tuned_cfg(e, key43, prec_, wino43_plane_args(e, L, B_, H_, W_, m_dyn), s_, w43, &wino_cfg)) < 0) return st2;
-                }
-                if (use_wino && !use_43 && !e->wino_fused &&
-                    (st2 = tuned_cfg(e, wkey, prec_, wino_plane_args(e, L, x_, B_, H_, W_, T, 0, m_dyn, m_mul), s_, wino, &wino_cfg)) < 0) return st2;
-            }
-            if (!use_wino && (st2 = tuned_cfg(e, key, prec_, ca, s_, direct, &cfg)) < 0) return st2;
-        }
-        ProfScope ps(e, s_, m_dyn ? 7 : 0, m_dyn ? 0.0 : flops, m_dyn ? 0.0 : bytes);
-        if (e->prof && !m_dyn) {          // category 8: FLOPs the MFMA pipe really executes
-            const double padded = use_43 ? (double)(((H_ + 3) / 4) * 4) * (((W_ + 3) / 4) * 4) / ((double)H_ * W_) : 1.0;
-            // (a split launch: six bf16 MFMAs, 192 pipe cycles, per 16 k against 512 for the fp32 MFMAs — its pipe time in units of the fp32 rate)
-            e->prof_flops[8] += use_43 ? flops * padded * 0.25 : (use_wino ? flops * 4.0 / 9.0 : (split ? flops * 6.0 / 16.0 : flops));
-            e->prof_launches[8] += use_wino ? 1 : 0;
-        }
-        if (use_43) {
-            // fp32 engine: the head rides in the F(4x4) output transform — a FIXED rule (layer shapes only), bit-identical to the
-            // separate launch anyway
-            const bool fuse43 = head && !use_fold && e->fuse_head && !m_dyn && relu && L.cout == 256 && head->cin == 256 && head->kh == 1 && head->kw == 1 &&
-                                head->cout <= 32 && !head->scale;
-            if (head_fused) *head_fused = fuse43;
-            return run_wino43(L, x_, B_, H_, W_, relu, y_, s_, m_dyn, wino_cfg, fuse43 ? head : nullptr, fuse43 ? head_y : nullptr, use_fold);
-        }
-        if (use_wino) return run_wino(L, x_, B_, H_, W_, relu, y_, s_, m_dyn, m_mul, wino_cfg);
-        const int cls = m_dyn ? TD_CLS_MASK_HEAD : (H_ == 1 && W_ == 1 ? TD_CLS_FC : (L.kh == 1 && L.kw == 1 ? TD_CLS_CONV1X1 : TD_CLS_CONV3X3));
-        // A 1x1 head contracted from the finished tile inside the same launch (the RPN's 15-row head after its 3x3 conv): only
-        // when the measured tile owns all 256 output channels — bit-identical to the separate launch either way, so the tile
-        // choice (a timing) may decide it. The head's FLOPs / bytes join this launch's; its own input read and this layer's
-        // output write disappear.
-        const bool fuse_head = head && e->fuse_head && !m_dyn && out_mode == 0 && !res_ && relu && L.cout == 256 && head->cin == 256 &&
-                               head->kh == 1 && head->kw == 1 && head->cout <= 32 && head->out_f32 && !head->scale && conv_head_capable(cfg, prec_);
-        if (head_fused) *head_fused = fuse_head;
-        ca.tile_cfg = cfg;
-        if (fuse_head) {
-            const double hflops = 2.0 * M * head->cout * L.cout, hbytes = 4.0 * M * head->cout + es * head->cout * L.cout;
-            const double bytes_f = bytes - es * M * L.cout + hbytes;
-            if (e->prof) {
-                e->prof_flops[0] += hflops;
-                e->prof_flops[8] += hflops;
-                e->prof_launches[0] += 1;          // two layers of the reference in one launch: "launches" keeps counting layers
-                e->prof_bytes[0] += hbytes + es * M * L.cout;       // the unfused pair's algorithmic bytes (every tensor of every layer once)
-            }
-            ca.head_w = head->w; ca.head_b = head->bias; ca.head_y = head_y; ca.head_n = head->cout;
-            ClassScope cs(e, s_, cls, flops + hflops, bytes_f);
-            return conv2d_launch(ca, prec_, s_);
-        }
-        ClassScope cs(e, s_, cls, m_dyn ? 0.0 : (split ? flops * 6.0 / 16.0 : flops), m_dyn ? 0.0 : bytes);
-        return conv2d_launch(ca, prec_, s_);
-    };
     // The same 3x3 layer shape on several pyramid levels as ONE launch (conv_pp8_grouped_launch, fp16 engine): the FPN's output
     // convs, the RPN conv with its head. The small levels (p4-p6: 79 / 20 / 6 tiles of 256 rows) cannot fill 256 CUs on their own;
     // in one grid their tiles run beside the big levels' last wave. A fixed rule (layer shapes only); bit-identical per level.
@@ -1256,10 +1189,10 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
                 void* y = ((nb - 1 - bi) % 2 == 0) ? resb : xtmp;
                 const void* shortcut = x;
                 if (blk.has_sc) {
-                    if ((st = run_conv(blk.sc, x, nb_img, xh, xw, blk.stride, 0, false, scb, nullptr, 0, s, prec)) < 0) return st;
+                    if ((st = run_conv(e, blk.sc, x, nb_img, xh, xw, blk.stride, 0, false, scb, nullptr, 0, s)) < 0) return st;
                     shortcut = scb;
                 }
-                if ((st = run_conv(blk.c1, x, nb_img, xh, xw, blk.stride, 0, true, t1, nullptr, 0, s, prec)) < 0) return st;
+                if ((st = run_conv(e, blk.c1, x, nb_img, xh, xw, blk.stride, 0, true, t1, nullptr, 0, s)) < 0) return st;
                 // Measured (round 3, plain loop, batch 8, 64-row blocks): fp32 res2 345 us fused against 215 + 185 us as two launches;
                 // fp16 res2 130 us against 54 + 87; fp16 res3 111 us against 41 + 47 — slower (a fused block is a chain of short
                 // latency-bound steps, and with 128 mid channels only two blocks fit a CU), so res3 fuses only on request
@@ -1270,8 +1203,8 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
                     // tensor t2 never reaches HBM
                     if ((st = run_tail(blk, t1, nb_img, oh, ow, y, shortcut, s)) < 0) return st;
                 } else {
-                    if ((st = run_conv(blk.c2, t1, nb_img, oh, ow, 1, 1, true, t2, nullptr, 0, s, prec)) < 0) return st;
-                    if ((st = run_conv(blk.c3, t2, nb_img, oh, ow, 1, 0, true, y, shortcut, 0, s, prec)) < 0) return st;
+                    if ((st = run_conv(e, blk.c2, t1, nb_img, oh, ow, 1, 1, true, t2, nullptr, 0, s)) < 0) return st;
+                    if ((st = run_conv(e, blk.c3, t2, nb_img, oh, ow, 1, 0, true, y, shortcut, 0, s)) < 0) return st;
                 }
                 x = y;
                 xh = oh;
@@ -1297,8 +1230,8 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
                            groupable(e->fpn_out[2]) && groupable(e->fpn_out[3]);
     for (int l = 3; l >= 0; --l) {
         const void* td_res = l == 3 ? nullptr : e->inner[l + 1];
-        if ((st = run_conv(e->lateral[l], e->res[l], B, hs[l], wsz[l], 1, 0, false, e->inner[l], td_res, td_res ? 1 : 0, s, prec)) < 0) return st;
-        if (!group_fpn && (st = run_conv(e->fpn_out[l], e->inner[l], B, hs[l], wsz[l], 1, 1, false, e->pfeat[l], nullptr, 0, s, prec)) < 0) return st;
+        if ((st = run_conv(e, e->lateral[l], e->res[l], B, hs[l], wsz[l], 1, 0, false, e->inner[l], td_res, td_res ? 1 : 0, s)) < 0) return st;
+        if (!group_fpn && (st = run_conv(e, e->fpn_out[l], e->inner[l], B, hs[l], wsz[l], 1, 1, false, e->pfeat[l], nullptr, 0, s)) < 0) return st;
     }
     if (group_fpn) {
         const ConvLayer* Ls[4] = {&e->fpn_out[0], &e->fpn_out[1], &e->fpn_out[2], &e->fpn_out[3]};
@@ -1331,9 +1264,9 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
                 continue;
             }
             bool fused = false;
-            if ((st = run_conv(e->rpn_conv, e->pfeat[l], B, hs[l], wsz[l], 1, 1, true, e->rpn_t, nullptr, 0, s, prec, nullptr, 1, 0,
+            if ((st = run_conv(e, e->rpn_conv, e->pfeat[l], B, hs[l], wsz[l], 1, 1, true, e->rpn_t, nullptr, 0, s, nullptr, 1, 0,
                                &e->rpn_head, e->rpn_headbuf[l], &fused)) < 0) return st;
-            if (!fused && (st = run_conv(e->rpn_head, e->rpn_t, B, hs[l], wsz[l], 1, 0, false, e->rpn_headbuf[l], nullptr, 0, s, prec)) < 0) return st;
+            if (!fused && (st = run_conv(e, e->rpn_head, e->rpn_t, B, hs[l], wsz[l], 1, 0, false, e->rpn_headbuf[l], nullptr, 0, s)) < 0) return st;
             const std::string nm = "rpn_head" + std::to_string(l + 2);
             set_named(e, nm.c_str(), e->rpn_headbuf[l], B, hs[l], wsz[l], RPN_HEAD_C);
         }
@@ -1406,9 +1339,9 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
     if (PH(2)) {
     {
     ProfScope box_group(e, s, 0, 0.0, 0.0, true);
-    if ((st = run_conv(e->fc1, e->pooled7, B * P, 1, 1, 1, 0, true, e->fc1_out, nullptr, 0, s, prec)) < 0) return st;
-    if ((st = run_conv(e->fc2, e->fc1_out, B * P, 1, 1, 1, 0, true, e->fc2_out, nullptr, 0, s, prec)) < 0) return st;
-    if ((st = run_conv(e->pred, e->fc2_out, B * P, 1, 1, 1, 0, false, e->pred_out, nullptr, 0, s, prec)) < 0) return st;
+    if ((st = run_conv(e, e->fc1, e->pooled7, B * P, 1, 1, 1, 0, true, e->fc1_out, nullptr, 0, s)) < 0) return st;
+    if ((st = run_conv(e, e->fc2, e->fc1_out, B * P, 1, 1, 1, 0, true, e->fc2_out, nullptr, 0, s)) < 0) return st;
+    if ((st = run_conv(e, e->pred, e->fc2_out, B * P, 1, 1, 1, 0, false, e->pred_out, nullptr, 0, s)) < 0) return st;
     }
     set_named(e, "box_pred", e->pred_out, (int64_t)B * P, 6);
     }   // phase 2
@@ -1445,10 +1378,10 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
     {
     ProfScope mask_group(e, s, 7, 0.0, 0.0, true);
     for (int i = 0; i < 4; ++i) {
-        if ((st = run_conv(e->mask_fcn[i], mx, mrows, 14, 14, 1, 1, true, mbuf[i & 1], nullptr, 0, s, prec, e->total_rows, 196)) < 0) return st;
+        if ((st = run_conv(e, e->mask_fcn[i], mx, mrows, 14, 14, 1, 1, true, mbuf[i & 1], nullptr, 0, s, e->total_rows, 196)) < 0) return st;
         mx = mbuf[i & 1];
     }
-    if ((st = run_conv(e->deconv, mx, mrows, 14, 14, 1, 0, true, e->deconv_out, nullptr, 0, s, prec, e->total_rows, 196, 1)) < 0) return st;
+    if ((st = run_conv(e, e->deconv, mx, mrows, 14, 14, 1, 0, true, e->deconv_out, nullptr, 0, s, e->total_rows, 196, 1)) < 0) return st;
     }
     // (stage tests: the device row count every launch above reads, and the last two layers' outputs as stored)
     set_named(e, "mask_total_rows", e->total_rows, 1);

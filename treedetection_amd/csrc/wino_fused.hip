@@ -323,11 +323,7 @@ __global__ __launch_bounds__(NWT * 128, 2) void wino43_fused_kernel(const WinoFu
 
 }  // namespace
 
-bool wino43_fused_ok(int B, int H, int W, int C, int N) {
-    const long long T = (long long)B * ((H + 3) / 4) * ((W + 3) / 4);
-    return (C == 128 || C == 256 || C == 512) && N >= WF_BN && N % WF_BN == 0 && 36ull * (unsigned long long)T * C * 4 < 0xfffffff0ull - (1u << 20) &&
-           36ull * (unsigned long long)N * C * 4 < 0xfffffff0ull - (1u << 20) && (unsigned long long)B * H * W * N * 4 < 0xfffffff0ull - (1u << 20);
-}
+static_assert(WF_BN == 64, "wino43_fused_ok (conv_path.cpp) admits output channels in multiples of 64");
 
 // V [36][T][C] (wino43_input_launch) x U [36][N][C] → y [B,H,W,N] = act((A^T (sum_c U .* V) A) * scale + bias)
 td_status wino43_fused_launch(const float* V, const float* U, int B, int H, int W, int C, int N, const float* scale, const float* bias,
