@@ -446,6 +446,22 @@ td_status td_tiff_blocks_to_image_u16_dev(const uint8_t* blocks, int64_t block_c
  * Asynchronous on `stream`. */
 td_status td_tiff_blocks_to_image_f32_dev(const uint8_t* blocks, int64_t block_cap, int block_w, int block_h, int blocks_across,
                                           int blocks_down, int spp, int predictor, float* image, int width, int height, void* stream);
+/* The same three for band-separate files (PlanarConfiguration = 2): `blocks` holds the decoded blocks of the SELECTED bands only (bit p
+ * of plane_mask: band p), bands ascending, within a band the file's own order (blocks_across x blocks_down, row-major), each block at
+ * a multiple of block_cap BYTES. A block row is block_w consecutive samples of one band: predictor 2 is a stride-1 running sum per
+ * block row modulo 2^8 / 2^16 / 2^32; predictor 3 (float32 only) is TIFF Technical Note 3 with one sample per pixel (four byte planes
+ * of block_w bytes, most significant first, differenced byte-wise over all 4 * block_w bytes: td_tiff_unpredict_float's rule). image
+ * is [height][width][spp] as above; the channels of bands that are not selected are written as 0. 1 <= spp <= 4, plane_mask non-zero
+ * and below 1 << spp. One launch, asynchronous on `stream`. */
+td_status td_tiff_planes_to_image_dev(const uint8_t* blocks, int64_t block_cap, int block_w, int block_h, int blocks_across,
+                                      int blocks_down, int spp, int plane_mask, int predictor, uint8_t* image, int width, int height,
+                                      void* stream);
+td_status td_tiff_planes_to_image_u16_dev(const uint8_t* blocks, int64_t block_cap, int block_w, int block_h, int blocks_across,
+                                          int blocks_down, int spp, int plane_mask, int predictor, uint16_t* image, int width, int height,
+                                          void* stream);
+td_status td_tiff_planes_to_image_f32_dev(const uint8_t* blocks, int64_t block_cap, int block_w, int block_h, int blocks_across,
+                                          int blocks_down, int spp, int plane_mask, int predictor, float* image, int width, int height,
+                                          void* stream);
 /* ---- JPEG-in-TIFF (compression 7; jpeg_core.h, jpegcodec.cpp, jpegdecode.hip): sequential Huffman, 8-bit, grey, three components
  * (Y 1x1 / 2x1 / 2x2, chroma 1x1) or four (all 1x1, stored as they decode: RGB + an extra sample, separated), restart intervals; the
  * output equals the host reader's (Pillow's libjpeg: accurate integer IDCT, fancy

@@ -16,7 +16,15 @@ stage (a synthetic nDSM, one band) — per predictor one JSON line with the comp
 predictor kernel apart (HIP events on the stream they ran on, median of 7 warm runs; the scatter's GB/s counts one read and one
 write of the raster), the wall time from the file to a raster td_crown_stats can read for the device path (decode_to_device +
 check()) and for the host paths: the block reader (read()) + the copy to the device, and — predictor 3 — the whole image through Pillow
-+ the copy, which is how the reader served such files before it undid the floating-point predictor itself."""
++ the copy, which is how the reader served such files before it undid the floating-point predictor itself.
+planar=1 [path=device|host|chunky] [bands=0,3] [codec=lzw|deflate|zstd [level=9]] [side=9000] [tile=256|strip=N] [predictor=2] [host_threads=16]
+[file=PATH]: the four-band uint8 raster written band-separate (PlanarConfiguration = 2) — one JSON line for ONE path, so that each runs
+in a process of its own: "device" = decode_to_device(planar=True[, bands=...]) from the file to the raster in HBM (wall, best and
+median of 5 after a warm-up), then the block decoder's launch and the layout launch (td_tiff_planes_to_image_dev) apart, HIP events,
+median of 7 warm runs; "host" = the same file through the host reader on host_threads threads + the copy to the device (what the file
+costs with ``device_decode_planar`` off); "chunky" = the same pixels pixel-interleaved on the existing device path, its decoder and
+tiff_blocks_to_image_rgbi_kernel apart. ``bands`` (device only) decodes a plane subset, e.g. 0,3 for NDVI. ``file``: the raster is
+written there unless it exists, and stays (several paths over one file)."""
 import json
 import os
 import sys
@@ -146,8 +154,136 @@ def f32_main():
                 os.unlink(path)
 
 
+def planar_main():
+    from concurrent.futures import ThreadPoolExecutor
+    from statistics import median
+    from treedetection_amd import _lib
+    lib = _lib.load()
+    side, pred, codec, which = int(args.get("side", 9000)), int(args.get("predictor", 2)), args.get("codec", "lzw"), args.get("path", "device")
+    bands = tuple(int(v) for v in args["bands"].split(",")) if "bands" in args else None
+    assert which in ("device", "host", "chunky") and (bands is None or which == "device")
+    kw = {"rows_per_strip": int(args["strip"])} if "strip" in args else {"tile": (int(args.get("tile", 256)),) * 2}
+    if codec == "zstd":
+        kw["zstd_level"] = int(args.get("level", 9))
+    n = -(-side // 1000)
+    tiles = [make_tile(i, 1000)[0] for i in range(min(16, n * n))]
+    img = np.zeros((4, n * 1000, n * 1000), np.uint8)
+    for r in range(n):
+        for c in range(n):
+            t = tiles[(r * n + c) % len(tiles)]
+            img[:3, r * 1000:(r + 1) * 1000, c * 1000:(c + 1) * 1000] = t.transpose(2, 0, 1)
+            img[3, r * 1000:(r + 1) * 1000, c * 1000:(c + 1) * 1000] = t[..., 1]
+    img = np.ascontiguousarray(img[:, :side, :side])
+    base = "/dev/shm" if os.path.isdir("/dev/shm") else tempfile.gettempdir()
+    path = args.get("file", os.path.join(base, f"td_planarbench_{os.getpid()}.tif"))
+    planar = which != "chunky"
+    try:
+        if not ("file" in args and os.path.exists(path)):
+            write_geotiff(path, img, (0.2, 0, 412000.0, 0, -0.2, 5318000.0 + side * 0.2), 25832, compression=codec, predictor=pred, planar=planar, **kw)
+        g = GeoTiff(path)
+        assert g.planar == (2 if planar else 1) and g.device_decodable(planar=planar) and not (planar and g.device_decodable())
+        want = img.transpose(1, 2, 0).copy()
+        if bands is not None:
+            want[:, :, [c for c in range(4) if c not in bands]] = 0
+        line = {"path": which, "codec": codec, "raster": f"{side}x{side}x4", "layout": kw, "predictor": pred, "planar": planar, "bands": bands,
+                "raw_mb": img.nbytes / 1e6, "file_mb": os.path.getsize(path) / 1e6}
+        r3 = lambda v: [round(t, 3) for t in v]
+        if which == "host":
+            nth = int(args.get("host_threads", 16))
+            host_ms = []
+            for k in range(4):
+                h = GeoTiff(path)
+                h._setup_blocks()
+                keys = [(p, by, bx) for p in range(4) for by in range(h._ny) for bx in range(h._nx)]
+                t0 = time.perf_counter()
+                with ThreadPoolExecutor(max_workers=nth) as hp:
+                    blks = list(hp.map(lambda key: h._decode_block(*key), keys))
+                ref = np.empty((side, side, 4), np.uint8)
+                for (p, by, bx), blk in zip(keys, blks):
+                    r0, c0 = by * h._bh, bx * h._bw
+                    piece = blk[:min(blk.shape[0], side - r0), :min(h._bw, side - c0), 0]
+                    ref[r0:r0 + piece.shape[0], c0:c0 + piece.shape[1], p] = piece
+                dev_ref = torch.from_numpy(ref).cuda()
+                torch.cuda.synchronize()
+                host_ms.append((time.perf_counter() - t0) * 1e3)
+                if k == 0:
+                    assert np.array_equal(ref, want), "host reader differs from what was written"
+                del blks, dev_ref
+                h.close()
+            line.update(host_threads=nth, host_reader_plus_stitch_plus_h2d_ms=r3(host_ms), host_median_ms=round(median(host_ms[1:]), 1))
+            print(json.dumps(line), flush=True)
+            return
+        pinned, pool = [None], ThreadPoolExecutor(max_workers=8)
+        dkw = {"planar": True, "bands": bands} if planar else {}
+        wall_ms, kernel_ms = [], []
+        for k in range(6):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            image, check = g.decode_to_device("cuda:0", None, pinned, pool, **dkw)
+            got = check()
+            wall_ms.append((time.perf_counter() - t0) * 1e3)
+            kernel_ms.append(check.kernel_ms)
+            if k == 0:
+                assert np.array_equal(got.cpu().numpy(), want), "decoded raster differs from what was written"
+            del image, got
+        line.update(copied_mb=check.compressed_bytes / 1e6, file_to_hbm_ms=r3(wall_ms), file_to_hbm_median_ms=round(median(wall_ms[1:]), 1),
+                    file_to_hbm_best_ms=round(min(wall_ms[1:]), 1), both_launches_ms=r3(kernel_ms))
+        # the two launches apart, the selected planes' compressed blocks already on the device
+        planes, mask, offs, cnts, expect, ranges = g.device_block_plan(bands)
+        raw = np.fromfile(path, dtype=np.uint8)
+        comp = torch.from_numpy(np.concatenate([raw[lo:hi] for lo, hi in ranges] + [np.zeros(16, np.uint8)])).cuda()
+        starts = np.cumsum([0] + [hi - lo for lo, hi in ranges])
+        r_lo = np.array([r[0] for r in ranges], dtype=np.int64)
+        which_r = np.searchsorted(r_lo, offs, side="right") - 1
+        meta = torch.from_numpy(np.stack([offs - r_lo[which_r] + starts[:-1][which_r], cnts])).cuda()
+        nb, cap = len(offs), g._bw * g._bh * (1 if planar else 4)
+        blocks = torch.empty((nb, cap), dtype=torch.uint8, device="cuda")
+        dec = torch.empty((nb,), dtype=torch.int64, device="cuda")
+        ends = torch.empty((nb,), dtype=torch.int64, device="cuda")
+        status = torch.empty((2 * nb + 1,), dtype=torch.int32, device="cuda")
+        image = torch.empty((side, side, 4), dtype=torch.uint8, device="cuda")
+        sp = _lib.stream_ptr()
+        head = (comp.data_ptr(), meta[0].data_ptr(), meta[1].data_ptr(), nb, blocks.data_ptr(), cap, dec.data_ptr(), status.data_ptr())
+
+        def timed(fn, reps=7):
+            out = []
+            for _ in range(reps + 1):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                _lib.check(fn(), "launch")
+                e1.record()
+                torch.cuda.synchronize()
+                out.append(e0.elapsed_time(e1))
+            return out[1:]                                      # (the first run is the warm-up)
+        if codec == "lzw":
+            decode_ms = timed(lambda: lib.td_tiff_lzw_decode_dev(*head, sp))
+        elif codec == "zstd":
+            lits = torch.empty((int(lib.td_tiff_zstd_scratch_bytes(nb)),), dtype=torch.uint8, device="cuda")
+            decode_ms = timed(lambda: lib.td_tiff_zstd_decode_dev(*head, lits.data_ptr(), lits.numel(), sp))
+        else:
+            decode_ms = timed(lambda: lib.td_tiff_inflate_verified_dev(*head, ends.data_ptr(), sp))
+        assert int((status[:nb] != 0).sum()) == 0
+        if planar:
+            layout_ms = timed(lambda: lib.td_tiff_planes_to_image_dev(blocks.data_ptr(), cap, g._bw, g._bh, g._nx, g._ny, 4, mask, pred, image.data_ptr(),
+                                                                      side, side, sp))
+        else:
+            layout_ms = timed(lambda: lib.td_tiff_blocks_to_image_dev(blocks.data_ptr(), cap, g._bw, g._bh, g._nx, g._ny, 4, pred, image.data_ptr(),
+                                                                      side, side, sp))
+        assert np.array_equal(image.cpu().numpy(), want)
+        moved = img.nbytes + len(planes) * (img.nbytes // 4 if planar else img.nbytes)      # one write of the raster + one read of what was decoded
+        line.update(blocks=nb, decoder_ms=r3(decode_ms), decoder_median_ms=round(median(decode_ms), 3), layout_ms=r3(layout_ms),
+                    layout_median_ms=round(median(layout_ms), 3), layout_gb_per_s_read_plus_write=moved / (median(layout_ms) * 1e-3) / 1e9)
+        print(json.dumps(line), flush=True)
+    finally:
+        if "file" not in args and os.path.exists(path):
+            os.unlink(path)
+
+
 if args.get("samples") == "f32":
     f32_main()
+    sys.exit(0)
+if args.get("planar") == "1":
+    planar_main()
     sys.exit(0)
 side, pred, data, codec = int(args.get("side", 9000)), int(args.get("predictor", 2)), args.get("data", "tiles"), args.get("codec", "lzw")
 kw = {"rows_per_strip": int(args["strip"])} if "strip" in args else {"tile": (int(args.get("tile", 256)),) * 2}

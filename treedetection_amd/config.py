@@ -12,7 +12,8 @@ its tile files are complete, while the next one predicts), ``fp16_min_batch`` (0
 detection.engine_batch_size), ``device_contours`` ("auto" | true | false: mask borders followed on the GPU while the host epilogue,
 not the GPU, sets the batch period; same files), ``device_decode`` ("auto" | false | "all": LZW, DEFLATE, ZSTD and JPEG rasters decoded on the GPU, tile windows cut
 in HBM — "all": uncompressed rasters are kept in HBM too; same pixels), ``device_decode_long_jpeg`` (true | false, default false: JPEG
-rasters whose blocks have no restart markers are decoded on the GPU too, a wave per entropy-coded segment; same pixels), ``device_filters`` ("auto" | true | false: the crown stage's
+rasters whose blocks have no restart markers are decoded on the GPU too, a wave per entropy-coded segment; same pixels), ``device_decode_planar`` (true | false, default false: band-separate rasters, PlanarConfiguration = 2,
+are decoded on the GPU too and their planes interleaved there; same pixels), ``device_filters`` ("auto" | true | false: the crown stage's
 box-IoU de-duplication and containment pair tests on the GPU, sparse result only — "auto" keeps the host functions; same features),
 ``clean_crowns`` (true | false, default false: the crown stage first thins each layer by the IoU of the crown outlines, threshold 0.7,
 the reference's ``clean_crowns`` — treedetection_amd.cleaning; false: not one byte of any output changes).
@@ -167,7 +168,7 @@ def get_config(config_path: str):
         # extensions of this package (defaults = the reference's behaviour)
         "precision": "fp32", "resnet_depth": 101, "sharded_epilogue": "auto", "shard_by": "auto", "eager_stitch": True,
         "fp16_min_batch": 0, "device_contours": "auto", "device_decode": "auto", "device_filters": "auto",
-        "device_decode_long_jpeg": False, "clean_crowns": False,
+        "device_decode_long_jpeg": False, "device_decode_planar": False, "clean_crowns": False,
     }
     for k, v in defaults.items():
         config[k] = config.get(k, v)

@@ -600,21 +600,13 @@ __device__ __forceinline__ uint32_t fp_spread(uint32_t e, int ph) {
     const uint64_t twice = (uint64_t)e | ((uint64_t)e << 24);
     return (uint32_t)(twice >> (8 * ph));
 }
+// One block row for the whole workgroup: `row` = its n = bw * spp samples (4n bytes), the first nvalid of them are stored, sample k at
+// dst[k * dst_stride] (1: pixel-interleaved blocks; the raster's spp for one band of a planar file, tiff_fp_planes_to_image_kernel).
 template <int spp>
-__global__ __launch_bounds__(FP_THREADS) void tiff_fp_blocks_to_image_kernel(const uint8_t* __restrict__ blocks, int64_t block_cap, int bw, int bh,
-                                                                             int blocks_across, uint32_t* __restrict__ image, int width,
-                                                                             int height) {
-    __shared__ uint32_t plane_tot[4];
-    __shared__ uint32_t xch[2][4][64];                     // two steps' dwords of the four planes (one barrier per step)
+__device__ __forceinline__ void fp_block_row(const uint32_t* __restrict__ row, int n, int nvalid, uint32_t* __restrict__ dst, int dst_stride,
+                                             uint32_t* plane_tot, uint32_t (*xch)[4][64]) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int plane = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int y = blockIdx.x, bx = blockIdx.y;
-    const int by = y / bh;
-    const int n = bw * spp;
-    const uint32_t* row = reinterpret_cast<const uint32_t*>(blocks + ((int64_t)by * blocks_across + bx) * block_cap) + (int64_t)(y - by * bh) * n;
-    const int x0 = bx * bw;
-    const int nvalid = min(bw, width - x0) * spp;          // samples of this block row that lie inside the raster
-    uint32_t* dst = image + ((int64_t)y * width + x0) * spp;
     // pass 1: this plane's total per channel
     uint32_t acc = 0;
     for (int base = 0; base < n; base += FP_THREADS) {
@@ -648,10 +640,223 @@ __global__ __launch_bounds__(FP_THREADS) void tiff_fp_blocks_to_image_kernel(con
         const int k = base + tid;
         if (k < nvalid) {
             const int sh = 8 * (tid & 3);
-            dst[k] = (((xch[buf][0][tid >> 2] >> sh) & 255u) << 24) | (((xch[buf][1][tid >> 2] >> sh) & 255u) << 16) |
-                     (((xch[buf][2][tid >> 2] >> sh) & 255u) << 8) | ((xch[buf][3][tid >> 2] >> sh) & 255u);
+            dst[(int64_t)k * dst_stride] = (((xch[buf][0][tid >> 2] >> sh) & 255u) << 24) | (((xch[buf][1][tid >> 2] >> sh) & 255u) << 16) |
+                                           (((xch[buf][2][tid >> 2] >> sh) & 255u) << 8) | ((xch[buf][3][tid >> 2] >> sh) & 255u);
         }
     }
+}
+template <int spp>
+__global__ __launch_bounds__(FP_THREADS) void tiff_fp_blocks_to_image_kernel(const uint8_t* __restrict__ blocks, int64_t block_cap, int bw, int bh,
+                                                                             int blocks_across, uint32_t* __restrict__ image, int width,
+                                                                             int height) {
+    __shared__ uint32_t plane_tot[4];
+    __shared__ uint32_t xch[2][4][64];                     // two steps' dwords of the four planes (one barrier per step)
+    const int y = blockIdx.x, bx = blockIdx.y;
+    const int by = y / bh;
+    const int n = bw * spp;
+    const uint32_t* row = reinterpret_cast<const uint32_t*>(blocks + ((int64_t)by * blocks_across + bx) * block_cap) + (int64_t)(y - by * bh) * n;
+    const int x0 = bx * bw;
+    const int nvalid = min(bw, width - x0) * spp;          // samples of this block row that lie inside the raster
+    fp_block_row<spp>(row, n, nvalid, image + ((int64_t)y * width + x0) * spp, 1, plane_tot, xch);
+}
+
+// ---- band-separate (PlanarConfiguration = 2) files: decoded planes → the same raster [height][width][spp] ----------------------------
+// `blocks` holds one grid of blocks_across x blocks_down blocks per SELECTED band (bit c of plane_mask), ascending, each block at a
+// multiple of block_cap; a block row is bw consecutive samples of one band, so predictor 2 is a stride-1 running sum. Channels of
+// bands that were not selected are stored as 0: every output sample is written once, every selected plane sample read once, in ONE
+// launch. One WAVE per (image row, block column), four rows per workgroup, as tiff_blocks_to_image_rgbi_kernel; a lane takes one
+// dword = 4 / sizeof(T) consecutive samples of EVERY selected band per step, so a step is 256 uint8 / 128 uint16 / 64 float32 pixels.
+// PL_LOAD_DWORDS: every block row begins at a dword (the launcher's test: blocks, block_cap, bw * sizeof(T) multiples of 4) and is
+// read as dwords; otherwise (odd block widths — the strips of most rasters — or an odd block_cap) the same samples are read one by
+// one. PL_STORE_DWORDS: a pixel is one or two whole dwords (4 x uint8, 2 or 4 x uint16) of a dword-aligned image and is stored as
+// such; otherwise sample by sample (float32 samples are dwords either way).
+constexpr int PL_LOAD_DWORDS = 1, PL_STORE_DWORDS = 2;
+
+// the block rows of the spp bands of image row y in block column bx (nullptr: band not selected)
+template <int spp>
+__device__ __forceinline__ void planar_rows(const uint8_t* __restrict__ blocks, int64_t block_cap, int64_t row_bytes, int bh, int blocks_across,
+                                            int blocks_down, int plane_mask, int y, int bx, const uint8_t* (&src)[spp]) {
+    const int by = y / bh;
+    int slot = 0;
+#pragma unroll
+    for (int c = 0; c < spp; ++c) {
+        const bool sel = (plane_mask >> c) & 1;
+        src[c] = sel ? blocks + (((int64_t)slot * blocks_down + by) * blocks_across + bx) * block_cap + (int64_t)(y - by * bh) * row_bytes : nullptr;
+        slot += sel;
+    }
+}
+
+// uint8: the four pixels of a lane ride in one dword per band (byte j = pixel j): the running sum inside the dword is two packed
+// byte adds, the lanes' totals of ALL bands are scanned across the wave as one dword (byte c = band c: one scan per 256 pixels,
+// whatever spp), and a 4 x 4 byte transpose (v_perm_b32) turns the four band dwords into four pixel dwords at spp == 4.
+// VGPRs / SGPRs per instantiation (gfx950, spp = 1 .. 4): uint8 22 / 40, 22 / 46, 27 / 48, 32 / 58; uint16 21 / 35, 26 / 43, 33 / 43,
+// 38 / 47; float32 20 / 31, 25 / 37, 28 / 41, 28 / 43; the predictor-3 kernel 23 / 46 and 2 064 B of LDS. Eight waves per SIMD
+// everywhere; the integer kernels use no LDS and no barrier; nothing spills to scratch.
+template <int spp>
+__global__ __launch_bounds__(256) void tiff_planes_to_image_u8_kernel(const uint8_t* __restrict__ blocks, int64_t block_cap, int bw, int bh,
+                                                                      int blocks_across, int blocks_down, int plane_mask, int predictor,
+                                                                      int flags, uint8_t* __restrict__ image, int width, int height) {
+    const int lane = threadIdx.x & 63;
+    const int y = blockIdx.x * 4 + (threadIdx.x >> 6), bx = blockIdx.y;
+    if (y >= height) return;
+    const uint8_t* src[spp];
+    planar_rows<spp>(blocks, block_cap, bw, bh, blocks_across, blocks_down, plane_mask, y, bx, src);
+    const int x0 = bx * bw;
+    const int valid = min(bw, width - x0);
+    uint8_t* dst = image + ((int64_t)y * width + x0) * spp;
+    uint32_t carry = 0;                                    // byte c: band c's running sum before this step (the same in every lane)
+    for (int p0 = 0; p0 < valid; p0 += 256) {
+        const int p = p0 + 4 * lane;
+        uint32_t v[spp];
+#pragma unroll
+        for (int c = 0; c < spp; ++c) {
+            v[c] = 0;
+            if (!src[c]) continue;
+            if (flags & PL_LOAD_DWORDS) {                  // bw is a multiple of 4: the dword lies inside the row or past it
+                if (p < bw) v[c] = *reinterpret_cast<const uint32_t*>(src[c] + p);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (p + j < bw) v[c] |= (uint32_t)src[c][p + j] << (8 * j);
+            }
+        }
+        if (predictor == 2) {
+            uint32_t incl = 0;
+#pragma unroll
+            for (int c = 0; c < spp; ++c) {
+                v[c] = add_bytes(v[c], v[c] << 8);
+                v[c] = add_bytes(v[c], v[c] << 16);
+                incl |= (v[c] >> 24) << (8 * c);
+            }
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const uint32_t up = (uint32_t)__shfl_up((int)incl, d);
+                if (lane >= d) incl = add_bytes(incl, up);
+            }
+            uint32_t excl = (uint32_t)__shfl_up((int)incl, 1);
+            excl = add_bytes(lane ? excl : 0u, carry);
+            carry = add_bytes(carry, (uint32_t)__builtin_amdgcn_readlane((int)incl, 63));
+#pragma unroll
+            for (int c = 0; c < spp; ++c) v[c] = add_bytes(v[c], ((excl >> (8 * c)) & 255u) * 0x01010101u);
+        }
+        if constexpr (spp == 4) {
+            if (flags & PL_STORE_DWORDS) {
+                // v_perm_b32(hi, lo, sel): selector bytes 0-3 pick from lo, 4-7 from hi
+                const uint32_t a = __builtin_amdgcn_perm(v[1], v[0], 0x05010400u), b = __builtin_amdgcn_perm(v[1], v[0], 0x07030602u);
+                const uint32_t e = __builtin_amdgcn_perm(v[3], v[2], 0x05010400u), f = __builtin_amdgcn_perm(v[3], v[2], 0x07030602u);
+                const uint32_t px[4] = {__builtin_amdgcn_perm(e, a, 0x05040100u), __builtin_amdgcn_perm(e, a, 0x07060302u),
+                                        __builtin_amdgcn_perm(f, b, 0x05040100u), __builtin_amdgcn_perm(f, b, 0x07060302u)};
+                uint32_t* d32 = reinterpret_cast<uint32_t*>(dst);
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (p + j < valid) d32[p + j] = px[j];
+                continue;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (p + j < valid) {
+#pragma unroll
+                for (int c = 0; c < spp; ++c) dst[(int64_t)(p + j) * spp + c] = (uint8_t)(v[c] >> (8 * j));
+            }
+    }
+}
+
+// uint16 (two samples per lane and band) and the bit patterns of float32 with predictor 1 or 2 (one): the running sums are plain
+// 32-bit adds — modulo 2^16 is their low half — one wave scan per band and step.
+template <typename T, int spp>
+__global__ __launch_bounds__(256) void tiff_planes_to_image_kernel(const uint8_t* __restrict__ blocks, int64_t block_cap, int bw, int bh,
+                                                                   int blocks_across, int blocks_down, int plane_mask, int predictor, int flags,
+                                                                   T* __restrict__ image, int width, int height) {
+    constexpr int V = 4 / (int)sizeof(T);
+    const int lane = threadIdx.x & 63;
+    const int y = blockIdx.x * 4 + (threadIdx.x >> 6), bx = blockIdx.y;
+    if (y >= height) return;
+    const uint8_t* rows[spp];
+    planar_rows<spp>(blocks, block_cap, (int64_t)bw * (int64_t)sizeof(T), bh, blocks_across, blocks_down, plane_mask, y, bx, rows);
+    const int x0 = bx * bw;
+    const int valid = min(bw, width - x0);
+    T* dst = image + ((int64_t)y * width + x0) * spp;
+    uint32_t carry[spp];
+#pragma unroll
+    for (int c = 0; c < spp; ++c) carry[c] = 0;
+    for (int p0 = 0; p0 < valid; p0 += 64 * V) {
+        const int p = p0 + V * lane;
+        uint32_t s[spp][V];
+#pragma unroll
+        for (int c = 0; c < spp; ++c) {
+#pragma unroll
+            for (int j = 0; j < V; ++j) s[c][j] = 0;
+            if (!rows[c]) continue;
+            const T* src = reinterpret_cast<const T*>(rows[c]);
+            if (V == 1 || !(flags & PL_LOAD_DWORDS)) {
+#pragma unroll
+                for (int j = 0; j < V; ++j)
+                    if (p + j < bw) s[c][j] = src[p + j];
+            } else if (p < bw) {                           // bw is even: both samples lie inside the row
+                const uint32_t w = *reinterpret_cast<const uint32_t*>(src + p);
+                s[c][0] = w & 0xffffu;
+                s[c][V - 1] = w >> 16;
+            }
+            if (predictor == 2) {
+                if (V == 2) s[c][V - 1] += s[c][0];
+                uint32_t incl = s[c][V - 1];
+#pragma unroll
+                for (int d = 1; d < 64; d <<= 1) {
+                    const uint32_t up = (uint32_t)__shfl_up((int)incl, d);
+                    if (lane >= d) incl += up;
+                }
+                uint32_t excl = (uint32_t)__shfl_up((int)incl, 1);
+                excl = (lane ? excl : 0u) + carry[c];
+                carry[c] += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+#pragma unroll
+                for (int j = 0; j < V; ++j) s[c][j] += excl;
+            }
+        }
+        if constexpr (sizeof(T) == 2 && spp % 2 == 0) {
+            if (flags & PL_STORE_DWORDS) {
+                uint32_t* d32 = reinterpret_cast<uint32_t*>(dst);
+#pragma unroll
+                for (int j = 0; j < V; ++j)
+                    if (p + j < valid) {
+#pragma unroll
+                        for (int c = 0; c < spp; c += 2)
+                            d32[((int64_t)(p + j) * spp + c) >> 1] = (s[c][j] & 0xffffu) | (s[c + 1][j] << 16);
+                    }
+                continue;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < V; ++j)
+            if (p + j < valid) {
+#pragma unroll
+                for (int c = 0; c < spp; ++c) dst[(int64_t)(p + j) * spp + c] = (T)s[c][j];
+            }
+    }
+}
+
+// float32 with predictor 3: a block row of one band is tiff_fp_blocks_to_image_kernel<1>'s row (four byte planes of bw bytes), stored
+// with the raster's pixel stride. One workgroup per (image row, block column, band); the workgroup of a band that was not selected
+// stores that band's zeros. 132 B + 2 KB of LDS as the chunky kernel. The stores of one band are spp dwords apart: with spp > 1 a
+// wave's store covers spp times the lines (the single-band height raster, the case this path is for, stores as the chunky kernel).
+__global__ __launch_bounds__(FP_THREADS) void tiff_fp_planes_to_image_kernel(const uint8_t* __restrict__ blocks, int64_t block_cap, int bw, int bh,
+                                                                             int blocks_across, int blocks_down, int spp, int plane_mask,
+                                                                             uint32_t* __restrict__ image, int width, int height) {
+    __shared__ uint32_t plane_tot[4];
+    __shared__ uint32_t xch[2][4][64];
+    const int y = blockIdx.x, bx = blockIdx.y, c = blockIdx.z;
+    const int x0 = bx * bw;
+    const int nvalid = min(bw, width - x0);
+    uint32_t* dst = image + ((int64_t)y * width + x0) * spp + c;
+    if (!((plane_mask >> c) & 1)) {
+        for (int k = threadIdx.x; k < nvalid; k += FP_THREADS) dst[(int64_t)k * spp] = 0u;
+        return;
+    }
+    const int by = y / bh;
+    const int slot = __builtin_popcount(plane_mask & ((1 << c) - 1));
+    const uint32_t* row = reinterpret_cast<const uint32_t*>(blocks + (((int64_t)slot * blocks_down + by) * blocks_across + bx) * block_cap) +
+                          (int64_t)(y - by * bh) * bw;
+    fp_block_row<1>(row, bw, nvalid, dst, spp, plane_tot, xch);
 }
 
 struct Tickets {
@@ -869,7 +1074,76 @@ td_status blocks_to_image(const char* what, const uint8_t* blocks, int64_t block
     return TD_OK;
 }
 
+// the same for the planes of a band-separate file: blocks_to_image's checks with one sample per pixel in a block, and the plane mask
+template <typename T>
+td_status planes_to_image(const char* what, const uint8_t* blocks, int64_t block_cap, int block_w, int block_h, int blocks_across, int blocks_down,
+                          int spp, int plane_mask, int predictor, T* image, int width, int height, void* stream) {
+    TD_REQUIRE(blocks && image, "%s: null pointer", what);
+    TD_REQUIRE(block_w >= 1 && block_h >= 1 && blocks_across >= 1 && blocks_down >= 1 && width >= 1 && height >= 1, "%s: bad geometry", what);
+    TD_REQUIRE(spp >= 1 && spp <= SC_MAX_SPP && (predictor == 1 || predictor == 2 || (sizeof(T) == 4 && predictor == 3)),
+               "%s: %d samples per pixel, predictor %d", what, spp, predictor);
+    TD_REQUIRE(plane_mask > 0 && plane_mask < (1 << spp), "%s: plane mask 0x%x does not select bands of %d", what, (unsigned)plane_mask, spp);
+    TD_REQUIRE((int64_t)block_w * block_h * (int64_t)sizeof(T) <= block_cap, "%s: a %d x %d block does not fit %lld bytes", what, block_w, block_h,
+               (long long)block_cap);
+    TD_REQUIRE((int64_t)blocks_across * block_w >= width && (int64_t)blocks_down * block_h >= height && (int64_t)(blocks_across - 1) * block_w < width &&
+               (int64_t)(blocks_down - 1) * block_h < height, "%s: %d x %d blocks of %d x %d do not tile a %d x %d raster", what,
+               blocks_across, blocks_down, block_w, block_h, width, height);
+    TD_REQUIRE(blocks_across <= 65535, "%s: too many block columns", what);
+    TD_REQUIRE(block_cap % sizeof(T) == 0 && reinterpret_cast<uintptr_t>(blocks) % sizeof(T) == 0 && reinterpret_cast<uintptr_t>(image) % sizeof(T) == 0,
+               "%s: blocks, image and block_cap must be multiples of the sample size", what);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if constexpr (sizeof(T) == 4) {
+        if (predictor == 3) {
+            hipLaunchKernelGGL(tiff_fp_planes_to_image_kernel, dim3(height, blocks_across, spp), dim3(FP_THREADS), 0, s, blocks, block_cap, block_w,
+                               block_h, blocks_across, blocks_down, spp, plane_mask, image, width, height);
+            TD_KERNEL_CHECK();
+            return TD_OK;
+        }
+    }
+    int flags = 0;
+    if (block_cap % 4 == 0 && reinterpret_cast<uintptr_t>(blocks) % 4 == 0 && (int64_t)block_w * (int64_t)sizeof(T) % 4 == 0) flags |= PL_LOAD_DWORDS;
+    if (reinterpret_cast<uintptr_t>(image) % 4 == 0 && spp * (int)sizeof(T) % 4 == 0) flags |= PL_STORE_DWORDS;
+    const dim3 grid((height + 3) / 4, blocks_across);
+#define TD_PLANES(N)                                                                                                                              \
+    if constexpr (sizeof(T) == 1)                                                                                                                 \
+        hipLaunchKernelGGL((tiff_planes_to_image_u8_kernel<N>), grid, dim3(256), 0, s, blocks, block_cap, block_w, block_h, blocks_across,         \
+                           blocks_down, plane_mask, predictor, flags, image, width, height);                                                      \
+    else                                                                                                                                          \
+        hipLaunchKernelGGL((tiff_planes_to_image_kernel<T, N>), grid, dim3(256), 0, s, blocks, block_cap, block_w, block_h, blocks_across,         \
+                           blocks_down, plane_mask, predictor, flags, image, width, height)
+    switch (spp) {
+        case 1: TD_PLANES(1); break;
+        case 2: TD_PLANES(2); break;
+        case 3: TD_PLANES(3); break;
+        default: TD_PLANES(4); break;
+    }
+#undef TD_PLANES
+    TD_KERNEL_CHECK();
+    return TD_OK;
+}
+
 }  // namespace
+
+extern "C" td_status td_tiff_planes_to_image_dev(const uint8_t* blocks, int64_t block_cap, int block_w, int block_h, int blocks_across,
+                                                 int blocks_down, int spp, int plane_mask, int predictor, uint8_t* image, int width, int height,
+                                                 void* stream) {
+    return planes_to_image<uint8_t>("td_tiff_planes_to_image_dev", blocks, block_cap, block_w, block_h, blocks_across, blocks_down, spp, plane_mask,
+                                    predictor, image, width, height, stream);
+}
+
+extern "C" td_status td_tiff_planes_to_image_u16_dev(const uint8_t* blocks, int64_t block_cap, int block_w, int block_h, int blocks_across,
+                                                     int blocks_down, int spp, int plane_mask, int predictor, uint16_t* image, int width,
+                                                     int height, void* stream) {
+    return planes_to_image<uint16_t>("td_tiff_planes_to_image_u16_dev", blocks, block_cap, block_w, block_h, blocks_across, blocks_down, spp,
+                                     plane_mask, predictor, image, width, height, stream);
+}
+
+extern "C" td_status td_tiff_planes_to_image_f32_dev(const uint8_t* blocks, int64_t block_cap, int block_w, int block_h, int blocks_across,
+                                                     int blocks_down, int spp, int plane_mask, int predictor, float* image, int width, int height,
+                                                     void* stream) {
+    return planes_to_image<uint32_t>("td_tiff_planes_to_image_f32_dev", blocks, block_cap, block_w, block_h, blocks_across, blocks_down, spp,
+                                     plane_mask, predictor, reinterpret_cast<uint32_t*>(image), width, height, stream);
+}
 
 extern "C" td_status td_tiff_blocks_to_image_dev(const uint8_t* blocks, int64_t block_cap, int block_w, int block_h, int blocks_across,
                                                  int blocks_down, int spp, int predictor, uint8_t* image, int width, int height,

@@ -223,6 +223,7 @@ def predict_on_model(config, model_path, tiles_path, output_path, batch_size=10,
                           pipeline=config.get("pipeline", True), device_contours=config.get("device_contours", "auto"),
                           device_decode=config.get("device_decode", "auto"),
                           device_decode_long_jpeg=config.get("device_decode_long_jpeg", False),
+                          device_decode_planar=config.get("device_decode_planar", False),
                           sharded_epilogue=epilogue)
     try:
         shard_by = resolve_shard_by(config, W, predictor.sharded_epilogue, len(images_paths))

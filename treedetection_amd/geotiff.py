@@ -379,15 +379,19 @@ class GeoTiff:
         return out
 
     # -- compressed raster → HBM (tiffdecode.hip) --------------------------------------------------------------------------
-    def device_decodable(self, float_samples: bool = False, long_segments: bool = False) -> bool:
+    def device_decodable(self, float_samples: bool = False, long_segments: bool = False, planar: bool = False) -> bool:
         """True when the raster's blocks can be decoded on the GPU: LZW, DEFLATE (zlib) or ZSTD strips or tiles of pixel-interleaved
         uint8 or native-order (little-endian) uint16 samples (<= 4 per pixel), predictor 1 or 2; JPEG (compression 7) grey,
         three-band or four-band blocks when the host plan (td_tiff_jpeg_plan: sequential Huffman, 8-bit, 4:4:4 / 4:2:2 / 4:2:0, four
         components all 1x1 and stored as they are) accepts every one of them. ``float_samples=True`` (the height raster of the post-processing stage; the tile loop never asks) also admits
         native-order float32 samples in the same LZW / DEFLATE / ZSTD layouts, predictor 1, 2 or 3 (floating-point predictor). Everything
-        else keeps the host reader: big-endian and planar files, PackBits, int16 / int32 and float64 samples, 12-bit JPEG — and JPEG
+        else keeps the host reader: big-endian files, planar files (unless ``planar=True``, below), PackBits, int16 / int32 and float64 samples, 12-bit JPEG — and JPEG
         rasters with an entropy-coded segment beyond JPEG_DEVICE_MAX_SEGMENT (blocks without restart markers), unless
-        ``long_segments=True``: ``decode_to_device(long_segments=True)`` decodes such segments with a whole wave each."""
+        ``long_segments=True``: ``decode_to_device(long_segments=True)`` decodes such segments with a whole wave each.
+        ``planar=True`` (the ``device_decode_planar`` config key; default off) admits band-separate files (PlanarConfiguration = 2: one
+        grid of blocks per band) under otherwise the same rules — LZW / DEFLATE / ZSTD, the same sample types, band counts and
+        predictors, a block (one sample per pixel) below 2^31 bytes; ``decode_to_device(planar=True)`` decodes their planes with the
+        same decoders and interleaves them in one launch (td_tiff_planes_to_image*_dev). Planar JPEG keeps the host reader."""
         self._setup_blocks()
         if self.compression == 7:
             if not (hasattr(self, "_jpeg_tables") and self._counts is not None and self._pil is None and self._flat is None):
@@ -395,9 +399,46 @@ class GeoTiff:
             plan = self._jpeg_plan()
             return plan is not None and (long_segments or int(plan[1][:, 1].max()) <= self.JPEG_DEVICE_MAX_SEGMENT)
         f32 = float_samples and self.dtype.kind == "f" and self.dtype.itemsize == 4 and self.dtype.isnative
-        return (self.compression in (5, 8, 32946, 50000) and self.planar == 1 and (self._device_samples() or f32) and 1 <= self.count <= 4
+        layout = self.planar == 1 or (bool(planar) and self.planar == 2)
+        return (self.compression in (5, 8, 32946, 50000) and layout and (self._device_samples() or f32) and 1 <= self.count <= 4
                 and self._predictor in ((1, 2, 3) if f32 else (1, 2)) and self._counts is not None and self._pil is None
-                and self._bw * self._bh * self.count * self.dtype.itemsize < (1 << 31))
+                and self._bw * self._bh * (self.count if self.planar == 1 else 1) * self.dtype.itemsize < (1 << 31))
+
+    def device_block_plan(self, bands: Optional[Sequence[int]] = None):
+        """What ``decode_to_device`` reads and decodes, worked out on the host (no GPU): → (planes, plane_mask, offsets, counts, expect,
+        ranges). A pixel-interleaved file has one "plane" (0) whose blocks hold every band, and ``bands`` is refused. A band-separate
+        file has one grid of nx x ny blocks per band: ``bands`` (band indices, any order, default all) picks the planes — ascending in
+        ``planes``, bit p of ``plane_mask`` for band p — and only their blocks are listed: ``offsets`` / ``counts`` are the file's
+        own (int64, plane after plane, within a plane the file's order), ``expect`` is what each block must decode to in bytes (every
+        plane of a strip file ends in its own short strip). ``ranges`` are the byte ranges [(lo, hi), ...] of the file that hold
+        those blocks, one per plane, ascending, merged where they overlap or lie within 4 KB of each other: what is read and copied to the device."""
+        self._setup_blocks()
+        per = self._nx * self._ny
+        item = self.dtype.itemsize
+        if self.planar != 2:
+            if bands is not None:
+                raise ValueError(f"{self.path}: bands={tuple(bands)!r} picks planes of a band-separate file; this one is pixel-interleaved")
+            planes, cb = [0], self.count
+        else:
+            planes, cb = sorted(set(int(b) for b in (range(self.count) if bands is None else bands))), 1
+            if not planes or planes[0] < 0 or planes[-1] >= self.count or (bands is not None and len(planes) != len(list(bands))):
+                raise ValueError(f"{self.path}: bands={tuple(bands)!r} must be distinct band indices below {self.count}")
+        if self._counts is None or len(self._offs) != len(self._counts) or len(self._offs) != per * (self.count if self.planar == 2 else 1):
+            raise ValueError(f"{self.path}: {len(self._offs)} block offsets for {per} blocks per plane")
+        idx = np.concatenate([np.arange(p * per, (p + 1) * per) for p in planes])
+        offs = np.asarray(self._offs, dtype=np.int64)[idx]
+        cnts = np.asarray(self._counts, dtype=np.int64)[idx]
+        one = np.array([self._block_rows(by) * self._bw * cb * item for by in range(self._ny) for _ in range(self._nx)], dtype=np.int64)
+        expect = np.tile(one, len(planes))
+        spans = sorted((int(offs[i * per:(i + 1) * per].min()), int((offs + cnts)[i * per:(i + 1) * per].max())) for i in range(len(planes)))
+        ranges = [spans[0]]
+        for lo, hi in spans[1:]:
+            if lo <= ranges[-1][1] + 4096:                 # (writers pad blocks to even or page offsets: a small gap is read with its neighbours)
+                ranges[-1] = (ranges[-1][0], max(ranges[-1][1], hi))
+            else:
+                ranges.append((lo, hi))
+        mask = sum(1 << p for p in planes) if self.planar == 2 else 1
+        return planes, mask, offs, cnts, expect, ranges
 
     def _device_samples(self) -> bool:
         """Sample types the device kernels take as they lie in the file: uint8, and uint16 in the host's (= the GPU's) byte order."""
@@ -443,7 +484,7 @@ class GeoTiff:
         return plan
 
     def decode_to_device(self, device, stream=None, pinned=None, pool=None, long_segments: bool = False, long_threshold: Optional[int] = None,
-                         subseq_bytes: Optional[int] = None):
+                         subseq_bytes: Optional[int] = None, planar: bool = False, bands: Optional[Sequence[int]] = None):
         """The whole raster decoded in HBM: the compressed blocks are read as they lie in the file (one pread of the span that
         holds them, into pinned memory), copied to the device once, decoded one wave per block (td_tiff_lzw_decode_dev / td_tiff_zstd_decode_dev /
         td_tiff_inflate_verified_dev, which also checks every DEFLATE block's Adler-32 trailer as zlib does; JPEG: one lane per
@@ -457,19 +498,26 @@ class GeoTiff:
         ``long_segments`` (JPEG only): entropy-coded segments of more than ``long_threshold`` bytes (default JPEG_DEVICE_MAX_SEGMENT;
         0: every segment) are decoded by one wave each, in subsequences of ``subseq_bytes`` (default JPEG_SYNC_SUBSEQ), the others one
         per lane as ever (td_tiff_jpeg_decode_long_dev); ``check`` then carries ``.long_segments`` (how many took the wave) and
-        ``.sync_rounds`` (walk rounds per window of 64 subsequences, mean; 1.0 = every guess was right)."""
+        ``.sync_rounds`` (walk rounds per window of 64 subsequences, mean; 1.0 = every guess was right).
+        ``planar=True`` takes band-separate files too (``device_decodable(planar=True)``): every plane's blocks go through the same
+        decoders, one sample per pixel, and td_tiff_planes_to_image_dev / _u16_dev / _f32_dev interleaves them into the same
+        [height, width, bands] tensor in one launch. ``bands`` (band-separate files only; ValueError otherwise): the band indices that
+        are needed — only their planes are read from the file, copied and decoded (:meth:`device_block_plan`); the image keeps all its
+        channels, the others are 0, and ``check.compressed_bytes`` counts what was copied."""
         import torch
         from . import _lib
-        if not self.device_decodable(float_samples=True, long_segments=long_segments):
+        if not self.device_decodable(float_samples=True, long_segments=long_segments, planar=planar):
             raise ValueError(f"{self.path}: not decodable on the device (compression {self.compression}, {self.dtype}, {self.count} bands)")
         lib = _lib.load()
         dev = torch.device(device)
-        offs = np.asarray(self._offs, dtype=np.int64)
-        cnts = np.asarray(self._counts, dtype=np.int64)
-        nb = self._nx * self._ny
-        assert len(offs) == nb == len(cnts)
-        lo, hi = int(offs.min()), int((offs + cnts).max())
-        span = hi - lo
+        planes, plane_mask, offs, cnts, expect, ranges = self.device_block_plan(bands)
+        nb = len(offs)
+        # the ranges of the file that hold the blocks lie one behind the other in the buffer (one range, unless planes were left out)
+        starts = np.cumsum([0] + [hi - lo for lo, hi in ranges])
+        span = int(starts[-1])
+        lo = ranges[0][0]
+        which = np.searchsorted(np.array([r[0] for r in ranges], dtype=np.int64), offs, side="right") - 1
+        rel = offs - np.array([r[0] for r in ranges], dtype=np.int64)[which] + starts[:-1][which]
         if pinned is not None and pinned and pinned[0] is not None and pinned[0].numel() >= span + 16:
             pin = pinned[0]
         else:
@@ -479,17 +527,17 @@ class GeoTiff:
         buf = pin.numpy()
         fd = os.open(self.path, os.O_RDONLY)
 
-        def read_piece(pr):
+        def read_piece(pr):                                     # (position in the buffer, bytes, position in the file)
             got = 0
             view = memoryview(buf)[pr[0]:pr[0] + pr[1]]
             while got < pr[1]:
-                n = os.preadv(fd, [view[got:]], lo + pr[0] + got)
+                n = os.preadv(fd, [view[got:]], pr[2] + got)
                 if n <= 0:
                     raise ValueError(f"{self.path}: file ends inside its block data")
                 got += n
         try:
             piece = 8 << 20
-            parts = [(p, min(piece, span - p)) for p in range(0, span, piece)]
+            parts = [(int(s0) + p, min(piece, r1 - r0 - p), r0 + p) for s0, (r0, r1) in zip(starts, ranges) for p in range(0, r1 - r0, piece)]
             if pool is not None and len(parts) > 1:
                 list(pool.map(read_piece, parts))
             else:
@@ -499,8 +547,7 @@ class GeoTiff:
             os.close(fd)
         buf[span:] = 0
         item = self.dtype.itemsize                              # block sizes, capacities and what a block must decode to count BYTES
-        block_cap = self._bw * self._bh * self.count * item
-        expect = np.array([self._block_rows(by) * self._bw * self.count * item for by in range(self._ny) for _ in range(self._nx)], dtype=np.int64)
+        block_cap = self._bw * self._bh * (self.count if self.planar == 1 else 1) * item
         ctx = torch.cuda.stream(stream) if stream is not None else _NullCtx()
         with torch.cuda.device(dev), ctx:
             st = _lib.stream_ptr()
@@ -508,7 +555,7 @@ class GeoTiff:
             k0, k1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             if self.compression == 7:
                 return self._jpeg_to_device(dev, pin, comp, lo, span, k0, k1, long_segments, long_threshold, subseq_bytes)
-            meta = torch.from_numpy(np.stack([offs - lo, cnts])).to(dev, non_blocking=True)
+            meta = torch.from_numpy(np.stack([rel, cnts])).to(dev, non_blocking=True)
             blocks = torch.empty((nb, block_cap), dtype=torch.uint8, device=dev)
             decoded = torch.empty((nb,), dtype=torch.int64, device=dev)
             status = torch.empty((2 * nb + 1,), dtype=torch.int32, device=dev)      # [nb] status + scratch of the wide-table pass
@@ -527,10 +574,15 @@ class GeoTiff:
                 _lib.check(lib.td_tiff_inflate_verified_dev(comp.data_ptr(), meta[0].data_ptr(), meta[1].data_ptr(), nb, blocks.data_ptr(), block_cap,
                                                             decoded.data_ptr(), status.data_ptr(), ends.data_ptr(), st), "td_tiff_inflate_verified_dev")
             image = torch.empty((self.height, self.width, self.count), dtype={1: torch.uint8, 2: torch.uint16, 4: torch.float32}[item], device=dev)
-            sname = {1: "td_tiff_blocks_to_image_dev", 2: "td_tiff_blocks_to_image_u16_dev", 4: "td_tiff_blocks_to_image_f32_dev"}[item]
-            scatter = getattr(lib, sname)
-            _lib.check(scatter(blocks.data_ptr(), block_cap, self._bw, self._bh, self._nx, self._ny, self.count,
-                               self._predictor, image.data_ptr(), self.width, self.height, st), sname)
+            if self.planar == 2:
+                sname = {1: "td_tiff_planes_to_image_dev", 2: "td_tiff_planes_to_image_u16_dev", 4: "td_tiff_planes_to_image_f32_dev"}[item]
+                _lib.check(getattr(lib, sname)(blocks.data_ptr(), block_cap, self._bw, self._bh, self._nx, self._ny, self.count, plane_mask,
+                                               self._predictor, image.data_ptr(), self.width, self.height, st), sname)
+            else:
+                sname = {1: "td_tiff_blocks_to_image_dev", 2: "td_tiff_blocks_to_image_u16_dev", 4: "td_tiff_blocks_to_image_f32_dev"}[item]
+                scatter = getattr(lib, sname)
+                _lib.check(scatter(blocks.data_ptr(), block_cap, self._bw, self._bh, self._nx, self._ny, self.count,
+                                   self._predictor, image.data_ptr(), self.width, self.height, st), sname)
             k1.record()
             done = torch.cuda.Event()
             done.record()
@@ -551,11 +603,13 @@ class GeoTiff:
             bad = np.nonzero((st_h.numpy() != 0) | (produced != expect))[0]
             if bad.size:
                 b = int(bad[0])
+                per = nb // len(planes)
+                fb = planes[b // per] * per + b % per           # the block's number in the file (planes that were left out count)
                 if self.compression in (8, 32946) and int(st_h[b]) == 3:
-                    raise ValueError(f"{self.path}: block {b}: Adler-32 mismatch (status 3): its {int(produced[b])} decoded bytes do not sum to the stream's trailer")
+                    raise ValueError(f"{self.path}: block {fb}: Adler-32 mismatch (status 3): its {int(produced[b])} decoded bytes do not sum to the stream's trailer")
                 if self.compression == 50000 and int(st_h[b]) == 4:
-                    raise ValueError(f"{self.path}: block {b}: declined by the device decoder (status 4): a content checksum, a second frame or a skippable frame")
-                raise ValueError(f"{self.path}: block {b} decodes to {int(produced[b])} bytes (status {int(st_h[b])}), expected {int(expect[b])}")
+                    raise ValueError(f"{self.path}: block {fb}: declined by the device decoder (status 4): a content checksum, a second frame or a skippable frame")
+                raise ValueError(f"{self.path}: block {fb} decodes to {int(produced[b])} bytes (status {int(st_h[b])}), expected {int(expect[b])}")
             return image
         check.event = done
         check.compressed_bytes = span
@@ -822,6 +876,17 @@ def device_decode_long_jpeg_setting(value=False) -> bool:
         value = False
     if not any(value is v for v in (True, False)) and value not in ("true", "false"):
         raise ValueError(f"device_decode_long_jpeg must be true or false, got {value!r}")
+    return value in (True, "true")
+
+
+def device_decode_planar_setting(value=False) -> bool:
+    """The ``device_decode_planar`` config key as both stages read it: true / false (default) → whether band-separate rasters
+    (PlanarConfiguration = 2) go to the device decoders too (``device_decodable(planar=True)``), where ``device_decode`` sends rasters
+    there at all. Anything else is refused."""
+    if value is None:
+        value = False
+    if not any(value is v for v in (True, False)) and value not in ("true", "false"):
+        raise ValueError(f"device_decode_planar must be true or false, got {value!r}")
     return value in (True, "true")
 
 

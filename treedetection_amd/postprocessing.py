@@ -30,7 +30,7 @@ import torch
 import yaml
 
 from . import _lib
-from .geotiff import GeoTiff, device_decode_long_jpeg_setting, device_decode_setting
+from .geotiff import GeoTiff, device_decode_long_jpeg_setting, device_decode_planar_setting, device_decode_setting
 from .gpkg import polygon_blob, read_layer, write_blobs
 from .stitching import simplify_ring
 
@@ -454,17 +454,18 @@ def _height_on_device(hg: GeoTiff, h_scale: float, config, device: int):
     """The height raster decoded in HBM (GeoTiff.decode_to_device → float32 CUDA tensor [rows, cols], which td_crown_stats reads
     where it lies: no inflate on the host, no copy of the array) and, when ``height_scaling_factor`` shrinks it, decimated there
     (:func:`resample_on_device`, mode "f32"); or None when the host reader has to serve it: ``device_decode``
-    is not explicitly true / "all" (the default "auto" keeps the host reader for this raster: DESIGN.md §7), the raster is not a single-band native float32 LZW / DEFLATE / ZSTD raster (``device_decodable(float_samples=True)``), the
+    is not explicitly true / "all" (the default "auto" keeps the host reader for this raster: DESIGN.md §7), the raster is not a single-band native float32 LZW / DEFLATE / ZSTD raster (``device_decodable(float_samples=True)``; band-separate by its tag only with ``device_decode_planar: true``), the
     scaling factor enlarges it (a factor above 1 stays host numpy), or a block turns out corrupt (printed, like the prediction stage)."""
     if not _device_decode_on(config):
         return None
     out_h, out_w = int(hg.height * h_scale), int(hg.width * h_scale)
     if hg.count != 1 or not (1 <= out_h <= hg.height and 1 <= out_w <= hg.width):
         return None
-    if not hg.device_decodable(float_samples=True):
+    planar = _planar_on(config)
+    if not hg.device_decodable(float_samples=True, planar=planar):
         return None
     try:
-        _, check = hg.decode_to_device(torch.device("cuda", device))
+        _, check = hg.decode_to_device(torch.device("cuda", device), planar=planar)
         height = check().view(hg.height, hg.width)
     except ValueError as e:
         print(f"device decode of {hg.path} failed ({e}): using the host reader")
@@ -487,22 +488,35 @@ def _long_jpeg_on(config) -> bool:
     return device_decode_long_jpeg_setting(config.get("device_decode_long_jpeg", False))
 
 
+def _planar_on(config) -> bool:
+    """``device_decode_planar`` as the Predictor reads it: band-separate rasters take the device path too."""
+    return device_decode_planar_setting(config.get("device_decode_planar", False))
+
+
+# what the last _ndvi_on_device call copied to the device: {"planes": how many were decoded, "compressed_bytes": their bytes} (tests,
+# measurements: a band-separate RGBI raster gives up only bands 0 and 3)
+ndvi_decode_stats = {"planes": 0, "compressed_bytes": 0}
+
+
 def _ndvi_on_device(rg: GeoTiff, n_scale: float, config, device: int):
     """The NDVI raster of the crown statistics computed in HBM: the RGBI raster decoded there (GeoTiff.decode_to_device), bands 0 and
     3 resampled to [int(rows * n_scale), int(cols * n_scale)] and turned into NDVI by one call of td_resample_gdal_dev (mode "ndvi";
     with ``n_scale`` 1 the same kernels run with identity taps) → float32 CUDA tensor for :func:`crown_stats`. None when the host
     reader has to serve it, by the gating of :func:`_height_on_device`: ``device_decode`` not explicitly true / "all", a raster that
-    is not uint8 with four bands in a layout the device decoders take (LZW / DEFLATE / JPEG, pixel-interleaved; JPEG blocks without
-    restart markers only with ``device_decode_long_jpeg: true``), or a corrupt block (printed)."""
+    is not uint8 with four bands in a layout the device decoders take (LZW / DEFLATE / ZSTD / JPEG, pixel-interleaved; JPEG blocks without
+    restart markers only with ``device_decode_long_jpeg: true``; band-separate LZW / DEFLATE / ZSTD files only with ``device_decode_planar: true``
+    — of those only the planes of bands 0 and 3 are read, copied and decoded, the tensor's other channels are 0), or a corrupt block (printed)."""
     if not _device_decode_on(config):
         return None
     out_h, out_w = int(rg.height * n_scale), int(rg.width * n_scale)
-    long_jpeg = _long_jpeg_on(config)
-    if rg.dtype != np.uint8 or rg.count < 4 or out_h < 1 or out_w < 1 or not rg.device_decodable(long_segments=long_jpeg):
+    long_jpeg, planar = _long_jpeg_on(config), _planar_on(config)
+    if rg.dtype != np.uint8 or rg.count < 4 or out_h < 1 or out_w < 1 or not rg.device_decodable(long_segments=long_jpeg, planar=planar):
         return None
+    bands = (0, 3) if rg.planar == 2 else None              # NDVI reads red and infrared: the other planes of a band-separate file stay in the file
     try:
-        _, check = rg.decode_to_device(torch.device("cuda", device), long_segments=long_jpeg)
+        _, check = rg.decode_to_device(torch.device("cuda", device), long_segments=long_jpeg, planar=planar, bands=bands)
         rgbi = check()
+        ndvi_decode_stats.update(planes=len(bands) if bands else rg.count, compressed_bytes=check.compressed_bytes)
     except ValueError as e:
         print(f"device decode of {rg.path} failed ({e}): using the host reader")
         return None

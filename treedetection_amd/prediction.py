@@ -24,7 +24,7 @@ from . import _lib
 from . import distributed as D
 from .contours import batch_prediction_files, find_contours, tile_polygons_json, tile_polygons_json_dev, tile_prediction_file, xy
 from .engine import Engine, INPUT_F32_CHW, INPUT_U8_HWC
-from .geotiff import GeoTiff, device_decode_long_jpeg_setting, device_decode_setting
+from .geotiff import GeoTiff, device_decode_long_jpeg_setting, device_decode_planar_setting, device_decode_setting
 from .weights import load_checkpoint
 
 
@@ -187,7 +187,7 @@ class Predictor:
                  precision: str = "fp32", state_dict: Optional[Dict[str, np.ndarray]] = None,
                  return_predictions: bool = True, host_workers: Optional[int] = None, pipeline: bool = True,
                  device_contours: bool = False, sharded_epilogue: str = "rank0", schedule: str = "streams",
-                 device_decode="auto", device_decode_long_jpeg=False):
+                 device_decode="auto", device_decode_long_jpeg=False, device_decode_planar=False):
         """cfg from ``setup_model_cfg``; ``device_type`` = GPU index ("0", 0) as config["device"] carries it.
         ``state_dict`` lets tests and the bench inject weights instead of reading cfg.MODEL.WEIGHTS.
         ``return_predictions=False`` skips rebuilding the Python list ``__call__`` returns (the reference's own caller
@@ -211,6 +211,9 @@ class Predictor:
         # JPEG rasters with entropy-coded segments too long for one lane (blocks without restart markers) go to the device as well, a
         # wave per segment (GeoTiff.decode_to_device(long_segments=True)); off by default (the measurements: DESIGN.md §7)
         self.device_decode_long_jpeg = device_decode_long_jpeg_setting(device_decode_long_jpeg)
+        # band-separate rasters (PlanarConfiguration = 2) go to the device decoders as well, their planes interleaved there
+        # (GeoTiff.decode_to_device(planar=True)); off by default: such files keep the host reader unless asked
+        self.device_decode_planar = device_decode_planar_setting(device_decode_planar)
         self._rasters: Dict[str, "object"] = {}
         self._raster_pool = None
         self._decode_stream = None
@@ -381,7 +384,7 @@ class Predictor:
         raster's bytes copied to the device in large sequential pieces (GeoTiff.upload_to_device) — while the current image
         predicts. ``detection.walk_images`` calls it with the path after the one it submits. uint8 and little-endian uint16 rasters
         qualify (a 16-bit raster stays in HBM as uint16 and its windows become the model's float input there:
-        Engine.preprocess_windows_u16). No-op for rasters the host reader serves (PackBits, planar and big-endian files, int16 and
+        Engine.preprocess_windows_u16). No-op for rasters the host reader serves (PackBits, big-endian files, planar files unless ``device_decode_planar`` is on, int16 and
         float32 samples — ``device_decodable()`` is asked without ``float_samples``: float32 rasters are decoded on the device only
         for the post-processing stage — JPEG blocks the device decoder does not take) and when ``device_decode`` is off."""
         if not self.device_decode or tifpath in self._rasters:
@@ -396,7 +399,7 @@ class Predictor:
         img = None
         try:
             img = GeoTiff(tifpath)
-            decode = img.device_decodable(long_segments=self.device_decode_long_jpeg)
+            decode = img.device_decodable(long_segments=self.device_decode_long_jpeg, planar=self.device_decode_planar)
             if not decode and not (self.device_upload and img.device_uploadable()
                                    and img.height * img.width * img.count * img.dtype.itemsize <= self.device_raster_max_bytes):
                 return None
@@ -409,7 +412,7 @@ class Predictor:
                 self._upload_pool = ThreadPoolExecutor(max_workers=max(1, min(8, host_core_share() // 4)), thread_name_prefix="td-upload")
             if decode:
                 image, check = img.decode_to_device(self.device, self._decode_stream, self._decode_pinned, self._upload_pool,
-                                                    long_segments=self.device_decode_long_jpeg)
+                                                    long_segments=self.device_decode_long_jpeg, planar=self.device_decode_planar)
             else:
                 # an uncompressed raster: its bytes go to HBM in large sequential pieces (GeoTiff.upload_to_device), the windows
                 # are cut there — one memcpy per byte out of the page cache instead of a pread per window row + an H2D per batch
