@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from treedetection_amd import _lib
+from treedetection_amd import device_decode as D
 from treedetection_amd import postprocessing as P
 from treedetection_amd.geotiff import GeoTiff, write_geotiff
 from treedetection_amd.synth import make_tile
@@ -215,6 +216,47 @@ def test_a_band_subset_reads_and_decodes_only_its_planes(tmp_path, dtype, kw):
     # and a planar file without the keyword is refused as ever
     with pytest.raises(ValueError, match="not decodable on the device"):
         GeoTiff(path).decode_to_device("cuda:0")
+
+
+# ---- 3b. the steps by hand, as the measuring tool composes them ---------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["planar_deflate_u8_bands03", "chunky_lzw_u16_p2_strips"])
+def test_the_steps_called_by_hand_give_decode_to_devices_image(tmp_path, name):
+    """device_block_plan → stage_offsets → alloc_block_buffers → launch_block_decoder → launch_layout (tools/raster_decode_bench.py times
+    the launches through these calls): the same bytes as decode_to_device and the host reader, every block's status 0."""
+    path = str(tmp_path / "s.tif")
+    if name.startswith("planar"):
+        img, bands = np.random.default_rng(0).integers(0, 256, (4, 80, 112), dtype=np.uint8), (0, 3)
+        write_geotiff(path, img, T, 25832, compression="deflate", planar=True, tile=(32, 48))
+    else:
+        img, bands = np.random.default_rng(1).integers(0, 65536, (3, 61, 83), dtype=np.uint16), None
+        write_geotiff(path, img, T, 25832, compression="lzw", predictor=2, rows_per_strip=7)
+    g = GeoTiff(path)
+    planes, mask, offs, cnts, expect, ranges = g.device_block_plan(bands)
+    assert len(ranges) == (2 if bands else 1)
+    rel, starts, span = D.stage_offsets(offs, ranges)
+    raw = np.fromfile(path, dtype=np.uint8)
+    comp = torch.from_numpy(np.concatenate([raw[lo:hi] for lo, hi in ranges] + [np.zeros(16, np.uint8)])).cuda()
+    assert comp.numel() == span + 16
+    meta = torch.from_numpy(np.stack([rel, cnts])).cuda()
+    nb, cap = len(offs), g._bw * g._bh * (g.count if g.planar == 1 else 1) * g.dtype.itemsize
+    bufs = D.alloc_block_buffers(g.compression, nb, cap, "cuda")
+    assert bufs.blocks.shape == (nb, cap) and bufs.decoded.shape == (nb,) and bufs.status.shape == (2 * nb + 1,)
+    image = torch.empty((g.height, g.width, g.count), dtype={1: torch.uint8, 2: torch.uint16}[g.dtype.itemsize], device="cuda")
+    sp = _lib.stream_ptr()
+    D.launch_block_decoder(g.compression, comp, meta, bufs, sp)
+    D.launch_layout(bufs.blocks, cap, g._bw, g._bh, g._nx, g._ny, g.count, g._predictor, image, g.width, g.height, sp,
+                    mask if g.planar == 2 else None)
+    torch.cuda.synchronize()
+    assert not bufs.status[:nb].cpu().numpy().any()
+    assert np.array_equal(bufs.decoded.cpu().numpy() & 0xffffffff, expect)
+    got = image.cpu().numpy()
+    _, check = GeoTiff(path).decode_to_device("cuda:0", planar=g.planar == 2, bands=bands)
+    assert np.array_equal(_bytes(got), _bytes(check().cpu().numpy()))
+    host = GeoTiff(path).read()
+    for c in range(g.count):
+        want = host[c] if bands is None or c in bands else np.zeros_like(host[c])
+        assert np.array_equal(_bytes(got[:, :, c]), _bytes(want)), c
+    assert np.array_equal(host, img)
 
 
 # ---- 4. more blocks than decoder waves -------------------------------------------------------------------------------------------------

@@ -4,12 +4,14 @@ subset, the ``device_decode_planar`` setting as the Predictor and the crown stag
 entry points: declared, exported, bound, and refusing bad arguments before anything is launched."""
 import os
 import struct
+import zlib
 
 import numpy as np
 import pytest
 
 from treedetection_amd import _lib
 from treedetection_amd import postprocessing as P
+from treedetection_amd.device_decode import stage_offsets
 from treedetection_amd.geotiff import GeoTiff, device_decode_planar_setting, write_geotiff
 
 from f32_cases import to_big_endian
@@ -125,6 +127,33 @@ def test_the_block_plan_of_a_band_subset(tmp_path):
     assert planes == [0] and mask == 1 and expect.tolist() == [7 * 83 * 4] * 22 + [3 * 83 * 4] and len(ranges) == 1
     with pytest.raises(ValueError, match="bands"):
         c.device_block_plan(bands=(0, 3))
+
+
+def test_staged_blocks_lie_where_stage_offsets_says(tmp_path):
+    """The byte ranges of the plan, one behind the other as decode_to_device stages them: every block's stream begins at its ``rel``
+    (zlib inflates it to the block's size from there), and ``span`` is all that is staged."""
+    path = str(tmp_path / "p.tif")
+    img = np.random.default_rng(0).integers(0, 256, (4, 80, 112), dtype=np.uint8)
+    # (band-separate or not, bands) → ranges, blocks: 3 x 3 tiles per plane
+    for planar, bands, nranges, nb in ((True, (0, 3), 2, 18), (True, None, 1, 36), (False, None, 1, 9)):
+        write_geotiff(path, img, T, 25832, compression="deflate", planar=planar, tile=(32, 48))
+        planes, mask, offs, cnts, expect, ranges = GeoTiff(path).device_block_plan(bands)
+        assert len(ranges) == nranges and len(offs) == nb, (planar, bands, ranges)
+        rel, starts, span = stage_offsets(offs, ranges)
+        raw = open(path, "rb").read()
+        staged = b"".join(raw[lo:hi] for lo, hi in ranges)
+        assert span == len(staged) == sum(hi - lo for lo, hi in ranges)
+        assert starts.tolist() == np.cumsum([0] + [hi - lo for lo, hi in ranges]).tolist()
+        for i in range(nb):
+            assert 0 <= rel[i] and rel[i] + cnts[i] <= span
+            block = zlib.decompress(staged[rel[i]:rel[i] + cnts[i]])
+            assert len(block) == expect[i], (planar, bands, i)
+            # ... and it is THAT block: plane i // 9 of the selected ones, tile (i % 9 // 3, i % 3), its pixels inside the raster
+            by, bx = i % 9 // 3, i % 3
+            want = img[planes[i // 9]:planes[i // 9] + 1] if planar else img
+            want = want[:, by * 32:(by + 1) * 32, bx * 48:(bx + 1) * 48].transpose(1, 2, 0)
+            got = np.frombuffer(block, np.uint8).reshape(32, 48, -1)[:want.shape[0], :want.shape[1]]
+            assert np.array_equal(got, want), (planar, bands, i)
 
 
 def test_the_setting_is_read_alike_and_refuses_anything_else():

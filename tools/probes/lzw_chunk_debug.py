@@ -3,6 +3,7 @@ import sys, os
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from treedetection_amd import _lib
+from treedetection_amd.device_decode import LZW, alloc_block_buffers, launch_block_decoder
 from treedetection_amd.synth import make_tile
 lib = _lib.load()
 rng = np.random.default_rng(0)
@@ -14,13 +15,13 @@ for name, raw in cases.items():
     src = np.frombuffer(raw, np.uint8); enc = np.empty(len(raw) * 2 + 64, np.uint8)
     n = lib.td_tiff_lzw_encode(src.ctypes.data, src.size, enc.ctypes.data, enc.size)
     comp = torch.from_numpy(np.concatenate([enc[:n], np.zeros(16, np.uint8)])).cuda()
-    off = torch.zeros(1, dtype=torch.int64, device="cuda"); nb = torch.tensor([n], dtype=torch.int64, device="cuda")
+    meta = torch.tensor([[0], [n]], dtype=torch.int64, device="cuda")
     cap = len(raw) + 64
     for one in ("1", "0"):
         os.environ["TD_LZW_ONE_BY_ONE"] = one
-        out = torch.zeros((1, cap), dtype=torch.uint8, device="cuda"); dec = torch.zeros(1, dtype=torch.int64, device="cuda")
-        st = torch.full((3,), -1, dtype=torch.int32, device="cuda")
-        _lib.check(lib.td_tiff_lzw_decode_dev(comp.data_ptr(), off.data_ptr(), nb.data_ptr(), 1, out.data_ptr(), cap, dec.data_ptr(), st.data_ptr(), _lib.stream_ptr()), "dec")
+        bufs = alloc_block_buffers(LZW, 1, cap, "cuda")
+        out, dec, st = bufs.blocks.zero_(), bufs.decoded.zero_(), bufs.status.fill_(-1)
+        launch_block_decoder(LZW, comp, meta, bufs, _lib.stream_ptr())
         torch.cuda.synchronize()
         got = out[0, :len(raw)].cpu().numpy()
         d = np.nonzero(got != src)[0]

@@ -30,23 +30,60 @@ import os
 import sys
 import tempfile
 import time
+from types import SimpleNamespace
 
 import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from treedetection_amd import _lib                                  # noqa: E402
+from treedetection_amd.device_decode import alloc_block_buffers, launch_block_decoder, launch_layout, stage_offsets      # noqa: E402
 from treedetection_amd.geotiff import GeoTiff, write_geotiff      # noqa: E402
 from treedetection_amd.synth import make_tile                      # noqa: E402
 
 args = dict(a.split("=", 1) for a in sys.argv[1:] if "=" in a)
 
 
+def timed(fn, reps=7, warmup=1):
+    """HIP events around ``fn()`` on the current stream: ms of ``reps`` runs after ``warmup`` runs that do not count."""
+    out = []
+    for _ in range(warmup + reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        out.append(e0.elapsed_time(e1))
+    return out[warmup:]
+
+
+def staged(g, bands=None):
+    """The raster's compressed blocks on the device as decode_to_device stages them (device_block_plan + stage_offsets), the buffers its
+    launches write, and decode(verified=True) / layout(image): its two launches on the current stream, to be timed apart.
+    → a record of comp, meta, bufs, cap, nb, planes, decode, layout"""
+    planes, mask, offs, cnts, expect, ranges = g.device_block_plan(bands)
+    rel, starts, span = stage_offsets(offs, ranges)
+    comp = torch.zeros((span + 16,), dtype=torch.uint8)
+    for s0, (lo, hi) in zip(starts, ranges):
+        comp[int(s0):int(s0) + hi - lo] = torch.from_numpy(np.fromfile(g.path, dtype=np.uint8, count=hi - lo, offset=lo))
+    comp, meta = comp.cuda(), torch.from_numpy(np.stack([rel, cnts])).cuda()
+    cap = g._bw * g._bh * (g.count if g.planar == 1 else 1) * g.dtype.itemsize
+    bufs = alloc_block_buffers(g.compression, len(offs), cap, "cuda")
+    sp = _lib.stream_ptr()
+
+    def decode(verified=True):
+        launch_block_decoder(g.compression, comp, meta, bufs, sp, verified)
+
+    def layout(image):
+        launch_layout(bufs.blocks, cap, g._bw, g._bh, g._nx, g._ny, g.count, g._predictor, image, g.width, g.height, sp,
+                      mask if g.planar == 2 else None)
+    return SimpleNamespace(comp=comp, meta=meta, bufs=bufs, cap=cap, nb=len(offs), planes=planes, decode=decode, layout=layout)
+
+
 def f32_main():
     from concurrent.futures import ThreadPoolExecutor
     from statistics import median
-    from treedetection_amd import _lib
-    lib = _lib.load()
     side, codec = int(args.get("side", 9000)), args.get("codec", "deflate")
     kw = {"rows_per_strip": int(args["strip"])} if "strip" in args else {"tile": (int(args.get("tile", 256)),) * 2}
     n = -(-side // 1000)
@@ -55,18 +92,6 @@ def f32_main():
     base = "/dev/shm" if os.path.isdir("/dev/shm") else tempfile.gettempdir()
     path = os.path.join(base, f"td_f32bench_{os.getpid()}.tif")
     pinned, pool = [None], ThreadPoolExecutor(max_workers=8)
-    sp = _lib.stream_ptr()
-
-    def timed(fn, reps=7):
-        out = []
-        for _ in range(reps + 1):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            _lib.check(fn(), "launch")
-            e1.record()
-            torch.cuda.synchronize()
-            out.append(e0.elapsed_time(e1))
-        return out[1:]                                      # (the first run is the warm-up)
 
     def wall(fn, reps=5):
         out = []
@@ -106,33 +131,12 @@ def f32_main():
             host_ms = wall(host_blocks, 3)
             pillow_ms = wall(host_pillow, 3) if pred == 3 else None
             # the two launches apart, the raster's compressed blocks already on the device
-            offs, cnts = np.asarray(g._offs, dtype=np.int64), np.asarray(g._counts, dtype=np.int64)
-            lo, nb = int(offs.min()), g._nx * g._ny
-            span = int((offs + cnts).max()) - lo
-            cap = g._bw * g._bh * 4
-            comp = torch.zeros((span + 16,), dtype=torch.uint8)
-            comp[:span] = torch.from_numpy(np.fromfile(path, dtype=np.uint8, count=span, offset=lo))
-            comp = comp.cuda()
-            meta = torch.from_numpy(np.stack([offs - lo, cnts])).cuda()
-            blocks = torch.empty((nb, cap), dtype=torch.uint8, device="cuda")
-            dec = torch.empty((nb,), dtype=torch.int64, device="cuda")
-            ends = torch.empty((nb,), dtype=torch.int64, device="cuda")
-            status = torch.empty((2 * nb + 1,), dtype=torch.int32, device="cuda")
+            dev, nb = staged(g), g._nx * g._ny
             image = torch.empty((side, side), dtype=torch.float32, device="cuda")
-            head = (comp.data_ptr(), meta[0].data_ptr(), meta[1].data_ptr(), nb, blocks.data_ptr(), cap, dec.data_ptr(), status.data_ptr())
-            if codec == "lzw":
-                decode_ms = timed(lambda: lib.td_tiff_lzw_decode_dev(*head, sp))
-                plain_ms = None
-            elif codec == "zstd":
-                lits = torch.empty((int(lib.td_tiff_zstd_scratch_bytes(nb)),), dtype=torch.uint8, device="cuda")
-                decode_ms = timed(lambda: lib.td_tiff_zstd_decode_dev(*head, lits.data_ptr(), lits.numel(), sp))
-                plain_ms = None
-            else:
-                plain_ms = timed(lambda: lib.td_tiff_inflate_dev(*head, sp))
-                decode_ms = timed(lambda: lib.td_tiff_inflate_verified_dev(*head, ends.data_ptr(), sp))
-            assert int((status[:nb] != 0).sum()) == 0
-            scatter_ms = timed(lambda: lib.td_tiff_blocks_to_image_f32_dev(blocks.data_ptr(), cap, g._bw, g._bh, g._nx, g._ny, 1, pred, image.data_ptr(),
-                                                                          side, side, sp))
+            plain_ms = timed(lambda: dev.decode(verified=False)) if codec == "deflate" else None
+            decode_ms = timed(dev.decode)
+            assert int((dev.bufs.status[:nb] != 0).sum()) == 0
+            scatter_ms = timed(lambda: dev.layout(image))
             assert np.array_equal(image.cpu().numpy().view(np.uint32), img[0].view(np.uint32))
             raw = img.nbytes
             r3 = lambda v: None if v is None else [round(t, 3) for t in v]
@@ -148,7 +152,7 @@ def f32_main():
                               "host_pillow_whole_image_plus_h2d_ms": r3(pillow_ms),
                               "host_pillow_median_ms": None if pillow_ms is None else round(median(pillow_ms), 1)}), flush=True)
             g.close()
-            del comp, meta, blocks, dec, ends, status, image
+            del dev, image
         finally:
             if os.path.exists(path):
                 os.unlink(path)
@@ -157,8 +161,6 @@ def f32_main():
 def planar_main():
     from concurrent.futures import ThreadPoolExecutor
     from statistics import median
-    from treedetection_amd import _lib
-    lib = _lib.load()
     side, pred, codec, which = int(args.get("side", 9000)), int(args.get("predictor", 2)), args.get("codec", "lzw"), args.get("path", "device")
     bands = tuple(int(v) for v in args["bands"].split(",")) if "bands" in args else None
     assert which in ("device", "host", "chunky") and (bands is None or which == "device")
@@ -229,46 +231,12 @@ def planar_main():
         line.update(copied_mb=check.compressed_bytes / 1e6, file_to_hbm_ms=r3(wall_ms), file_to_hbm_median_ms=round(median(wall_ms[1:]), 1),
                     file_to_hbm_best_ms=round(min(wall_ms[1:]), 1), both_launches_ms=r3(kernel_ms))
         # the two launches apart, the selected planes' compressed blocks already on the device
-        planes, mask, offs, cnts, expect, ranges = g.device_block_plan(bands)
-        raw = np.fromfile(path, dtype=np.uint8)
-        comp = torch.from_numpy(np.concatenate([raw[lo:hi] for lo, hi in ranges] + [np.zeros(16, np.uint8)])).cuda()
-        starts = np.cumsum([0] + [hi - lo for lo, hi in ranges])
-        r_lo = np.array([r[0] for r in ranges], dtype=np.int64)
-        which_r = np.searchsorted(r_lo, offs, side="right") - 1
-        meta = torch.from_numpy(np.stack([offs - r_lo[which_r] + starts[:-1][which_r], cnts])).cuda()
-        nb, cap = len(offs), g._bw * g._bh * (1 if planar else 4)
-        blocks = torch.empty((nb, cap), dtype=torch.uint8, device="cuda")
-        dec = torch.empty((nb,), dtype=torch.int64, device="cuda")
-        ends = torch.empty((nb,), dtype=torch.int64, device="cuda")
-        status = torch.empty((2 * nb + 1,), dtype=torch.int32, device="cuda")
+        dev = staged(g, bands)
+        nb, planes = dev.nb, dev.planes
         image = torch.empty((side, side, 4), dtype=torch.uint8, device="cuda")
-        sp = _lib.stream_ptr()
-        head = (comp.data_ptr(), meta[0].data_ptr(), meta[1].data_ptr(), nb, blocks.data_ptr(), cap, dec.data_ptr(), status.data_ptr())
-
-        def timed(fn, reps=7):
-            out = []
-            for _ in range(reps + 1):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                _lib.check(fn(), "launch")
-                e1.record()
-                torch.cuda.synchronize()
-                out.append(e0.elapsed_time(e1))
-            return out[1:]                                      # (the first run is the warm-up)
-        if codec == "lzw":
-            decode_ms = timed(lambda: lib.td_tiff_lzw_decode_dev(*head, sp))
-        elif codec == "zstd":
-            lits = torch.empty((int(lib.td_tiff_zstd_scratch_bytes(nb)),), dtype=torch.uint8, device="cuda")
-            decode_ms = timed(lambda: lib.td_tiff_zstd_decode_dev(*head, lits.data_ptr(), lits.numel(), sp))
-        else:
-            decode_ms = timed(lambda: lib.td_tiff_inflate_verified_dev(*head, ends.data_ptr(), sp))
-        assert int((status[:nb] != 0).sum()) == 0
-        if planar:
-            layout_ms = timed(lambda: lib.td_tiff_planes_to_image_dev(blocks.data_ptr(), cap, g._bw, g._bh, g._nx, g._ny, 4, mask, pred, image.data_ptr(),
-                                                                      side, side, sp))
-        else:
-            layout_ms = timed(lambda: lib.td_tiff_blocks_to_image_dev(blocks.data_ptr(), cap, g._bw, g._bh, g._nx, g._ny, 4, pred, image.data_ptr(),
-                                                                      side, side, sp))
+        decode_ms = timed(dev.decode)
+        assert int((dev.bufs.status[:nb] != 0).sum()) == 0
+        layout_ms = timed(lambda: dev.layout(image))
         assert np.array_equal(image.cpu().numpy(), want)
         moved = img.nbytes + len(planes) * (img.nbytes // 4 if planar else img.nbytes)      # one write of the raster + one read of what was decoded
         line.update(blocks=nb, decoder_ms=r3(decode_ms), decoder_median_ms=round(median(decode_ms), 3), layout_ms=r3(layout_ms),
@@ -349,74 +317,29 @@ try:
     extra = {}
     if codec == "deflate":
         # the two launches of td_tiff_inflate_verified_dev apart: the decoder alone, then the checksum launch alone over its output
-        from treedetection_amd import _lib
-        lib = _lib.load()
-        offs, cnts = np.asarray(g._offs, dtype=np.int64), np.asarray(g._counts, dtype=np.int64)
-        lo, nb = int(offs.min()), g._nx * g._ny
-        span = int((offs + cnts).max()) - lo
-        cap = g._bw * g._bh * g.count * g.dtype.itemsize
-        comp = torch.zeros((span + 16,), dtype=torch.uint8)
-        comp[:span] = torch.from_numpy(np.fromfile(path, dtype=np.uint8, count=span, offset=lo))
-        comp = comp.cuda()
-        meta = torch.from_numpy(np.stack([offs - lo, cnts])).cuda()
-        blocks = torch.empty((nb, cap), dtype=torch.uint8, device="cuda")
-        dec = torch.empty((nb,), dtype=torch.int64, device="cuda")
-        ends = torch.empty((nb,), dtype=torch.int64, device="cuda")
-        status = torch.empty((nb,), dtype=torch.int32, device="cuda")
-        head = (comp.data_ptr(), meta[0].data_ptr(), meta[1].data_ptr(), nb, blocks.data_ptr(), cap, dec.data_ptr(), status.data_ptr())
-        sp = _lib.stream_ptr()
-        _lib.check(lib.td_tiff_inflate_verified_dev(*head, ends.data_ptr(), sp), "td_tiff_inflate_verified_dev")
-        assert int((status != 0).sum()) == 0, "a block failed its checksum"
-
-        def timed(fn):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            _lib.check(fn(), "launch")
-            e1.record()
-            torch.cuda.synchronize()
-            return e0.elapsed_time(e1)
-        inflate_ms = [timed(lambda: lib.td_tiff_inflate_dev(*head, sp)) for _ in range(5)]
-        verified_ms = [timed(lambda: lib.td_tiff_inflate_verified_dev(*head, ends.data_ptr(), sp)) for _ in range(5)]
-        checksum_ms = [timed(lambda: lib.td_tiff_adler32_blocks_dev(blocks.data_ptr(), cap, dec.data_ptr(), comp.data_ptr(), meta[0].data_ptr(),
-                                                                    meta[1].data_ptr(), ends.data_ptr(), nb, status.data_ptr(), sp)) for _ in range(5)]
-        assert int((status != 0).sum()) == 0
+        dev = staged(g)
+        bufs, meta, nb, lib, sp = dev.bufs, dev.meta, dev.nb, _lib.load(), _lib.stream_ptr()
+        dev.decode()
+        assert int((bufs.status[:nb] != 0).sum()) == 0, "a block failed its checksum"
+        inflate_ms = timed(lambda: dev.decode(verified=False), 5, 0)
+        verified_ms = timed(dev.decode, 5, 0)
+        checksum_ms = timed(lambda: _lib.check(lib.td_tiff_adler32_blocks_dev(bufs.blocks.data_ptr(), dev.cap, bufs.decoded.data_ptr(), dev.comp.data_ptr(),
+                                                                              meta[0].data_ptr(), meta[1].data_ptr(), bufs.ends.data_ptr(), nb,
+                                                                              bufs.status.data_ptr(), sp), "td_tiff_adler32_blocks_dev"), 5, 0)
+        assert int((bufs.status[:nb] != 0).sum()) == 0
         extra = {"inflate_ms": [round(t, 3) for t in inflate_ms], "inflate_verified_ms": [round(t, 3) for t in verified_ms],
                  "checksum_ms": [round(t, 3) for t in checksum_ms], "checksum_share_of_inflate": min(checksum_ms) / min(inflate_ms)}
-        del comp, meta, blocks, dec, ends, status
+        del dev, bufs, meta
     if codec == "zstd":
         # the launches apart (the decoder, the scatter / predictor kernel), the host reader on host_threads threads (every block through
         # GeoTiff._decode_block: td_tiff_zstd_decode + the predictor), and — once — the whole file through Pillow: how such a file was read before
-        from treedetection_amd import _lib
-        lib = _lib.load()
-        offs, cnts = np.asarray(g._offs, dtype=np.int64), np.asarray(g._counts, dtype=np.int64)
-        lo, nb = int(offs.min()), g._nx * g._ny
-        span = int((offs + cnts).max()) - lo
-        cap = g._bw * g._bh * g.count * g.dtype.itemsize
-        comp = torch.zeros((span + 16,), dtype=torch.uint8)
-        comp[:span] = torch.from_numpy(np.fromfile(path, dtype=np.uint8, count=span, offset=lo))
-        comp = comp.cuda()
-        meta = torch.from_numpy(np.stack([offs - lo, cnts])).cuda()
-        blocks = torch.empty((nb, cap), dtype=torch.uint8, device="cuda")
-        dec = torch.empty((nb,), dtype=torch.int64, device="cuda")
-        status = torch.empty((nb,), dtype=torch.int32, device="cuda")
-        lits = torch.empty((int(lib.td_tiff_zstd_scratch_bytes(nb)),), dtype=torch.uint8, device="cuda")
+        dev = staged(g)
         image = torch.empty((g.height, g.width, g.count), dtype=torch.uint8, device="cuda")
-        sp = _lib.stream_ptr()
-
-        def timed(fn):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            _lib.check(fn(), "launch")
-            e1.record()
-            torch.cuda.synchronize()
-            return e0.elapsed_time(e1)
-        zstd_ms = [timed(lambda: lib.td_tiff_zstd_decode_dev(comp.data_ptr(), meta[0].data_ptr(), meta[1].data_ptr(), nb, blocks.data_ptr(), cap,
-                                                             dec.data_ptr(), status.data_ptr(), lits.data_ptr(), lits.numel(), sp)) for _ in range(5)]
-        assert int((status != 0).sum()) == 0
-        scatter_ms = [timed(lambda: lib.td_tiff_blocks_to_image_dev(blocks.data_ptr(), cap, g._bw, g._bh, g._nx, g._ny, g.count, g._predictor,
-                                                                    image.data_ptr(), g.width, g.height, sp)) for _ in range(5)]
+        zstd_ms = timed(dev.decode, 5, 0)
+        assert int((dev.bufs.status[:dev.nb] != 0).sum()) == 0
+        scatter_ms = timed(lambda: dev.layout(image), 5, 0)
         assert np.array_equal(image.cpu().numpy().transpose(2, 0, 1), img)
-        del comp, meta, blocks, dec, status, lits, image
+        del dev, image
         nth = int(args.get("host_threads", 16))
         keys = [(0, by, bx) for by in range(g._ny) for bx in range(g._nx)]
         host_s, host_decode_s = [], []                             # blocks + stitch + copy / the blocks alone: what the JPEG branch times

@@ -1020,22 +1020,32 @@ extern "C" td_status td_adler32_dev(const uint8_t* data_dev, int64_t n, uint32_t
 
 namespace {
 
-// the checks and the launch of every sample width (four bytes: float32, which alone has predictor 3); `what` names the entry point in messages
+// what both layout launchers ask of their arguments, for every sample width (four bytes: float32, which alone has predictor 3); `what` names
+// the entry point in messages. What a block holds per pixel differs (every sample, or one plane's), so each launcher checks block_cap itself
 template <typename T>
-td_status blocks_to_image(const char* what, const uint8_t* blocks, int64_t block_cap, int block_w, int block_h, int blocks_across, int blocks_down,
-                          int spp, int predictor, T* image, int width, int height, void* stream) {
+td_status check_layout_args(const char* what, const uint8_t* blocks, int64_t block_cap, int block_w, int block_h, int blocks_across, int blocks_down,
+                            int spp, int predictor, const T* image, int width, int height) {
     TD_REQUIRE(blocks && image, "%s: null pointer", what);
     TD_REQUIRE(block_w >= 1 && block_h >= 1 && blocks_across >= 1 && blocks_down >= 1 && width >= 1 && height >= 1, "%s: bad geometry", what);
     TD_REQUIRE(spp >= 1 && spp <= SC_MAX_SPP && (predictor == 1 || predictor == 2 || (sizeof(T) == 4 && predictor == 3)),
                "%s: %d samples per pixel, predictor %d", what, spp, predictor);
-    TD_REQUIRE((int64_t)block_w * block_h * spp * (int64_t)sizeof(T) <= block_cap, "%s: a %d x %d x %d block does not fit %lld bytes", what, block_w,
-               block_h, spp, (long long)block_cap);
     TD_REQUIRE((int64_t)blocks_across * block_w >= width && (int64_t)blocks_down * block_h >= height && (int64_t)(blocks_across - 1) * block_w < width &&
                (int64_t)(blocks_down - 1) * block_h < height, "%s: %d x %d blocks of %d x %d do not tile a %d x %d raster", what,
                blocks_across, blocks_down, block_w, block_h, width, height);
     TD_REQUIRE(blocks_across <= 65535, "%s: too many block columns", what);
     TD_REQUIRE(block_cap % sizeof(T) == 0 && reinterpret_cast<uintptr_t>(blocks) % sizeof(T) == 0 && reinterpret_cast<uintptr_t>(image) % sizeof(T) == 0,
                "%s: blocks, image and block_cap must be multiples of the sample size", what);
+    return TD_OK;
+}
+
+// the launch of every sample width, pixel-interleaved blocks
+template <typename T>
+td_status blocks_to_image(const char* what, const uint8_t* blocks, int64_t block_cap, int block_w, int block_h, int blocks_across, int blocks_down,
+                          int spp, int predictor, T* image, int width, int height, void* stream) {
+    const td_status args = check_layout_args<T>(what, blocks, block_cap, block_w, block_h, blocks_across, blocks_down, spp, predictor, image, width, height);
+    if (args < 0) return args;
+    TD_REQUIRE((int64_t)block_w * block_h * spp * (int64_t)sizeof(T) <= block_cap, "%s: a %d x %d x %d block does not fit %lld bytes", what, block_w,
+               block_h, spp, (long long)block_cap);
     const dim3 grid(height, blocks_across);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if constexpr (sizeof(T) == 1) {
@@ -1074,23 +1084,15 @@ td_status blocks_to_image(const char* what, const uint8_t* blocks, int64_t block
     return TD_OK;
 }
 
-// the same for the planes of a band-separate file: blocks_to_image's checks with one sample per pixel in a block, and the plane mask
+// the same for the planes of a band-separate file: one sample per pixel in a block, and the plane mask
 template <typename T>
 td_status planes_to_image(const char* what, const uint8_t* blocks, int64_t block_cap, int block_w, int block_h, int blocks_across, int blocks_down,
                           int spp, int plane_mask, int predictor, T* image, int width, int height, void* stream) {
-    TD_REQUIRE(blocks && image, "%s: null pointer", what);
-    TD_REQUIRE(block_w >= 1 && block_h >= 1 && blocks_across >= 1 && blocks_down >= 1 && width >= 1 && height >= 1, "%s: bad geometry", what);
-    TD_REQUIRE(spp >= 1 && spp <= SC_MAX_SPP && (predictor == 1 || predictor == 2 || (sizeof(T) == 4 && predictor == 3)),
-               "%s: %d samples per pixel, predictor %d", what, spp, predictor);
+    const td_status args = check_layout_args<T>(what, blocks, block_cap, block_w, block_h, blocks_across, blocks_down, spp, predictor, image, width, height);
+    if (args < 0) return args;
     TD_REQUIRE(plane_mask > 0 && plane_mask < (1 << spp), "%s: plane mask 0x%x does not select bands of %d", what, (unsigned)plane_mask, spp);
     TD_REQUIRE((int64_t)block_w * block_h * (int64_t)sizeof(T) <= block_cap, "%s: a %d x %d block does not fit %lld bytes", what, block_w, block_h,
                (long long)block_cap);
-    TD_REQUIRE((int64_t)blocks_across * block_w >= width && (int64_t)blocks_down * block_h >= height && (int64_t)(blocks_across - 1) * block_w < width &&
-               (int64_t)(blocks_down - 1) * block_h < height, "%s: %d x %d blocks of %d x %d do not tile a %d x %d raster", what,
-               blocks_across, blocks_down, block_w, block_h, width, height);
-    TD_REQUIRE(blocks_across <= 65535, "%s: too many block columns", what);
-    TD_REQUIRE(block_cap % sizeof(T) == 0 && reinterpret_cast<uintptr_t>(blocks) % sizeof(T) == 0 && reinterpret_cast<uintptr_t>(image) % sizeof(T) == 0,
-               "%s: blocks, image and block_cap must be multiples of the sample size", what);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if constexpr (sizeof(T) == 4) {
         if (predictor == 3) {

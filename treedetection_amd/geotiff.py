@@ -11,7 +11,8 @@ block (GDAL does the same through libtiff). The floating-point predictor (predic
 is undone block by block (td_tiff_unpredict_float). Other codecs (old-style JPEG, predictor 3 on float64, ...): whole image through Pillow.
 Whole rasters can instead be decoded on the GPU and kept in HBM (``decode_to_device``): LZW, DEFLATE and ZSTD (tiffdecode.hip, zstddecode.hip; uint8 and
 native-order uint16 samples; native-order float32 height rasters, predictors 1 - 3, for callers that ask for them) and sequential-Huffman
-JPEG (jpegdecode.hip, byte-identical to the Pillow path) — see ``device_decodable``.
+JPEG (jpegdecode.hip, byte-identical to the Pillow path) — see ``device_decodable``. The steps of the device paths (staging, the file
+read, the decoder and layout launches, ``check``) are device_decode.py's; the methods here compose them.
 """
 from __future__ import annotations
 
@@ -25,6 +26,8 @@ from concurrent.futures import ThreadPoolExecutor
 from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
+
+from .device_decode import alloc_block_buffers, finish, launch_block_decoder, launch_layout, read_ranges, stage_offsets
 
 _TYPES = {1: ("B", 1), 2: ("c", 1), 3: ("H", 2), 4: ("I", 4), 5: ("II", 8), 6: ("b", 1), 7: ("B", 1), 8: ("h", 2),
           9: ("i", 4), 10: ("ii", 8), 11: ("f", 4), 12: ("d", 8), 16: ("Q", 8), 17: ("q", 8), 18: ("Q", 8)}
@@ -508,16 +511,10 @@ class GeoTiff:
         from . import _lib
         if not self.device_decodable(float_samples=True, long_segments=long_segments, planar=planar):
             raise ValueError(f"{self.path}: not decodable on the device (compression {self.compression}, {self.dtype}, {self.count} bands)")
-        lib = _lib.load()
         dev = torch.device(device)
         planes, plane_mask, offs, cnts, expect, ranges = self.device_block_plan(bands)
         nb = len(offs)
-        # the ranges of the file that hold the blocks lie one behind the other in the buffer (one range, unless planes were left out)
-        starts = np.cumsum([0] + [hi - lo for lo, hi in ranges])
-        span = int(starts[-1])
-        lo = ranges[0][0]
-        which = np.searchsorted(np.array([r[0] for r in ranges], dtype=np.int64), offs, side="right") - 1
-        rel = offs - np.array([r[0] for r in ranges], dtype=np.int64)[which] + starts[:-1][which]
+        rel, starts, span = stage_offsets(offs, ranges)
         if pinned is not None and pinned and pinned[0] is not None and pinned[0].numel() >= span + 16:
             pin = pinned[0]
         else:
@@ -525,26 +522,10 @@ class GeoTiff:
             if pinned is not None:
                 pinned[:] = [pin]
         buf = pin.numpy()
-        fd = os.open(self.path, os.O_RDONLY)
-
-        def read_piece(pr):                                     # (position in the buffer, bytes, position in the file)
-            got = 0
-            view = memoryview(buf)[pr[0]:pr[0] + pr[1]]
-            while got < pr[1]:
-                n = os.preadv(fd, [view[got:]], pr[2] + got)
-                if n <= 0:
-                    raise ValueError(f"{self.path}: file ends inside its block data")
-                got += n
-        try:
-            piece = 8 << 20
-            parts = [(int(s0) + p, min(piece, r1 - r0 - p), r0 + p) for s0, (r0, r1) in zip(starts, ranges) for p in range(0, r1 - r0, piece)]
-            if pool is not None and len(parts) > 1:
-                list(pool.map(read_piece, parts))
-            else:
-                for pr in parts:
-                    read_piece(pr)
-        finally:
-            os.close(fd)
+        piece = 8 << 20
+        parts = [(int(s0) + p, min(piece, r1 - r0 - p), r0 + p) for s0, (r0, r1) in zip(starts, ranges) for p in range(0, r1 - r0, piece)]
+        for _ in read_ranges(self.path, parts, buf, pool, "block data"):
+            pass
         buf[span:] = 0
         item = self.dtype.itemsize                              # block sizes, capacities and what a block must decode to count BYTES
         block_cap = self._bw * self._bh * (self.count if self.planar == 1 else 1) * item
@@ -554,66 +535,31 @@ class GeoTiff:
             comp = pin[:span + 16].to(dev, non_blocking=True)
             k0, k1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             if self.compression == 7:
-                return self._jpeg_to_device(dev, pin, comp, lo, span, k0, k1, long_segments, long_threshold, subseq_bytes)
+                return self._jpeg_to_device(dev, pin, comp, ranges[0][0], span, k0, k1, long_segments, long_threshold, subseq_bytes)
             meta = torch.from_numpy(np.stack([rel, cnts])).to(dev, non_blocking=True)
-            blocks = torch.empty((nb, block_cap), dtype=torch.uint8, device=dev)
-            decoded = torch.empty((nb,), dtype=torch.int64, device=dev)
-            status = torch.empty((2 * nb + 1,), dtype=torch.int32, device=dev)      # [nb] status + scratch of the wide-table pass
-            ends = torch.empty((nb,), dtype=torch.int64, device=dev) if self.compression in (8, 32946) else None      # DEFLATE: where each trailer begins
-            lits = None
-            if self.compression == 50000:                       # ZSTD: the literal buffers of the resident decoder waves
-                lits = torch.empty((max(int(lib.td_tiff_zstd_scratch_bytes(nb)), 1),), dtype=torch.uint8, device=dev)
+            bufs = alloc_block_buffers(self.compression, nb, block_cap, dev)
             k0.record()
-            if self.compression == 5:
-                _lib.check(lib.td_tiff_lzw_decode_dev(comp.data_ptr(), meta[0].data_ptr(), meta[1].data_ptr(), nb, blocks.data_ptr(), block_cap,
-                                                      decoded.data_ptr(), status.data_ptr(), st), "td_tiff_lzw_decode_dev")
-            elif self.compression == 50000:
-                _lib.check(lib.td_tiff_zstd_decode_dev(comp.data_ptr(), meta[0].data_ptr(), meta[1].data_ptr(), nb, blocks.data_ptr(), block_cap,
-                                                       decoded.data_ptr(), status.data_ptr(), lits.data_ptr(), lits.numel(), st), "td_tiff_zstd_decode_dev")
-            else:
-                _lib.check(lib.td_tiff_inflate_verified_dev(comp.data_ptr(), meta[0].data_ptr(), meta[1].data_ptr(), nb, blocks.data_ptr(), block_cap,
-                                                            decoded.data_ptr(), status.data_ptr(), ends.data_ptr(), st), "td_tiff_inflate_verified_dev")
+            launch_block_decoder(self.compression, comp, meta, bufs, st)
             image = torch.empty((self.height, self.width, self.count), dtype={1: torch.uint8, 2: torch.uint16, 4: torch.float32}[item], device=dev)
-            if self.planar == 2:
-                sname = {1: "td_tiff_planes_to_image_dev", 2: "td_tiff_planes_to_image_u16_dev", 4: "td_tiff_planes_to_image_f32_dev"}[item]
-                _lib.check(getattr(lib, sname)(blocks.data_ptr(), block_cap, self._bw, self._bh, self._nx, self._ny, self.count, plane_mask,
-                                               self._predictor, image.data_ptr(), self.width, self.height, st), sname)
-            else:
-                sname = {1: "td_tiff_blocks_to_image_dev", 2: "td_tiff_blocks_to_image_u16_dev", 4: "td_tiff_blocks_to_image_f32_dev"}[item]
-                scatter = getattr(lib, sname)
-                _lib.check(scatter(blocks.data_ptr(), block_cap, self._bw, self._bh, self._nx, self._ny, self.count,
-                                   self._predictor, image.data_ptr(), self.width, self.height, st), sname)
-            k1.record()
-            done = torch.cuda.Event()
-            done.record()
-            dec_h = torch.empty((nb,), dtype=torch.int64, pin_memory=True)
-            st_h = torch.empty((nb,), dtype=torch.int32, pin_memory=True)
-            dec_h.copy_(decoded, non_blocking=True)
-            st_h.copy_(status[:nb], non_blocking=True)
-            copied = torch.cuda.Event(blocking=True)
-            copied.record()
-        keep = [pin, comp, meta, blocks, decoded, status, ends, lits]     # alive until check() has run: the kernels read them
+            launch_layout(bufs.blocks, block_cap, self._bw, self._bh, self._nx, self._ny, self.count, self._predictor, image, self.width,
+                          self.height, st, plane_mask if self.planar == 2 else None)
+            k1.record()                                    # the decode launches (DEFLATE: + the checksum launch) + the scatter / predictor kernel
 
-        def check():
-            copied.synchronize()
-            check.kernel_ms = k0.elapsed_time(k1)          # the decode launches (DEFLATE: + the checksum launch) + the scatter / predictor kernel
-            keep.clear()
-            produced = dec_h.numpy() & 0xffffffff
-            check.slow_codes = int((dec_h.numpy() >> 32).sum())     # LZW: strings copied through memory (sources older than the LDS ring)
-            bad = np.nonzero((st_h.numpy() != 0) | (produced != expect))[0]
-            if bad.size:
-                b = int(bad[0])
-                per = nb // len(planes)
-                fb = planes[b // per] * per + b % per           # the block's number in the file (planes that were left out count)
-                if self.compression in (8, 32946) and int(st_h[b]) == 3:
-                    raise ValueError(f"{self.path}: block {fb}: Adler-32 mismatch (status 3): its {int(produced[b])} decoded bytes do not sum to the stream's trailer")
-                if self.compression == 50000 and int(st_h[b]) == 4:
-                    raise ValueError(f"{self.path}: block {fb}: declined by the device decoder (status 4): a content checksum, a second frame or a skippable frame")
-                raise ValueError(f"{self.path}: block {fb} decodes to {int(produced[b])} bytes (status {int(st_h[b])}), expected {int(expect[b])}")
-            return image
-        check.event = done
-        check.compressed_bytes = span
-        return image, check
+            def verdict(check, dec_h, st_h):
+                produced = dec_h & 0xffffffff
+                check.slow_codes = int((dec_h >> 32).sum())     # LZW: strings copied through memory (sources older than the LDS ring)
+                bad = np.nonzero((st_h != 0) | (produced != expect))[0]
+                if bad.size:
+                    b = int(bad[0])
+                    per = nb // len(planes)
+                    fb = planes[b // per] * per + b % per           # the block's number in the file (planes that were left out count)
+                    if self.compression in (8, 32946) and int(st_h[b]) == 3:
+                        raise ValueError(f"{self.path}: block {fb}: Adler-32 mismatch (status 3): its {int(produced[b])} decoded bytes do not sum to the stream's trailer")
+                    if self.compression == 50000 and int(st_h[b]) == 4:
+                        raise ValueError(f"{self.path}: block {fb}: declined by the device decoder (status 4): a content checksum, a second frame or a skippable frame")
+                    raise ValueError(f"{self.path}: block {fb} decodes to {int(produced[b])} bytes (status {int(st_h[b])}), expected {int(expect[b])}")
+            keep = [pin, comp, meta, bufs]                 # alive until check() has run: the kernels read them
+            return image, finish(image, k0, k1, [bufs.decoded, bufs.status[:nb]], keep, verdict, span)
 
     def _jpeg_to_device(self, dev, pin, comp, lo, span, k0, k1, long_segments=False, long_threshold=None, subseq_bytes=None):
         """decode_to_device for JPEG blocks (inside its device / stream context, the compressed bytes already on their way to ``comp``):
@@ -635,7 +581,7 @@ class GeoTiff:
         status = torch.empty((nb,), dtype=torch.int32, device=dev)
         image = torch.empty((self.height, self.width, self.count), dtype=torch.uint8, device=dev)
         st = _lib.stream_ptr()
-        nlong, stats, stats_h = 0, None, None
+        nlong, stats = 0, None
         if long_segments:
             limit = self.JPEG_DEVICE_MAX_SEGMENT if long_threshold is None else int(long_threshold)
             is_long = segs[:, 1] > limit
@@ -656,36 +602,19 @@ class GeoTiff:
             _lib.check(lib.td_tiff_jpeg_decode_dev(comp.data_ptr(), info_d.data_ptr(), nb, segs_d.data_ptr(), len(segs), sets_d.data_ptr(),
                                                    coef.data_ptr(), planes.data_ptr(), ncoef, status.data_ptr(), image.data_ptr(), self.width,
                                                    self.height, self.count, self._bw, self._bh, self._nx, st), "td_tiff_jpeg_decode_dev")
-        k1.record()
-        done = torch.cuda.Event()
-        done.record()
-        st_h = torch.empty((nb,), dtype=torch.int32, pin_memory=True)
-        st_h.copy_(status, non_blocking=True)
-        if stats is not None:
-            stats_h = torch.empty((4,), dtype=torch.int64, pin_memory=True)
-            stats_h.copy_(stats, non_blocking=True)
-        copied = torch.cuda.Event(blocking=True)
-        copied.record()
-        keep = [pin, comp, info_d, segs_d, sets_d, coef, planes, status, stats]     # alive until check() has run: the kernels read them
+        k1.record()                                        # entropy decode + IDCT + upsampling / colour
 
-        def check():
-            copied.synchronize()
-            check.kernel_ms = k0.elapsed_time(k1)          # entropy decode + IDCT + upsampling / colour
-            keep.clear()
+        def verdict(check, st_h, stats_h=None):
             if stats_h is not None:                        # rounds, windows, most rounds of a window, windows of one round
                 check.sync_stats = [int(v) for v in stats_h]
                 check.sync_rounds = check.sync_stats[0] / max(1, check.sync_stats[1])
-            bad = np.nonzero(st_h.numpy() != 0)[0]
+            bad = np.nonzero(st_h != 0)[0]
             if bad.size:
                 b = int(bad[0])
                 raise ValueError(f"{self.path}: JPEG block {b} is corrupt (status {int(st_h[b])})")
-            return image
-        check.event = done
-        check.compressed_bytes = span
-        check.segments = len(segs)
-        check.long_segments = nlong
-        check.sync_rounds = 0.0
-        return image, check
+        keep = [pin, comp, info_d, segs_d, sets_d, coef, planes, status, stats]     # alive until check() has run: the kernels read them
+        return image, finish(image, k0, k1, [status] if stats is None else [status, stats], keep, verdict, span,
+                             segments=len(segs), long_segments=nlong, sync_rounds=0.0)
 
     def device_uploadable(self) -> bool:
         """True when the raster's pixels lie in the file as ONE dense [rows, cols, bands] array of uint8 or native-order uint16
@@ -714,54 +643,27 @@ class GeoTiff:
             staging = [torch.empty((4 * piece,), dtype=torch.uint8, pin_memory=True) for _ in range(2)]
         cap = min(t.numel() for t in staging)
         ctx = torch.cuda.stream(stream) if stream is not None else _NullCtx()
-        own_fd = getattr(self, "_fd", None) is None          # (the window reader keeps a descriptor for uint8 files only)
-        fd, base = os.open(self.path, os.O_RDONLY) if own_fd else self._fd, int(self._flat.offset)
-
-        def read_into(view: memoryview, off: int) -> None:
-            got = 0
-            while got < len(view):
-                n = os.preadv(fd, [view[got:]], base + off + got)
-                if n <= 0:
-                    raise ValueError(f"{self.path}: file ends inside its pixel data")
-                got += n
-
-        try:
-            with torch.cuda.device(dev), ctx:
-                image = torch.empty((self.height, self.width, self.count), dtype=torch.uint8 if self.dtype.itemsize == 1 else torch.uint16, device=dev)
-                flat = image.view(-1).view(torch.uint8)
-                events = [None] * len(staging)
-                k = 0
-                for o in range(0, total, cap):
-                    n = min(cap, total - o)
-                    buf = staging[k % len(staging)]
-                    if events[k % len(staging)] is not None:
-                        events[k % len(staging)].synchronize()          # the copy that last used this staging buffer has finished
-                    mv = memoryview(buf.numpy())
-                    parts = [(p, min(piece, n - p)) for p in range(0, n, piece)]
-
-                    def one(pr, mv=mv, o=o):
-                        read_into(mv[pr[0]:pr[0] + pr[1]], o + pr[0])
-                        return pr
-                    # every piece goes to the device as soon as it (and the pieces before it) has been read: copies of a few MB keep
-                    # the DMA queue short for the small result copies of the running forwards (64-MB copies delayed them by a millisecond)
-                    for p0, pn in (pool.map(one, parts) if pool is not None and len(parts) > 1 else map(one, parts)):
-                        flat[o + p0:o + p0 + pn].copy_(buf[p0:p0 + pn], non_blocking=True)
-                    ev = torch.cuda.Event()
-                    ev.record()
-                    events[k % len(staging)] = ev
-                    k += 1
-                done = torch.cuda.Event(blocking=True)
-                done.record()
-        finally:
-            if own_fd:
-                os.close(fd)
-
-        def check():
-            done.synchronize()
-            return image
-        check.event = done
-        check.compressed_bytes = total
-        return image, check
+        base = int(self._flat.offset)
+        with torch.cuda.device(dev), ctx:
+            image = torch.empty((self.height, self.width, self.count), dtype=torch.uint8 if self.dtype.itemsize == 1 else torch.uint16, device=dev)
+            flat = image.view(-1).view(torch.uint8)
+            events = [None] * len(staging)
+            k = 0
+            for o in range(0, total, cap):
+                n = min(cap, total - o)
+                buf = staging[k % len(staging)]
+                if events[k % len(staging)] is not None:
+                    events[k % len(staging)].synchronize()          # the copy that last used this staging buffer has finished
+                parts = [(p, min(piece, n - p), base + o + p) for p in range(0, n, piece)]
+                # every piece goes to the device as soon as it (and the pieces before it) has been read: copies of a few MB keep
+                # the DMA queue short for the small result copies of the running forwards (64-MB copies delayed them by a millisecond)
+                for p0, pn, _ in read_ranges(self.path, parts, buf.numpy(), pool, "pixel data"):
+                    flat[o + p0:o + p0 + pn].copy_(buf[p0:p0 + pn], non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record()
+                events[k % len(staging)] = ev
+                k += 1
+            return image, finish(image, None, None, [], [], None, total)
 
     def _load(self) -> np.ndarray:
         """Whole raster as [bands, rows, cols]."""
@@ -868,26 +770,26 @@ def device_decode_setting(value="auto"):
     return value in (True, "auto", "true", "all"), value == "all"
 
 
+def _true_false_setting(key, value) -> bool:
+    if value is None:
+        value = False
+    if not any(value is v for v in (True, False)) and value not in ("true", "false"):
+        raise ValueError(f"{key} must be true or false, got {value!r}")
+    return value in (True, "true")
+
+
 def device_decode_long_jpeg_setting(value=False) -> bool:
     """The ``device_decode_long_jpeg`` config key as both stages read it: true / false (default) → whether JPEG rasters with segments
     beyond GeoTiff.JPEG_DEVICE_MAX_SEGMENT go to the device too (``device_decodable(long_segments=True)``), where ``device_decode``
     sends rasters there at all. Anything else is refused."""
-    if value is None:
-        value = False
-    if not any(value is v for v in (True, False)) and value not in ("true", "false"):
-        raise ValueError(f"device_decode_long_jpeg must be true or false, got {value!r}")
-    return value in (True, "true")
+    return _true_false_setting("device_decode_long_jpeg", value)
 
 
 def device_decode_planar_setting(value=False) -> bool:
     """The ``device_decode_planar`` config key as both stages read it: true / false (default) → whether band-separate rasters
     (PlanarConfiguration = 2) go to the device decoders too (``device_decodable(planar=True)``), where ``device_decode`` sends rasters
     there at all. Anything else is refused."""
-    if value is None:
-        value = False
-    if not any(value is v for v in (True, False)) and value not in ("true", "false"):
-        raise ValueError(f"device_decode_planar must be true or false, got {value!r}")
-    return value in (True, "true")
+    return _true_false_setting("device_decode_planar", value)
 
 
 class _NullCtx:
