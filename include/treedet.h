@@ -610,7 +610,7 @@ td_status td_crown_stats(const float* raster, int rows, int cols, const double* 
  * uint8 as in mode u8, then (nir / 255 - red / 255) / (nir / 255 + red / 255 + 1e-10) in float64, rounded once. Modes u8 and ndvi
  * take uint8 sources only. Returns TD_ERR_INVALID (with a message, before any launch) for a null pointer, a bad shape, sample type
  * or mode, a band index >= c, or a mode / band count / sample type combination outside the above. Asynchronous on `stream`. */
-enum { TD_SAMPLE_U8 = 0, TD_SAMPLE_F32 = 1 };
+enum { TD_SAMPLE_U8 = 0, TD_SAMPLE_F32 = 1, TD_SAMPLE_U16 = 2 };    /* (U16: td_seam_first_dev only) */
 enum { TD_RESAMPLE_F32 = 0, TD_RESAMPLE_U8 = 1, TD_RESAMPLE_NDVI = 2 };
 td_status td_resample_gdal_dev(const void* src, int sample_type, int height, int width, int c, const int32_t* bands, int n_bands,
                                const int32_t* x_start, const int32_t* x_count, const int32_t* x_offset, const float* x_weights,
@@ -672,6 +672,33 @@ td_status td_ring_pairs_area_dev(const double* xy_a, const int64_t* start_a, int
                                  int n_b, const int32_t* pairs, int64_t n_pairs, double* out, int32_t* status, void* stream);
 td_status td_ring_pairs_area(const double* xy_a, const int64_t* start_a, int n_a, const double* xy_b, const int64_t* start_b, int n_b,
                              const int32_t* pairs, int64_t n_pairs, double* out, int32_t* status);
+
+/* ---- seam strips (reference helpers.py merge_images 1023-1051 + crop_image 1053-1085; csrc/seam.hip) ----
+ * The strip [rows][cols][spp] (DEVICE, dense, aligned to its samples; TD_SAMPLE_U8, TD_SAMPLE_U16 or TD_SAMPLE_F32, 1 <= spp <= 4)
+ * that the centre crop of rasterio.merge's "first" mosaic of two rasters holds, from up to two source buffers in one launch, without
+ * the mosaic. Per SAMPLE: d = fill; then for `first`, then `second`: where the pixel lies in the source's rectangle, equals(d, fill)
+ * and not (has_own and equals(s, own)), d = s. equals: exact for the integer types; float32: isnan(a) when the value is NaN, else
+ * (|a - (float)v| <= (float)(1e-8 + 1e-5 |v|) and isfinite(v)) or a == (float)v, subtraction and comparisons in float32, float32
+ * subnormals kept — numpy.isclose(float32 array, python float) as treedetection_amd.merging._equals calls it.
+ * A source: `data` DEVICE samples of the strip's type, pixel-interleaved, `rows` buffer rows of `pitch` PIXELS; (row0, col0) = the
+ * strip coordinates of its pixel (0, 0), negative where the buffer begins above / left of the strip; rows r_lo..r_hi and columns
+ * c_lo..c_hi (half-open, inside the strip AND inside the buffer) = the rectangle it may fill — the caller clips it as merge_images
+ * clips the footprint; has_own / own = its own nodata. A NULL source, NULL data or an empty rectangle contributes nothing.
+ * fill and own are given as doubles; for the integer types they must be values of the type. Lanes store 16 bytes at aligned
+ * addresses and load 16 bytes, dwords or single samples as the source address of the row allows. Returns TD_ERR_INVALID (with a
+ * message, before the launch) for a null or misaligned pointer, a bad shape or sample type, or a rectangle that leaves the strip or
+ * its buffer. Asynchronous on `stream`. */
+typedef struct td_seam_source {
+    const void* data;
+    int64_t pitch;
+    int32_t rows;
+    int32_t row0, col0;
+    int32_t r_lo, c_lo, r_hi, c_hi;
+    int32_t has_own;
+    double own;
+} td_seam_source;
+td_status td_seam_first_dev(void* strip, int rows, int cols, int spp, int sample_type, double fill, const td_seam_source* first,
+                            const td_seam_source* second, void* stream);
 
 #ifdef __cplusplus
 }

@@ -20,7 +20,7 @@ ERR_CAPACITY = -4   # TD_ERR_CAPACITY
 ERR_STATE = -5      # TD_ERR_STATE
 ERR_UNSUPPORTED = -6  # TD_ERR_UNSUPPORTED
 JPEG_TABSET_BYTES = 11904  # TD_JPEG_TABSET_BYTES: one table set of td_tiff_jpeg_plan
-SAMPLE_U8, SAMPLE_F32 = 0, 1                          # TD_SAMPLE_*: source of td_resample_gdal_dev
+SAMPLE_U8, SAMPLE_F32, SAMPLE_U16 = 0, 1, 2           # TD_SAMPLE_*: source of td_resample_gdal_dev (U16: td_seam_first_dev only)
 RESAMPLE_MODES = {"f32": 0, "u8": 1, "ndvi": 2}       # TD_RESAMPLE_*: its output modes
 ZSTD_STATS = ("frames block_raw block_rle block_comp max_blocks_per_frame lit_raw lit_rle lit_huff lit_treeless lit_streams_1 lit_streams_4 "
               "hufw_direct hufw_fse seq0 LL_predef LL_rle LL_fse LL_repeat OF_predef OF_rle OF_fse OF_repeat ML_predef ML_rle ML_fse ML_repeat "
@@ -41,6 +41,13 @@ class ModelDesc(C.Structure):
 
 class TensorDesc(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("ndim", C.c_int32), ("shape", C.c_int64 * 4)]
+
+
+class SeamSource(C.Structure):
+    """td_seam_source: one source buffer of td_seam_first_dev."""
+    _fields_ = [("data", C.c_void_p), ("pitch", C.c_int64), ("rows", C.c_int32), ("row0", C.c_int32), ("col0", C.c_int32),
+                ("r_lo", C.c_int32), ("c_lo", C.c_int32), ("r_hi", C.c_int32), ("c_hi", C.c_int32), ("has_own", C.c_int32),
+                ("own", C.c_double)]
 
 
 class Detections(C.Structure):
@@ -98,6 +105,8 @@ SIGNATURES = {
     "td_resample_gdal_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int]
                              + [C.c_void_p] * 4 + [C.c_int, C.c_int64] + [C.c_void_p] * 4 + [C.c_int, C.c_int64]
                              + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "td_seam_first_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(SeamSource), C.POINTER(SeamSource),
+                                    C.c_void_p]),
     "td_crown_pairs_count": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_uint16, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
                                        C.c_void_p]),
     "td_crown_pairs_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_uint16, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

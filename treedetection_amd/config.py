@@ -16,7 +16,9 @@ rasters whose blocks have no restart markers are decoded on the GPU too, a wave 
 are decoded on the GPU too and their planes interleaved there; same pixels), ``device_filters`` ("auto" | true | false: the crown stage's
 box-IoU de-duplication and containment pair tests on the GPU, sparse result only — "auto" keeps the host functions; same features),
 ``clean_crowns`` (true | false, default false: the crown stage first thins each layer by the IoU of the crown outlines, threshold 0.7,
-the reference's ``clean_crowns`` — treedetection_amd.cleaning; false: not one byte of any output changes).
+the reference's ``clean_crowns`` — treedetection_amd.cleaning; false: not one byte of any output changes), ``device_seams`` (true |
+false, default false: the seam strips of ``use_overlap`` between LZW / DEFLATE / ZSTD rasters are cut on the GPU from only the blocks
+they touch — treedetection_amd.merging; same files).
 """
 from __future__ import annotations
 
@@ -168,7 +170,7 @@ def get_config(config_path: str):
         # extensions of this package (defaults = the reference's behaviour)
         "precision": "fp32", "resnet_depth": 101, "sharded_epilogue": "auto", "shard_by": "auto", "eager_stitch": True,
         "fp16_min_batch": 0, "device_contours": "auto", "device_decode": "auto", "device_filters": "auto",
-        "device_decode_long_jpeg": False, "device_decode_planar": False, "clean_crowns": False,
+        "device_decode_long_jpeg": False, "device_decode_planar": False, "clean_crowns": False, "device_seams": False,
     }
     for k, v in defaults.items():
         config[k] = config.get(k, v)

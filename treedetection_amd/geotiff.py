@@ -11,7 +11,8 @@ block (GDAL does the same through libtiff). The floating-point predictor (predic
 is undone block by block (td_tiff_unpredict_float). Other codecs (old-style JPEG, predictor 3 on float64, ...): whole image through Pillow.
 Whole rasters can instead be decoded on the GPU and kept in HBM (``decode_to_device``): LZW, DEFLATE and ZSTD (tiffdecode.hip, zstddecode.hip; uint8 and
 native-order uint16 samples; native-order float32 height rasters, predictors 1 - 3, for callers that ask for them) and sequential-Huffman
-JPEG (jpegdecode.hip, byte-identical to the Pillow path) — see ``device_decodable``. The steps of the device paths (staging, the file
+JPEG (jpegdecode.hip, byte-identical to the Pillow path) — see ``device_decodable`` — or, with ``window=``, only the blocks a pixel window
+overlaps (the seam strips of merging.py). The steps of the device paths (staging, the file
 read, the decoder and layout launches, ``check``) are device_decode.py's; the methods here compose them.
 """
 from __future__ import annotations
@@ -407,17 +408,39 @@ class GeoTiff:
                 and self._predictor in ((1, 2, 3) if f32 else (1, 2)) and self._counts is not None and self._pil is None
                 and self._bw * self._bh * (self.count if self.planar == 1 else 1) * self.dtype.itemsize < (1 << 31))
 
-    def device_block_plan(self, bands: Optional[Sequence[int]] = None):
+    def _window_blocks(self, window):
+        """``window`` = (r0, c0, h, w) in raster pixels, non-empty and inside the raster (ValueError naming it otherwise) → the
+        sub-grid of blocks it overlaps, (by0, bx0, ny', nx')."""
+        self._setup_blocks()
+        try:
+            r0, c0, h, w = (int(v) for v in window)
+            ok = all(int(v) == v for v in window)
+        except (TypeError, ValueError):
+            ok = False
+        if not ok or h < 1 or w < 1 or r0 < 0 or c0 < 0 or r0 + h > self.height or c0 + w > self.width:
+            raise ValueError(f"{self.path}: window {window!r} (r0, c0, h, w) must be non-empty and lie inside the {self.height} x {self.width} raster")
+        by0, bx0 = r0 // self._bh, c0 // self._bw
+        return by0, bx0, (r0 + h - 1) // self._bh - by0 + 1, (c0 + w - 1) // self._bw - bx0 + 1
+
+    def device_block_plan(self, bands: Optional[Sequence[int]] = None, window: Optional[Sequence[int]] = None):
         """What ``decode_to_device`` reads and decodes, worked out on the host (no GPU): → (planes, plane_mask, offsets, counts, expect,
-        ranges). A pixel-interleaved file has one "plane" (0) whose blocks hold every band, and ``bands`` is refused. A band-separate
+        ranges), and with ``window`` (below) a seventh entry. A pixel-interleaved file has one "plane" (0) whose blocks hold every band, and ``bands`` is refused. A band-separate
         file has one grid of nx x ny blocks per band: ``bands`` (band indices, any order, default all) picks the planes — ascending in
         ``planes``, bit p of ``plane_mask`` for band p — and only their blocks are listed: ``offsets`` / ``counts`` are the file's
         own (int64, plane after plane, within a plane the file's order), ``expect`` is what each block must decode to in bytes (every
         plane of a strip file ends in its own short strip). ``ranges`` are the byte ranges [(lo, hi), ...] of the file that hold
-        those blocks, one per plane, ascending, merged where they overlap or lie within 4 KB of each other: what is read and copied to the device."""
+        those blocks, one per plane, ascending, merged where they overlap or lie within 4 KB of each other: what is read and copied to the device.
+        ``window`` = (r0, c0, h, w) in raster pixels (non-empty, inside the raster: ValueError otherwise): only the blocks of the
+        sub-grid by0..by1 x bx0..bx1 the window overlaps are listed, per selected plane, row-major — to the layout kernels a small
+        raster of its own — and the result ends in that sub-grid, (by0, bx0, ny', nx'). ``ranges`` then hold one span per plane AND
+        BLOCK ROW of the sub-grid before the merge within 4 KB, not one per plane: in a tiled file a block row's tiles bx0..bx1 lie
+        side by side, but between two block rows lie the tiles left and right of the window — a window one tile wide in a raster 36
+        tiles wide would read 36 times its bytes in one range per plane. In a strip file the rows of a plane are adjacent and merge
+        back into one range."""
         self._setup_blocks()
         per = self._nx * self._ny
         item = self.dtype.itemsize
+        by0, bx0, ny, nx = (0, 0, self._ny, self._nx) if window is None else self._window_blocks(window)
         if self.planar != 2:
             if bands is not None:
                 raise ValueError(f"{self.path}: bands={tuple(bands)!r} picks planes of a band-separate file; this one is pixel-interleaved")
@@ -428,12 +451,14 @@ class GeoTiff:
                 raise ValueError(f"{self.path}: bands={tuple(bands)!r} must be distinct band indices below {self.count}")
         if self._counts is None or len(self._offs) != len(self._counts) or len(self._offs) != per * (self.count if self.planar == 2 else 1):
             raise ValueError(f"{self.path}: {len(self._offs)} block offsets for {per} blocks per plane")
-        idx = np.concatenate([np.arange(p * per, (p + 1) * per) for p in planes])
+        sub = ((by0 + np.arange(ny))[:, None] * self._nx + bx0 + np.arange(nx)[None, :]).ravel()      # the sub-grid's blocks within a plane
+        idx = np.concatenate([p * per + sub for p in planes])
         offs = np.asarray(self._offs, dtype=np.int64)[idx]
         cnts = np.asarray(self._counts, dtype=np.int64)[idx]
-        one = np.array([self._block_rows(by) * self._bw * cb * item for by in range(self._ny) for _ in range(self._nx)], dtype=np.int64)
+        one = np.array([self._block_rows(by) * self._bw * cb * item for by in range(by0, by0 + ny) for _ in range(nx)], dtype=np.int64)
         expect = np.tile(one, len(planes))
-        spans = sorted((int(offs[i * per:(i + 1) * per].min()), int((offs + cnts)[i * per:(i + 1) * per].max())) for i in range(len(planes)))
+        run = ny * nx if window is None else nx                # blocks that share a span: a plane's, or with a window one block row's
+        spans = sorted((int(offs[i:i + run].min()), int((offs + cnts)[i:i + run].max())) for i in range(0, len(idx), run))
         ranges = [spans[0]]
         for lo, hi in spans[1:]:
             if lo <= ranges[-1][1] + 4096:                 # (writers pad blocks to even or page offsets: a small gap is read with its neighbours)
@@ -441,7 +466,8 @@ class GeoTiff:
             else:
                 ranges.append((lo, hi))
         mask = sum(1 << p for p in planes) if self.planar == 2 else 1
-        return planes, mask, offs, cnts, expect, ranges
+        plan = (planes, mask, offs, cnts, expect, ranges)
+        return plan if window is None else plan + ((by0, bx0, ny, nx),)
 
     def _device_samples(self) -> bool:
         """Sample types the device kernels take as they lie in the file: uint8, and uint16 in the host's (= the GPU's) byte order."""
@@ -487,7 +513,8 @@ class GeoTiff:
         return plan
 
     def decode_to_device(self, device, stream=None, pinned=None, pool=None, long_segments: bool = False, long_threshold: Optional[int] = None,
-                         subseq_bytes: Optional[int] = None, planar: bool = False, bands: Optional[Sequence[int]] = None):
+                         subseq_bytes: Optional[int] = None, planar: bool = False, bands: Optional[Sequence[int]] = None,
+                         window: Optional[Sequence[int]] = None):
         """The whole raster decoded in HBM: the compressed blocks are read as they lie in the file (one pread of the span that
         holds them, into pinned memory), copied to the device once, decoded one wave per block (td_tiff_lzw_decode_dev / td_tiff_zstd_decode_dev /
         td_tiff_inflate_verified_dev, which also checks every DEFLATE block's Adler-32 trailer as zlib does; JPEG: one lane per
@@ -506,13 +533,28 @@ class GeoTiff:
         decoders, one sample per pixel, and td_tiff_planes_to_image_dev / _u16_dev / _f32_dev interleaves them into the same
         [height, width, bands] tensor in one launch. ``bands`` (band-separate files only; ValueError otherwise): the band indices that
         are needed — only their planes are read from the file, copied and decoded (:meth:`device_block_plan`); the image keeps all its
-        channels, the others are 0, and ``check.compressed_bytes`` counts what was copied."""
+        channels, the others are 0, and ``check.compressed_bytes`` counts what was copied.
+        ``window`` = (r0, c0, h, w) in raster pixels (non-empty, inside the raster: ValueError otherwise): only the blocks the window
+        overlaps are read, copied and decoded (:meth:`device_block_plan`), and the tensor is their block-aligned COVER
+        [cover_h, cover_w, bands], whose pixel (0, 0) is the raster's ``check.origin`` = (by0 * block rows, bx0 * block columns) and
+        which ends with the sub-grid or the raster, whichever comes first; the window lies in it at ``check.window`` = (row, column,
+        h, w). The same decoder and layout launches on the sub-grid as on a small raster of its own; a bad block is still named by
+        its number in the file. JPEG rasters ignore the window: they decode whole, origin (0, 0)."""
         import torch
         from . import _lib
         if not self.device_decodable(float_samples=True, long_segments=long_segments, planar=planar):
             raise ValueError(f"{self.path}: not decodable on the device (compression {self.compression}, {self.dtype}, {self.count} bands)")
         dev = torch.device(device)
-        planes, plane_mask, offs, cnts, expect, ranges = self.device_block_plan(bands)
+        by0, bx0, ny, nx = 0, 0, self._ny, self._nx
+        if window is not None and self.compression != 7:
+            planes, plane_mask, offs, cnts, expect, ranges, (by0, bx0, ny, nx) = self.device_block_plan(bands, window)
+        else:
+            if window is not None:
+                self._window_blocks(window)                     # (refused like any other raster's when it is bad)
+            planes, plane_mask, offs, cnts, expect, ranges = self.device_block_plan(bands)
+        oy, ox = by0 * self._bh, bx0 * self._bw
+        cover_h, cover_w = min((by0 + ny) * self._bh, self.height) - oy, min((bx0 + nx) * self._bw, self.width) - ox
+        where = {} if window is None else {"origin": (oy, ox), "window": (int(window[0]) - oy, int(window[1]) - ox, int(window[2]), int(window[3]))}
         nb = len(offs)
         rel, starts, span = stage_offsets(offs, ranges)
         if pinned is not None and pinned and pinned[0] is not None and pinned[0].numel() >= span + 16:
@@ -535,14 +577,14 @@ class GeoTiff:
             comp = pin[:span + 16].to(dev, non_blocking=True)
             k0, k1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             if self.compression == 7:
-                return self._jpeg_to_device(dev, pin, comp, ranges[0][0], span, k0, k1, long_segments, long_threshold, subseq_bytes)
+                return self._jpeg_to_device(dev, pin, comp, ranges[0][0], span, k0, k1, long_segments, long_threshold, subseq_bytes, where)
             meta = torch.from_numpy(np.stack([rel, cnts])).to(dev, non_blocking=True)
             bufs = alloc_block_buffers(self.compression, nb, block_cap, dev)
             k0.record()
             launch_block_decoder(self.compression, comp, meta, bufs, st)
-            image = torch.empty((self.height, self.width, self.count), dtype={1: torch.uint8, 2: torch.uint16, 4: torch.float32}[item], device=dev)
-            launch_layout(bufs.blocks, block_cap, self._bw, self._bh, self._nx, self._ny, self.count, self._predictor, image, self.width,
-                          self.height, st, plane_mask if self.planar == 2 else None)
+            image = torch.empty((cover_h, cover_w, self.count), dtype={1: torch.uint8, 2: torch.uint16, 4: torch.float32}[item], device=dev)
+            launch_layout(bufs.blocks, block_cap, self._bw, self._bh, nx, ny, self.count, self._predictor, image, cover_w,
+                          cover_h, st, plane_mask if self.planar == 2 else None)
             k1.record()                                    # the decode launches (DEFLATE: + the checksum launch) + the scatter / predictor kernel
 
             def verdict(check, dec_h, st_h):
@@ -552,16 +594,17 @@ class GeoTiff:
                 if bad.size:
                     b = int(bad[0])
                     per = nb // len(planes)
-                    fb = planes[b // per] * per + b % per           # the block's number in the file (planes that were left out count)
+                    # the block's number in the file (planes that were left out count, and the blocks around a window's sub-grid)
+                    fb = planes[b // per] * self._nx * self._ny + (by0 + b % per // nx) * self._nx + bx0 + b % per % nx
                     if self.compression in (8, 32946) and int(st_h[b]) == 3:
                         raise ValueError(f"{self.path}: block {fb}: Adler-32 mismatch (status 3): its {int(produced[b])} decoded bytes do not sum to the stream's trailer")
                     if self.compression == 50000 and int(st_h[b]) == 4:
                         raise ValueError(f"{self.path}: block {fb}: declined by the device decoder (status 4): a content checksum, a second frame or a skippable frame")
                     raise ValueError(f"{self.path}: block {fb} decodes to {int(produced[b])} bytes (status {int(st_h[b])}), expected {int(expect[b])}")
             keep = [pin, comp, meta, bufs]                 # alive until check() has run: the kernels read them
-            return image, finish(image, k0, k1, [bufs.decoded, bufs.status[:nb]], keep, verdict, span)
+            return image, finish(image, k0, k1, [bufs.decoded, bufs.status[:nb]], keep, verdict, span, **where)
 
-    def _jpeg_to_device(self, dev, pin, comp, lo, span, k0, k1, long_segments=False, long_threshold=None, subseq_bytes=None):
+    def _jpeg_to_device(self, dev, pin, comp, lo, span, k0, k1, long_segments=False, long_threshold=None, subseq_bytes=None, where=None):
         """decode_to_device for JPEG blocks (inside its device / stream context, the compressed bytes already on their way to ``comp``):
         the plan's arrays go to the device, td_tiff_jpeg_decode_dev decodes (entropy segments one per lane, IDCT, upsampling + colour)
         straight into the raster. Same (image, check) contract; ``check()`` names the first block whose data is corrupt.
@@ -614,7 +657,7 @@ class GeoTiff:
                 raise ValueError(f"{self.path}: JPEG block {b} is corrupt (status {int(st_h[b])})")
         keep = [pin, comp, info_d, segs_d, sets_d, coef, planes, status, stats]     # alive until check() has run: the kernels read them
         return image, finish(image, k0, k1, [status] if stats is None else [status, stats], keep, verdict, span,
-                             segments=len(segs), long_segments=nlong, sync_rounds=0.0)
+                             segments=len(segs), long_segments=nlong, sync_rounds=0.0, **(where or {}))
 
     def device_uploadable(self) -> bool:
         """True when the raster's pixels lie in the file as ONE dense [rows, cols, bands] array of uint8 or native-order uint16
