@@ -18,6 +18,7 @@ from treedetection_amd.contours import find_contours as host_find_contours  # no
 
 pytestmark = pytest.mark.gpu
 CMAX = 256
+LABEL_LARGE = 28 * 1024    # (w + 2) * (h + 2) labels of the larger on-chip image
 
 
 def _pack(masks_per_image, Dn):
@@ -64,7 +65,10 @@ def _trace(masks_per_image, Dn=12, pts_cap=60000):
     return pts.cpu().numpy(), img_pts.cpu().numpy(), det_info.cpu().numpy(), cont_info.cpu().numpy()
 
 
-def _check(masks_per_image, **kw):
+def _check(masks_per_image, full_ok=False, **kw):
+    """A non-zero status is never skipped: it must be the one include/treedet.h prescribes for that mask — 1 when the region
+    exceeds the on-chip label image, 2 when the oracle finds more than TD_CONTOUR_MAX contours — or, only where the test
+    made the point buffer too small (``full_ok``), 4; and a mask with such a reason must be flagged."""
     pts, img_pts, det_info, cont_info = _trace(masks_per_image, **kw)
     traced = 0
     for b, dets in enumerate(masks_per_image):
@@ -73,7 +77,10 @@ def _check(masks_per_image, **kw):
             want = find_contours(m.astype(np.uint8))
             host = host_find_contours(m.astype(np.uint8))
             assert len(host) == len(want) and all(np.array_equal(a, b) for a, b in zip(host, want)), (b, d)
+            expect = 1 if (m.shape[0] + 2) * (m.shape[1] + 2) > LABEL_LARGE else 2 if len(want) > CMAX else 0
+            assert status == expect or (status == 4 and expect == 0 and full_ok), (b, d, int(status), expect, len(want), m.shape)
             if status != 0:
+                assert nc == 0 and total == 0, (b, d, det_info[b, d].tolist())
                 continue
             traced += 1
             assert nc == len(want) and total == sum(len(c) for c in want), (b, d, nc, len(want))
@@ -133,7 +140,8 @@ def test_limits_are_flagged_not_mis_traced():
     ok = _blob(rng, 60, 60)
     det_info, traced = _check([[(0, 0, big), (5, 5, many), (9, 9, ok)]], Dn=3)
     assert det_info[0, :, 0].tolist() == [1, 2, 0] and traced == 1
-    det_info, _ = _check([[(0, 0, ok), (0, 0, ok)]], Dn=2, pts_cap=int(sum(len(c) for c in find_contours(ok.astype(np.uint8))) + 3))
+    det_info, _ = _check([[(0, 0, ok), (0, 0, ok)]], Dn=2, full_ok=True,
+                        pts_cap=int(sum(len(c) for c in find_contours(ok.astype(np.uint8))) + 3))
     assert sorted(det_info[0, :, 0].tolist()) == [0, 4]               # the second block does not fit the point buffer
 
 
