@@ -584,6 +584,35 @@ int td_stitch_tile_files(const char* paths, const int64_t* path_offsets, int n_f
 int td_region_relate(const double* ring_xy, const int64_t* ring_start, const int32_t* ring_poly, int n_rings,
                      const double* query_xy, const int64_t* query_start, int n_queries, uint8_t* flags);
 
+/* The same predicates on the device (csrc/regionrelate.hip; the arithmetic of csrc/geom_predicates.h on both sides, so flags[q] equals
+ * td_region_relate's for every query it decides). Every pointer is DEVICE memory; ring_xy and query_xy 16-byte aligned.
+ *   region: ring_xy / ring_start / ring_poly as above (n_vertices = ring_start[n_rings] < 2^31 - 1, ring_poly not decreasing) and
+ *   edge_ring int32 [n_vertices], the ring of each vertex. Edge id = index of the edge's first vertex.
+ *   index: the y-bins of td_region_relate — bin b = floor((y - ymin) * inv_h) clamped to [0, n_bins) — as bin_start int32
+ *   [n_bins + 1] into bin_edges int32 [n_bin_edges]: the ids of the edges whose y-range touches the bin, ascending; ymin / ymax the
+ *   region's y-range.
+ *   queries: closed rings, query_start int64 [n_queries + 1] into query_xy (n_query_vertices points).
+ * Out: flags uint8 [n_queries] (bit 0 intersects, bit 1 within, as above), status int32 [n_queries]:
+ *   0 decided; 1 NOT decided (flag 0) because a fixed capacity of the kernel was exceeded — more than TD_RELATE_QUERY_CAP points in
+ *   the ring, more than TD_RELATE_MEET_CAP meetings of ONE query edge with region edges, or more than TD_RELATE_RING_CAP distinct
+ *   region rings met by the query — td_region_relate decides such a query; 2 refused (flag 0): fewer than 4 points, not closed, a
+ *   non-finite coordinate, a start outside query_xy.
+ * One wave per query, one launch for any n_queries, asynchronous on `stream`; no query is half-decided. The kernel checks every id it
+ * takes from the index against n_vertices / n_rings / n_bin_edges before it addresses anything, so no index content makes it read
+ * outside the arrays; the ANSWERS need a consistent index. With check_index != 0 the call first verifies that on the device
+ * (bin_start rising within bin_edges, every edge id inside the edge array and inside the ring edge_ring names, ids ascending per
+ * bin, ring_poly not decreasing), waits for the verdict and returns TD_ERR_INVALID without launching the predicates when it fails:
+ * pass it once per uploaded index. TD_ERR_INVALID (before anything runs) for a null pointer, a bad count, a non-finite y-range or a
+ * misaligned xy; n_queries = 0 returns TD_OK and launches nothing. */
+#define TD_RELATE_QUERY_CAP 256   /* points of a query ring, the closing one included */
+#define TD_RELATE_MEET_CAP 254    /* meeting parameters of one query edge (a collinear overlap counts two) */
+#define TD_RELATE_RING_CAP 64     /* distinct region rings one query meets */
+td_status td_region_relate_dev(const double* ring_xy, const int64_t* ring_start, const int32_t* ring_poly, int n_rings, int64_t n_vertices,
+                               const int32_t* edge_ring, const int32_t* bin_start, const int32_t* bin_edges, int n_bins,
+                               int64_t n_bin_edges, double ymin, double ymax, double inv_h, const double* query_xy,
+                               const int64_t* query_start, int n_queries, int64_t n_query_vertices, uint8_t* flags, int32_t* status,
+                               int check_index, void* stream);
+
 /* ---- crown post-processing (reference postprocessing.py:25-347) ----------------------------- */
 /* Raster statistics inside each crown's bounding circle. raster: device float32 [rows][cols]; transform: host
  * (a,b,c,d,e,f) of the raster; window: host (row_lo, col_lo, row_hi, col_hi) = the reference's subset of the raster

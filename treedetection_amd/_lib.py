@@ -26,6 +26,8 @@ ZSTD_STATS = ("frames block_raw block_rle block_comp max_blocks_per_frame lit_ra
               "hufw_direct hufw_fse seq0 LL_predef LL_rle LL_fse LL_repeat OF_predef OF_rle OF_fse OF_repeat ML_predef ML_rle ML_fse ML_repeat "
               "window_desc single_segment checksum seq_long seq_2byte skippable").split()   # TD_ZSTD_STATS counters of td_zstd_stream_stats, in order
 RING_PAIR_CAP, RING_PAIR_WPB, RING_PAIR_GRID = 1024, 4, 2048   # ringiou.hip: vertices of a pair in LDS, waves per workgroup, workgroups per launch
+# TD_RELATE_*_CAP (regionrelate.hip): points of a query ring, meeting parameters of one query edge, distinct region rings a query meets
+RELATE_QUERY_CAP, RELATE_MEET_CAP, RELATE_RING_CAP = 256, 254, 64
 
 
 class TdError(RuntimeError):
@@ -160,6 +162,9 @@ SIGNATURES = {
     "td_tiff_unpredict": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int]),
     "td_tiff_unpredict_float": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int]),
     "td_region_relate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "td_region_relate_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64,
+                                       C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
+                                       C.c_int, C.c_void_p]),
     "td_simplify_ring": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_int]),
     "td_ring_is_valid": (C.c_int, [C.c_void_p, C.c_int]),
     "td_stitch_tile_json": (C.c_int, [C.c_char_p, C.c_int64, C.POINTER(C.c_double), C.c_double, C.c_int32, C.c_void_p,

@@ -13,7 +13,8 @@
 // That is the DE-9IM meaning of the two predicates for a simple query ring against the union of the polygons; it
 // differs from an overlay only for uncovered gaps that lie strictly inside a query without touching its boundary
 // and are bounded by several polygons at once (the hole of a single polygon is handled).
-// A y-binned edge index keeps each crossing count local. Pure host code.
+// A y-binned edge index keeps each crossing count local. Pure host code; the arithmetic is geom_predicates.h's, which the device
+// twin (regionrelate.hip, td_region_relate_dev) shares.
 #include "common.h"
 #include "geom_predicates.h"
 
@@ -40,11 +41,7 @@ struct Region {
     double y0 = 0, inv_h = 0;
     int nb = 1;
 
-    int bin_of(double y) const {
-        const double f = (y - y0) * inv_h;
-        if (!(f > 0)) return 0;
-        return f >= nb ? nb - 1 : (int)f;
-    }
+    int bin_of(double y) const { return relate_bin_of(y, y0, inv_h, nb); }
 
     // Crossing state of point p against every polygon near it: *on = polygon ids with p on one of their rings,
     // *in = polygon ids with an odd crossing count (horizontal ray to +x, half-open rule on y).
@@ -56,18 +53,9 @@ struct Region {
         if (p.y < ymin || p.y > ymax) return;
         for (int id : bins[bin_of(p.y)]) {
             const Edge& e = edges[id];
-            const double lo = std::fmin(e.a.y, e.b.y), hi = std::fmax(e.a.y, e.b.y);
-            if (p.y < lo || p.y > hi) continue;
-            if (std::fmax(e.a.x, e.b.x) < p.x) continue;
-            const int o = orientation(e.a.x, e.a.y, e.b.x, e.b.y, p.x, p.y);
-            if (o == 0 && env_has(e.a, e.b, p)) {
-                on.push_back(e.poly);
-                continue;
-            }
-            if ((e.a.y <= p.y) != (e.b.y <= p.y)) {          // half-open: counts an edge once at a shared vertex
-                const bool up = e.a.y <= p.y;                // a below-or-level, b above
-                if ((up && o > 0) || (!up && o < 0)) scratch.push_back(e.poly);
-            }
+            const int c = edge_point_rule(e.a, e.b, p);
+            if (c == 1) on.push_back(e.poly);
+            else if (c == 2) scratch.push_back(e.poly);
         }
         std::sort(scratch.begin(), scratch.end());
         for (size_t i = 0; i < scratch.size();) {
@@ -81,61 +69,6 @@ struct Region {
     }
     double ymin = 0, ymax = 0;
 };
-
-// does segment (p1,p2) meet segment (q1,q2) at all (touching counts)?
-bool segments_meet(const Pt& p1, const Pt& p2, const Pt& q1, const Pt& q2) {
-    if (!env_overlap(p1, p2, q1, q2)) return false;
-    const int a = orientation(p1.x, p1.y, p2.x, p2.y, q1.x, q1.y);
-    const int b = orientation(p1.x, p1.y, p2.x, p2.y, q2.x, q2.y);
-    if ((a > 0 && b > 0) || (a < 0 && b < 0)) return false;
-    const int c = orientation(q1.x, q1.y, q2.x, q2.y, p1.x, p1.y);
-    const int d = orientation(q1.x, q1.y, q2.x, q2.y, p2.x, p2.y);
-    if ((c > 0 && d > 0) || (c < 0 && d < 0)) return false;
-    return true;     // collinear pairs reach here only with overlapping envelopes, i.e. they share a point
-}
-
-// parameters t in [0,1] along (p1,p2) where it meets (q1,q2): none, one point, or the two ends of a collinear overlap
-int meet_params(const Pt& p1, const Pt& p2, const Pt& q1, const Pt& q2, double t[2]) {
-    if (!segments_meet(p1, p2, q1, q2)) return 0;
-    const double dx = p2.x - p1.x, dy = p2.y - p1.y;
-    const double len2 = dx * dx + dy * dy;
-    auto param = [&](const Pt& q) {
-        double v = len2 > 0 ? ((q.x - p1.x) * dx + (q.y - p1.y) * dy) / len2 : 0.0;
-        return v < 0 ? 0.0 : (v > 1 ? 1.0 : v);
-    };
-    const int a = orientation(p1.x, p1.y, p2.x, p2.y, q1.x, q1.y);
-    const int b = orientation(p1.x, p1.y, p2.x, p2.y, q2.x, q2.y);
-    if (a == 0 && b == 0) {                    // collinear overlap
-        double t0 = param(q1), t1 = param(q2);
-        if (t0 > t1) std::swap(t0, t1);
-        t[0] = t0;
-        t[1] = t1;
-        return 2;
-    }
-    if (a == 0) { t[0] = param(q1); return 1; }
-    if (b == 0) { t[0] = param(q2); return 1; }
-    // proper or end-of-p touch: solve with the cross products
-    const double ex = q2.x - q1.x, ey = q2.y - q1.y;
-    const double den = dx * ey - dy * ex;
-    double v = den != 0 ? ((q1.x - p1.x) * ey - (q1.y - p1.y) * ex) / den : 0.0;
-    t[0] = v < 0 ? 0.0 : (v > 1 ? 1.0 : v);
-    return 1;
-}
-
-// closed point-in-ring for the (small) query ring: 0 outside, 1 inside, 2 on the boundary
-int point_in_query(const Pt* q, int n, const Pt& p) {
-    bool in = false;
-    for (int i = 0; i + 1 < n; ++i) {
-        const Pt &a = q[i], &b = q[i + 1];
-        const int o = orientation(a.x, a.y, b.x, b.y, p.x, p.y);
-        if (o == 0 && env_has(a, b, p)) return 2;
-        if ((a.y <= p.y) != (b.y <= p.y)) {
-            const bool up = a.y <= p.y;
-            if ((up && o > 0) || (!up && o < 0)) in = !in;
-        }
-    }
-    return in ? 1 : 0;
-}
 
 }  // namespace
 
@@ -258,8 +191,7 @@ extern "C" int td_region_relate(const double* ring_xy, const int64_t* ring_start
                 std::sort(ts.begin(), ts.end());
                 for (size_t j = 0; j + 1 < ts.size(); ++j) {
                     if (!(ts[j + 1] > ts[j])) continue;
-                    const double tm = 0.5 * (ts[j] + ts[j + 1]);
-                    const Pt m{Q[i].x + tm * (Q[i + 1].x - Q[i].x), Q[i].y + tm * (Q[i + 1].y - Q[i].y)};
+                    const Pt m = piece_midpoint(Q[i], Q[i + 1], ts[j], ts[j + 1]);
                     if (!member(m)) {
                         within = false;
                         break;

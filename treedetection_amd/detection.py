@@ -21,7 +21,7 @@ from .config import Config, get_config, setup_model_cfg  # noqa: F401  (re-expor
 from .prediction import Predictor
 from .preprocessing import tile_data
 from .recoveries import load_prediction_recovery_data, save_prediction_recovery_data
-from .fusion import exclude_outlines, fuse_predictions  # noqa: F401
+from .fusion import exclude_outlines, fuse_predictions, outline_device  # noqa: F401
 from .merging import merge_and_crop_images
 from .postprocessing import process_files_in_directory
 from .stitching import process_and_stitch_predictions
@@ -316,7 +316,7 @@ def predict_tiles(config):
         t3 = time.time()
         if D.rank() == 0:
             fuse_predictions(os.path.join(out, "urban_geojson"), os.path.join(out, "forrest_geojson"), config["forrest_outline"],
-                             os.path.join(out, "geojson_predictions"), logger=logger)
+                             os.path.join(out, "geojson_predictions"), logger=logger, device=outline_device(config))
         logger.info("Fusion based on forest outline has been completed.")
         logger.debug(f"fuse prediction took {time.time() - t3} seconds")
         logger.debug(f"predict on model for urban took {t1 - t0} seconds")

@@ -4,7 +4,8 @@ the exclude-outline filter (helpers.py:33-69 ``exclude_outlines``).
 Per stitched image: keep the forest model's crowns that *intersect* the forest, and the urban model's crowns that are
 not *within* it; either layer alone passes through unchanged when the other is empty. The reference evaluates the two
 predicates against ``unary_union`` of the outline polygons near the image (geopandas/shapely, absent here); this
-module evaluates them against the polygons themselves with ``td_region_relate`` (libtreedet_hip.so, host code), which
+module evaluates them against the polygons themselves with ``td_region_relate`` (libtreedet_hip.so, host code; with the config key
+``device_outlines: true`` its device twin ``td_region_relate_dev``, a wave per crown, same answers), which
 gives the same answers without building the union. ``to_crs``: treedetection_amd.crs moves the OUTLINE into the crowns' CRS
 (geographic / UTM / Web Mercator codes; any other pair is refused with an error instead of guessed).
 
@@ -19,10 +20,11 @@ from __future__ import annotations
 
 import os
 import shutil
-from typing import List
+from typing import List, Optional
 
 import numpy as np
 
+from .geotiff import _true_false_setting
 from .gpkg import read_layer, write_blobs
 from .recoveries import load_fusion_recovery, save_fusion_recovery
 from .validity import buffer0, geometry_blob, ring_is_valid
@@ -34,7 +36,29 @@ def _check_dir(path, what):
         raise FileNotFoundError(f"{what} predictions path not found: {path}")
 
 
-def fuse_predictions(urban_fold, forrest_fold, forrest_path, output_dir, logger=None):
+def device_outlines_setting(value=False) -> bool:
+    """The ``device_outlines`` config key: true / false (default) → whether :func:`fuse_predictions` and :func:`exclude_outlines`
+    relate the crowns to the outline on the GPU (``Region.relate(device=...)``: td_region_relate_dev, the host function's answers).
+    Anything else is refused. The only_forest / only_urban tile flags of treedetection_amd.preprocessing — a handful of box queries
+    per image — stay on the host either way."""
+    return _true_false_setting("device_outlines", value)
+
+
+def outline_device(config) -> Optional[int]:
+    """The GPU index the outline steps relate on — the device this process is bound to — or None with ``device_outlines`` off."""
+    if not device_outlines_setting(config.get("device_outlines", False)):
+        return None
+    configured = config.get("device", "0")
+    if str(configured) == "cpu":
+        raise ValueError("device_outlines is true but device is 'cpu': the outline kernel needs a GPU")
+    from .distributed import local_device
+
+    return local_device(str(configured).replace("cuda:", "") or 0)
+
+
+def fuse_predictions(urban_fold, forrest_fold, forrest_path, output_dir, logger=None, device=None):
+    """``device``: None — the outline predicates on the host (td_region_relate) — or a GPU index (td_region_relate_dev; same
+    files)."""
     _check_dir(urban_fold, "Urban")
     _check_dir(forrest_fold, "Forest")
     if not os.path.exists(forrest_path) or not os.path.isfile(forrest_path):
@@ -107,8 +131,8 @@ def fuse_predictions(urban_fold, forrest_fold, forrest_path, output_dir, logger=
                                                         (boxes[:, 3] >= cb[1]) & (boxes[:, 1] <= cb[3]))[0]] if len(boxes) else []
             if near:
                 region = Region(near)
-                keep_f = region.relate(forest.rings())[0]
-                keep_u = ~region.relate(urban.rings())[1]
+                keep_f = region.relate(forest.rings(), device)[0]
+                keep_u = ~region.relate(urban.rings(), device)[1]
             else:
                 keep_f = np.zeros(len(forest), bool)
                 keep_u = np.ones(len(urban), bool)
@@ -148,7 +172,8 @@ def fuse_predictions(urban_fold, forrest_fold, forrest_path, output_dir, logger=
 
 def exclude_outlines(config, logger=None):
     """Drops crowns that lie within the outlines of ``config['exclude_files']`` from every ``processed_*`` layer in
-    ``<output_directory>/geojson_predictions`` (reference helpers.py:33-69)."""
+    ``<output_directory>/geojson_predictions`` (reference helpers.py:33-69). ``device_outlines: true`` relates on the GPU."""
+    device = outline_device(config)
     for outline in config.get("exclude_files", []) or []:
         try:
             polys, epsg = read_polygon_layer(outline)
@@ -168,7 +193,7 @@ def exclude_outlines(config, logger=None):
                 if epsg and crowns.srs_id != epsg:          # reference helpers.py:55: exclude_outline.to_crs(crowns.crs)
                     from .crs import to_crs
                     outline = to_crs(polys, epsg, crowns.srs_id)
-                keep = ~Region(outline).relate(crowns.rings())[1]
+                keep = ~Region(outline).relate(crowns.rings(), device)[1]
                 env = crowns.envelopes()[keep]
                 extent = (float(env[:, 0].min()), float(env[:, 2].min()), float(env[:, 1].max()), float(env[:, 3].max())) if len(env) else None
                 idx = np.nonzero(keep)[0]

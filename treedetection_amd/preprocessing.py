@@ -40,7 +40,8 @@ def _load_outline(path: Optional[str], target_epsg: Optional[int] = None):
 def _tile_flags(forest_polys, forest_boxes, minx, miny, tile_width, tile_height, bounds):
     """only_forest / only_urban of one tile (reference preprocessing.py:70-95): candidates = outline polygons whose
     envelope strictly overlaps the un-buffered tile; none of them intersects the buffered box → only_urban; the union
-    of those that do contains the box → only_forest."""
+    of those that do contains the box → only_forest. One box query against a handful of polygons: it stays on the host
+    (td_region_relate) whatever ``device_outlines`` says — that key moves the per-crown predicates of treedetection_amd.fusion."""
     from .vector import Region, box_ring
     fb = forest_boxes
     cand = np.nonzero((fb[:, 2] > minx) & (fb[:, 0] < minx + tile_width) & (fb[:, 3] > miny) & (fb[:, 1] < miny + tile_height))[0]

@@ -1,6 +1,6 @@
 """Polygon layers in and out of the outline steps: readers for the vector formats the reference opens with
 ``gpd.read_file`` (forest outline ``forrest_outline``: helpers.py:735, preprocessing.py:155; exclude files:
-helpers.py:41) — GeoJSON, GeoPackage and ESRI Shapefile — and the ctypes wrapper of ``td_region_relate``.
+helpers.py:41) — GeoJSON, GeoPackage and ESRI Shapefile — and the ctypes wrapper of ``td_region_relate`` / ``td_region_relate_dev``.
 
 A layer comes back as a list of polygons, each a list of closed rings ``[n,2] float64`` (shell first, then holes);
 MultiPolygons are flattened into their parts (the predicates below work on the union anyway). No reprojection:
@@ -204,21 +204,148 @@ class Region:
             self.bounds = (float(self.xy[:, 0].min()), float(self.xy[:, 1].min()), float(self.xy[:, 0].max()), float(self.xy[:, 1].max()))
         else:
             self.bounds = None
+        self.last_deferred = 0          # queries of the last relate(device=...) that the kernel left to the host function,
+        self.last_deferred_queries = np.zeros(0, dtype=np.int64)          # and which
+        self._index = None              # build_edge_index of this region (False: it does not fit int32), built on first device use
+        self._on_device = {}            # GPU index → the region and its index as uploaded tensors
 
-    def relate(self, queries: Sequence[np.ndarray]) -> Tuple[np.ndarray, np.ndarray]:
-        """closed query rings → (intersects[n], within[n]) against the union of the polygons."""
+    def relate(self, queries: Sequence[np.ndarray], device: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """closed query rings → (intersects[n], within[n]) against the union of the polygons.
+
+        ``device=None``: ``td_region_relate`` on the host. ``device`` = a GPU index: ``td_region_relate_dev`` (regionrelate.hip, a wave
+        per query, the host function's arithmetic) — the region and its y-bin edge index are packed and uploaded once per Region and
+        device and kept on the object, the queries are packed and uploaded, ONE launch on the current stream decides them, flags and
+        status come back, and the queries the kernel left undecided (status 1: a ring or a run of meetings beyond its fixed
+        capacities, ``_lib.RELATE_*_CAP``) — only those — go through the host function; ``last_deferred`` says how many that were.
+        Same flags either way. Rings the host call refuses (not closed, fewer than 4 points) raise what it raises, before any launch.
+        A set the device path does not take (an empty region, a non-finite coordinate, more edges, index entries or queries than
+        int32 holds) is announced in one printed line and served by the host function."""
         n = len(queries)
         flags = np.zeros(n, dtype=np.uint8)
+        self.last_deferred, self.last_deferred_queries = 0, np.zeros(0, dtype=np.int64)
         if n == 0 or self.n_rings == 0:
+            if device is not None and n:
+                _decline("Region.relate", "the region is empty")
             return flags.astype(bool), flags.astype(bool)
         qs = [np.ascontiguousarray(q, dtype=np.float64).reshape(-1, 2) for q in queries]
         q_start = np.zeros(n + 1, dtype=np.int64)
         q_start[1:] = np.cumsum([len(q) for q in qs])
         q_xy = np.concatenate(qs)
+        if device is not None and self._rings_refused(self.xy, self.ring_start) is None and self._rings_refused(q_xy, q_start) is None:
+            why = self._device_declined(q_xy, n)
+            if why is None:
+                flags = self._relate_device(q_xy, q_start, n, int(device))
+                return (flags & 1).astype(bool), (flags & 2).astype(bool)
+            _decline("Region.relate", why)
+        # (a ring the library refuses reaches it here, device or not, and raises there)
+        self._relate_host(q_xy, q_start, n, flags)
+        return (flags & 1).astype(bool), (flags & 2).astype(bool)
+
+    def _relate_host(self, q_xy, q_start, n, flags) -> None:
         st = _lib.load().td_region_relate(self.xy.ctypes.data, self.ring_start.ctypes.data, self.ring_poly.ctypes.data,
                                           self.n_rings, q_xy.ctypes.data, q_start.ctypes.data, n, flags.ctypes.data)
         _lib.check(st, "td_region_relate")
-        return (flags & 1).astype(bool), (flags & 2).astype(bool)
+
+    @staticmethod
+    def _rings_refused(xy: np.ndarray, start: np.ndarray) -> Optional[int]:
+        """Index of the first ring td_region_relate refuses (fewer than 4 points, first != last — a NaN there included), or None."""
+        first, last = xy[start[:-1].clip(max=len(xy) - 1)], xy[(start[1:] - 1).clip(min=0)]
+        bad = (np.diff(start) < 4) | ~((first == last).all(axis=1))
+        return int(np.argmax(bad)) if bad.any() else None
+
+    def _device_declined(self, q_xy: np.ndarray, n: int) -> Optional[str]:
+        """Why td_region_relate_dev must not see this region / these queries, or None."""
+        if not (np.isfinite(self.xy).all() and np.isfinite(q_xy).all()):
+            return "a coordinate is not finite"
+        if len(self.xy) >= INT32_LIMIT or n >= INT32_LIMIT:
+            return f"more than {INT32_LIMIT - 1} region vertices or queries"
+        if self._index is None:
+            self._index = build_edge_index(self.xy, self.ring_start)
+        if self._index is False:
+            return f"more than {INT32_LIMIT - 1} entries in the edge index"
+        return None
+
+    def _relate_device(self, q_xy, q_start, n, device: int) -> np.ndarray:
+        import torch
+
+        lib = _lib.load()
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            up = lambda a: torch.from_numpy(a).to(dev)
+            R = self._on_device.get(device)
+            if R is None:
+                edge_ring, bin_start, bin_edges = self._index[:3]
+                R = self._on_device[device] = {"xy": up(self.xy), "ring_start": up(self.ring_start), "ring_poly": up(self.ring_poly),
+                                               "edge_ring": up(edge_ring), "bin_start": up(bin_start),
+                                               "bin_edges": up(bin_edges if bin_edges.size else np.zeros(1, np.int32)),
+                                               "n_bin_edges": int(bin_edges.size), "checked": False}
+            ymin, ymax, inv_h = self._index[3:]
+            d_q, d_qs = up(q_xy), up(q_start)
+            d_f = torch.empty(n, dtype=torch.uint8, device=dev)
+            d_s = torch.empty(n, dtype=torch.int32, device=dev)
+            _lib.check(lib.td_region_relate_dev(R["xy"].data_ptr(), R["ring_start"].data_ptr(), R["ring_poly"].data_ptr(), self.n_rings,
+                                                len(self.xy), R["edge_ring"].data_ptr(), R["bin_start"].data_ptr(), R["bin_edges"].data_ptr(),
+                                                len(R["bin_start"]) - 1, R["n_bin_edges"], ymin, ymax, inv_h, d_q.data_ptr(), d_qs.data_ptr(),
+                                                n, len(q_xy), d_f.data_ptr(), d_s.data_ptr(), 0 if R["checked"] else 1, _lib.stream_ptr()),
+                       "td_region_relate_dev")
+            R["checked"] = True             # the uploaded index was verified against its arrays by that call
+            flags, status = d_f.cpu().numpy(), d_s.cpu().numpy()
+        if (status == 2).any():             # cannot happen after _rings_refused / _device_declined
+            raise _lib.TdError(f"td_region_relate_dev refused query {int(np.argmax(status == 2))}")
+        deferred = np.flatnonzero(status == 1)
+        self.last_deferred, self.last_deferred_queries = int(deferred.size), deferred
+        if deferred.size:
+            lens = np.diff(q_start)[deferred]
+            sub_start = np.zeros(deferred.size + 1, dtype=np.int64)
+            sub_start[1:] = np.cumsum(lens)
+            sub_xy = np.concatenate([q_xy[q_start[i]:q_start[i + 1]] for i in deferred])
+            sub_flags = np.zeros(deferred.size, dtype=np.uint8)
+            self._relate_host(sub_xy, sub_start, int(deferred.size), sub_flags)
+            flags[deferred] = sub_flags
+        return flags
+
+
+INT32_LIMIT = 2 ** 31 - 1
+
+
+def _decline(who: str, why: str) -> None:
+    from .postprocessing import _decline as decline
+
+    decline(who, why)
+
+
+def build_edge_index(xy: np.ndarray, ring_start: np.ndarray):
+    """The y-bin edge index of ``td_region_relate`` (csrc/region.cpp: same bin count, same bin of a y) as the flat arrays
+    ``td_region_relate_dev`` takes → (edge_ring int32 [n_vertices], bin_start int32 [n_bins + 1], bin_edges int32, ymin, ymax, inv_h),
+    or False when the entries do not fit int32. Edge id = index of the edge's first vertex; an edge is listed in every bin its
+    y-range touches; the ids of a bin ascend. ``xy``: finite closed rings of >= 4 points."""
+    n_rings = len(ring_start) - 1
+    edge_ring = np.repeat(np.arange(n_rings, dtype=np.int32), np.diff(ring_start))
+    is_edge = np.ones(len(xy), dtype=bool)
+    is_edge[ring_start[1:] - 1] = False                  # a ring's closing vertex starts no edge
+    ids = np.flatnonzero(is_edge)
+    y = xy[:, 1]
+    ymin, ymax = float(y.min()), float(y.max())
+    nb = int(min(8192, max(1, len(ids) // 4)))
+    inv_h = nb / (ymax - ymin) if ymax > ymin else 0.0
+
+    def bin_of(v):
+        f = (v - ymin) * inv_h
+        with np.errstate(invalid="ignore"):
+            return np.where(f > 0, np.where(f >= nb, nb - 1, np.floor(np.minimum(f, nb))), 0).astype(np.int64)
+
+    b0, b1 = bin_of(np.fmin(y[ids], y[ids + 1])), bin_of(np.fmax(y[ids], y[ids + 1]))
+    count = b1 - b0 + 1
+    total = int(count.sum())
+    if total >= INT32_LIMIT:
+        return False
+    first = np.cumsum(count) - count
+    bins = np.repeat(b0 - first, count) + np.arange(total)
+    order = np.argsort(bins, kind="stable")              # ids stay ascending inside a bin
+    bin_edges = np.repeat(ids, count)[order].astype(np.int32)
+    bin_start = np.zeros(nb + 1, dtype=np.int32)
+    bin_start[1:] = np.cumsum(np.bincount(bins, minlength=nb))
+    return edge_ring, bin_start, bin_edges, ymin, ymax, float(inv_h)
 
 
 def box_ring(minx, miny, maxx, maxy) -> np.ndarray:
