@@ -435,12 +435,15 @@ def test_chained_images_equal_image_by_image_and_survive_a_bad_image(tmp_path):
     assert read(tmp_path / "seq") == read(tmp_path / "chain")
 
 
-@pytest.mark.parametrize("mode", ["streams", "phases", "plain"])
-def test_launch_failures_do_not_leak_buffer_slots(tmp_path, mode):
+@pytest.mark.parametrize("mode,where", [pytest.param(m, w, id=m if w == "forward" else f"{m}-{w}")
+                                        for w in ("forward", "finish") for m in ("streams", "phases", "plain")])
+def test_launch_failures_do_not_leak_buffer_slots(tmp_path, mode, where):
     """the buffer slots live in ONE free list for the Predictor's lifetime. A launch that fails after the launcher took
-    (batch, slot) from the reader has no epilogue task to return the slot — so the launcher must. The engine's forward is made to
-    fail for MORE images than there are slots (predict_on_model logs and walks on, reference detection.py:117-120); afterwards every
-    slot is back, no stand-in slot stays in the list, and a good image gives the same files as on a fresh predictor."""
+    (batch, slot) from the reader has no epilogue task to return the slot — so the launcher must (Predictor._launch: it owns a slot
+    until its finish step has returned). Made to fail, for MORE images than there are slots (predict_on_model logs and walks on,
+    reference detection.py:117-120): the engine's forward, or ("finish") the finish step after a forward that went through — the
+    device contour tracer of a ``device_contours=True`` predictor raises on the host. Afterwards every slot is back, no stand-in
+    slot stays in the list, and a good image gives the same files as on a fresh predictor."""
     import treedetection_amd as T
     from treedetection_amd.preprocessing import tile_single_file
     sd = make_synthetic_state_dict(50, seed=3, width_div=2)
@@ -451,7 +454,8 @@ def test_launch_failures_do_not_leak_buffer_slots(tmp_path, mode):
     tile_single_file(tif, str(tmp_path / "tiles"), buffer=10, tile_width=40, tile_height=40)
     tj = str(tmp_path / "tiles" / "0.json")
     cfg = T.setup_model_cfg(update_model="x", device="0")
-    kw = dict(pipeline=mode != "plain", schedule=mode if mode != "plain" else "streams")
+    kw = dict(pipeline=mode != "plain", schedule=mode if mode != "plain" else "streams", device_contours=where == "finish")
+    broken = ("forward_raw", "forward_phase") if where == "forward" else ("trace_contours",)
     with T.Predictor(cfg, device_type="0", max_batch_size=2, output_dir=str(tmp_path / "good"), state_dict=sd, **kw) as pred:
         good = pred(tif, tj)
     assert len(good) > 3
@@ -462,16 +466,16 @@ def test_launch_failures_do_not_leak_buffer_slots(tmp_path, mode):
         def boom(*a, **k):
             calls["n"] += 1
             raise RuntimeError("injected launch failure")
-        saved = [(e, e.forward_raw, e.forward_phase) for e in pred._engines]
         for e in pred._engines:
-            e.forward_raw = boom
-            e.forward_phase = boom
+            for name in broken:
+                setattr(e, name, boom)           # (an instance attribute over the method)
         for _ in range(nslots + 3):              # more failed images than slots
             with pytest.raises(RuntimeError, match="injected launch failure"):
                 pred(tif, tj)
         assert calls["n"] >= nslots + 3
-        for e, fr, fp in saved:
-            e.forward_raw, e.forward_phase = fr, fp
+        for e in pred._engines:
+            for name in broken:
+                delattr(e, name)
         assert pred._free.qsize() == nslots
         assert not any(s.transient for s in list(pred._free.queue))
         assert pred(tif, tj) == good

@@ -85,7 +85,8 @@ def test_two_ranks_write_the_same_files_as_one(tmp_path):
     outs = {}
     runs = {"one": (1, {"pipeline": False}),
             "two_plain": (2, {"pipeline": False}),
-            "two_pipelined": (2, {"pipeline": True}),              # three engines per rank, gather on the side stream
+            "two_pipelined": (2, {"pipeline": True}),              # three engines per rank, gather on the engine's stream
+            "two_phases": (2, {"pipeline": True, "schedule": "phases"}),      # … the phase window, gather on the slot's side stream
             "two_local": (2, {"pipeline": True, "sharded_epilogue": "local"})}
     for name, (world, kw) in runs.items():
         out = str(tmp_path / f"out_{name}")

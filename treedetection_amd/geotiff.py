@@ -17,6 +17,7 @@ read, the decoder and layout launches, ``check``) are device_decode.py's; the me
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 import struct
@@ -571,7 +572,7 @@ class GeoTiff:
         buf[span:] = 0
         item = self.dtype.itemsize                              # block sizes, capacities and what a block must decode to count BYTES
         block_cap = self._bw * self._bh * (self.count if self.planar == 1 else 1) * item
-        ctx = torch.cuda.stream(stream) if stream is not None else _NullCtx()
+        ctx = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
         with torch.cuda.device(dev), ctx:
             st = _lib.stream_ptr()
             comp = pin[:span + 16].to(dev, non_blocking=True)
@@ -685,7 +686,7 @@ class GeoTiff:
         if staging is None:
             staging = [torch.empty((4 * piece,), dtype=torch.uint8, pin_memory=True) for _ in range(2)]
         cap = min(t.numel() for t in staging)
-        ctx = torch.cuda.stream(stream) if stream is not None else _NullCtx()
+        ctx = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
         base = int(self._flat.offset)
         with torch.cuda.device(dev), ctx:
             image = torch.empty((self.height, self.width, self.count), dtype=torch.uint8 if self.dtype.itemsize == 1 else torch.uint16, device=dev)
@@ -833,14 +834,6 @@ def device_decode_planar_setting(value=False) -> bool:
     (PlanarConfiguration = 2) go to the device decoders too (``device_decodable(planar=True)``), where ``device_decode`` sends rasters
     there at all. Anything else is refused."""
     return _true_false_setting("device_decode_planar", value)
-
-
-class _NullCtx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        return False
 
 
 def _jpeg_block(blk: np.ndarray, quality: int = 90, subsampling: int = 2, restart: int = 0) -> bytes:

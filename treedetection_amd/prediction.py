@@ -9,12 +9,14 @@ gather to rank 0 (treedetection_amd/distributed.py).
 """
 from __future__ import annotations
 
+import contextlib
 import json
 import os
 import queue
 import threading
 import time
 from concurrent.futures import ThreadPoolExecutor
+from dataclasses import dataclass
 from typing import Dict, List, Optional
 
 import numpy as np
@@ -67,6 +69,10 @@ class _Slot:
         self.submitted = 0.0        # when the batch's epilogue tasks were queued
         self.lock = threading.Lock()
         self.transient = False      # stand-in for a round that has no real slot (reader failure, _drain): never enters a free list
+        self.side = None            # "phases" schedule: the stream of this slot's selection phases (Predictor._launch allocates it)
+        self.mark_id = -1           # index of the launch that filled the slot last (TD_E2E_TRACE marks)
+        self._send = self._classes = self._recv = None      # sharded runs: allocated on first use below
+        self._paste_sets = {}
 
     def staging(self, nbytes: int, device) -> np.ndarray:
         if self.pin_in is None or self.pin_in.numel() < nbytes:
@@ -92,7 +98,7 @@ class _Slot:
 
     # -- sharded runs: send / receive / paste buffers ------------------------------------------------------------
     def gather_buffers(self, B: int, Dn: int, dev) -> Dict[str, torch.Tensor]:
-        if getattr(self, "_send", None) is None or self._send["count"].shape[0] != B:
+        if self._send is None or self._send["count"].shape[0] != B:
             self._send = {"count": torch.zeros((B,), dtype=torch.int32, device=dev),
                           "boxes": torch.zeros((B, Dn, 4), dtype=torch.float32, device=dev),
                           "scores": torch.zeros((B, Dn), dtype=torch.float32, device=dev),
@@ -105,7 +111,7 @@ class _Slot:
         return self._classes
 
     def recv_buffers(self, W: int, B: int, Dn: int, dev, host: bool):
-        if getattr(self, "_recv", None) is None or len(self._recv) != W or self._recv[0]["count"].shape[0] != B:
+        if self._recv is None or len(self._recv) != W or self._recv[0]["count"].shape[0] != B:
             where = torch.device("cpu") if host else dev
             self._recv = [{"count": torch.zeros((B,), dtype=torch.int32, device=where),
                            "boxes": torch.zeros((B, Dn, 4), dtype=torch.float32, device=where),
@@ -116,7 +122,7 @@ class _Slot:
     def paste(self, engine: Engine, src: int, g: Dict[str, torch.Tensor], hw, B: int, Dn: int, dev):
         """Pastes one rank's gathered batch (first len(hw) rows) on this device and queues the copies of what the
         host epilogue reads — packed masks, counts, scores — into pinned memory. → the pinned numpy views."""
-        sets = self.__dict__.setdefault("_paste_sets", {})
+        sets = self._paste_sets
         mh, mw = max(h for h, _ in hw), max(w for _, w in hw)
         cur = sets.get(src)
         if cur is None or cur["key"][0] < B or cur["key"][1] < mh or cur["key"][2] < mw:
@@ -159,6 +165,24 @@ class _Slot:
                 self.pin_cont[k][:n].copy_(v[:n], non_blocking=True)
 
 
+@dataclass
+class _InFlight:
+    """A batch the launcher took from the reader and has not finished yet (Predictor._launch)."""
+    batch: list                                 # the tiles' entries (_read_batch); [] for an empty or failed round
+    slot: _Slot
+    eng: Engine
+    round: int                                  # launch index within the image
+    stream: Optional["torch.cuda.Stream"]       # where ``finish`` enqueues (None = the current stream)
+    phase: int = 0                              # next forward phase to enqueue; 6 = the whole forward is enqueued
+    failed: Optional[BaseException] = None      # EMPTY_ROUND policy: what went wrong with this round
+
+
+# What a read or launch failure does to the image, for the reader and the launcher alike:
+FAIL_IMAGE = "fail_image"        # single process: the error ends the image and surfaces from the launcher
+EMPTY_ROUND = "empty_round"      # tile-sharded: the round still runs, with no detections (every rank issues the same collectives);
+                                 # the error is kept in the record for ``finish``
+
+
 # Who pastes / traces / writes the tile files of a sharded run, by arithmetic (DESIGN.md §6). "rank0": every rank's fixed-shape
 # payload (2.5 MB per 8-tile batch) goes to rank 0, whose GPU pastes for everybody and whose PCIe link carries everybody's packed
 # masks to its host (measured: ~0.83 MB of Prediction JSON and ~5 MB of packed mask rows per 1000x1000 tile on the synthetic
@@ -191,15 +215,22 @@ class Predictor:
         """cfg from ``setup_model_cfg``; ``device_type`` = GPU index ("0", 0) as config["device"] carries it.
         ``state_dict`` lets tests and the bench inject weights instead of reading cfg.MODEL.WEIGHTS.
         ``return_predictions=False`` skips rebuilding the Python list ``__call__`` returns (the reference's own caller
-        ignores it, detection.py:118); the per-tile files are written either way. ``pipeline`` (single-process runs):
-        three engines keep three batches in flight — contraction phases back to back on a main stream, each batch's
-        selection phases on its own side stream (td_engine_forward_phase; same results bit for bit as one plain
-        forward per batch, tests/test_fullsize_gpu.py) — at the price of three weight / workspace replicas.
-        ``schedule`` picks how the three engines overlap: "streams" (default) = every engine runs whole forwards on its
-        own HIP stream, batches round-robin — the HBM-bound kernels (Winograd transforms, thin 1x1 layers, RoIAlign) and
-        the kernel tails of one forward run under the MFMA-bound contractions of the others (bench: 615 vs 554 tiles/s
-        fp32, 1868 vs 1550 fp16); "phases" = the phase pipeline described above."""
+        ignores it, detection.py:118); the per-tile files are written either way. Every run — single process or
+        tile-sharded — goes through one launcher loop (:meth:`_launch`); ``pipeline`` and ``schedule`` pick what it does
+        with a batch. ``pipeline=False``: one engine, whole forwards on the current stream. ``pipeline=True``: three
+        engines (three weight / workspace replicas) and ``schedule`` says how they overlap: "streams" (default) = every
+        engine runs whole forwards on its own HIP stream, batches round-robin — the HBM-bound kernels (Winograd
+        transforms, thin 1x1 layers, RoIAlign) and the kernel tails of one forward run under the MFMA-bound
+        contractions of the others (bench: 615 vs 554 tiles/s fp32, 1868 vs 1550 fp16); "phases" = three batches in
+        flight, contraction phases back to back on a main stream, each batch's selection phases on its slot's side
+        stream (td_engine_forward_phase; same results bit for bit as one plain forward per batch,
+        tests/test_fullsize_gpu.py)."""
         self.cfg = cfg
+        self._pool = self._read_pool = None      # (declared before anything can raise: close() reads them)
+        self._engines: List[Engine] = []
+        self._main = None                        # "phases" schedule: the contraction stream   } allocated by the first
+        self._eng_streams = None                 # "streams" schedule: one stream per engine   } launch that needs them
+        self.totals = None                       # stage seconds of the images before the running one (_roll_stats)
         # LZW, DEFLATE and JPEG rasters are decoded on the GPU, whole, and their tile windows are cut in HBM (GeoTiff.decode_to_device;
         # images this process predicts alone: submit). "auto" / True: every raster that qualifies; False: the host reader for everything
         # (TD_DEVICE_DECODE overrides the default; the post-processing stage reads the same key the same way)
@@ -307,7 +338,9 @@ class Predictor:
         """A new image starts: its stage seconds start at zero; what the previous images spent stays in ``totals`` (a chained walk
         overlaps images, so late epilogue tasks of the previous image land in the new image's counters: only the totals are exact)."""
         with self._stats_lock:
-            tot = self.__dict__.setdefault("totals", dict.fromkeys(self.stats, 0.0))
+            if self.totals is None:
+                self.totals = dict.fromkeys(self.stats, 0.0)
+            tot = self.totals
             for k, v in self.stats.items():
                 tot[k] = tot.get(k, 0.0) + v
             self.stats = dict.fromkeys(self.stats, 0.0)
@@ -316,7 +349,7 @@ class Predictor:
         """Stage seconds (wall and CPU) summed over every image since the predictor was built (or since the caller cleared
         ``totals``), the running image included."""
         with self._stats_lock:
-            tot = dict(self.__dict__.get("totals") or dict.fromkeys(self.stats, 0.0))
+            tot = dict(self.totals or dict.fromkeys(self.stats, 0.0))
             for k, v in self.stats.items():
                 tot[k] = tot.get(k, 0.0) + v
         return tot
@@ -355,20 +388,20 @@ class Predictor:
 
     def close(self) -> None:
         """Stops the host worker threads and releases the engine's device memory."""
-        if getattr(self, "_pool", None) is not None:
+        if self._pool is not None:
             self._pool.shutdown(wait=True)
             self._pool = None
-        if getattr(self, "_read_pool", None) is not None:
+        if self._read_pool is not None:
             self._read_pool.shutdown(wait=True)
             self._read_pool = None
-        if getattr(self, "_raster_pool", None) is not None:
+        if self._raster_pool is not None:
             self._raster_pool.shutdown(wait=True)
             self._raster_pool = None
             self._rasters.clear()
-        if getattr(self, "_upload_pool", None) is not None:
+        if self._upload_pool is not None:
             self._upload_pool.shutdown(wait=True)
             self._upload_pool = self._upload_staging = None
-        for eng in getattr(self, "_engines", []) or []:
+        for eng in self._engines:
             eng.close()
 
     def __enter__(self):
@@ -465,6 +498,19 @@ class Predictor:
             tiles = self._filter_excluded_vars(tiles)
         return tiles
 
+    @staticmethod
+    def _tile_info(tile, h: int, w: int, failed: bool = False) -> dict:
+        """What the launcher and the epilogue know about a tile of a batch besides its pixels."""
+        info = {"orig_height": h, "orig_width": w, "height": h, "width": w,
+                "json_name": tile["json_name"], "tile_id": tile["tile_id"], "meta": tile["meta"]}
+        if failed:
+            info["failed"] = True        # a black stand-in for a crop that failed (_read_batch, keep_failed)
+        return info
+
+    @staticmethod
+    def _prediction_path(pred_subdir, tile) -> str:
+        return os.path.join(pred_subdir, f"Prediction_{os.path.basename(tile['tile_id'])}.json")
+
     # -- one tile: crop → BGR → (16-bit rescale) → device -------------------------------------------------------
     def _process_tile(self, tile, img: GeoTiff, staging: Optional[np.ndarray] = None, staging_off: int = 0):
         """Reference prediction.py:159-176. uint8 rasters: the window is copied (into the pinned ``staging`` buffer at
@@ -478,8 +524,7 @@ class Predictor:
                     raise ValueError("Input shapes do not overlap raster.")
                 if img.count < 3:
                     raise ValueError(f"tile has {img.count} bands, need >= 3")
-                info = {"orig_height": h, "orig_width": w, "height": h, "width": w,
-                        "json_name": tile["json_name"], "tile_id": tile["tile_id"], "meta": tile["meta"]}
+                info = self._tile_info(tile, h, w)
                 # uint8: the window is cut and resized as bytes; uint16: the rule of prediction.py:166-169 and the float resize read
                 # the raster in place (_to_model_input → Engine.preprocess_windows_u16)
                 kind = "devwin" if img.dtype == np.uint8 else "devwin16"
@@ -490,9 +535,7 @@ class Predictor:
                 hwc = img.read_bounds_hwc(tile["bounds"])              # [h, w, bands], band order of the file
             if hwc.shape[2] < 3:
                 raise ValueError(f"tile has {hwc.shape[2]} bands, need >= 3")
-            orig_h, orig_w = hwc.shape[:2]
-            info = {"orig_height": orig_h, "orig_width": orig_w, "height": orig_h, "width": orig_w,
-                    "json_name": tile["json_name"], "tile_id": tile["tile_id"], "meta": tile["meta"]}
+            info = self._tile_info(tile, *hwc.shape[:2])
             if hwc.dtype == np.uint8:                                   # max(band 1) <= 255 by construction
                 if staging is not None:
                     return {"staged": (staging_off, hwc.shape)}, info
@@ -595,9 +638,7 @@ class Predictor:
                         m = img.outside_mask(t["bounds"], c0, r0, w, h)
                         if m is not None:
                             img._mask_outside(staging[offs[k]:offs[k] + h * w * img.count].reshape(h, w, img.count), t["bounds"], c0, r0)
-                        results[k] = ({"staged": (offs[k], (h, w, img.count))},
-                                      {"orig_height": h, "orig_width": w, "height": h, "width": w, "json_name": t["json_name"],
-                                       "tile_id": t["tile_id"], "meta": t["meta"]})
+                        results[k] = ({"staged": (offs[k], (h, w, img.count))}, self._tile_info(t, h, w))
                     for k in range(len(indices)):
                         if results[k][0] is None:
                             print(f"Error processing tile {tiles[indices[k]]['json_name']}: Input shapes do not overlap raster.")
@@ -606,7 +647,7 @@ class Predictor:
         if results is not None:
             pass
         elif staging is not None and getattr(img, "_flat", None) is not None and len(indices) > 1:
-            if getattr(self, "_read_pool", None) is None:
+            if self._read_pool is None:
                 # windows are copied row by row out of the page cache (td_read_window: ~3 us per 4 KB row on tmpfs), eight of them
                 # side by side: e2e fp16, 400 tiles — 2 threads 1 758 tiles/s (reader-bound), 4: 1 851, 8: 1 905
                 nthreads = int(os.environ.get("TD_READ_THREADS", "0")) or max(2, min(8, host_core_share() // 2))
@@ -635,8 +676,7 @@ class Predictor:
                 if staging is not None:
                     staging[off:off + black.size] = 0
                     data = {"staged": (off, black.shape)}
-                info = {"orig_height": h, "orig_width": w, "height": h, "width": w, "json_name": tiles[idx]["json_name"],
-                        "tile_id": tiles[idx]["tile_id"], "meta": tiles[idx]["meta"], "failed": True}
+                info = self._tile_info(tiles[idx], h, w, failed=True)
             if data is None:
                 if dropped is not None:
                     dropped.append(idx)
@@ -646,26 +686,6 @@ class Predictor:
                 entry["raster"] = raster
             batch.append(entry)
         return batch
-
-    def _launch_batch(self, batch, slot: _Slot, pred_subdir, tifpath):
-        """Forward + asynchronous copy of the packed results to pinned memory; the per-tile host epilogue is queued on
-        the worker pool and waits on the slot's event, so this thread goes straight on to the next batch."""
-        try:
-            images, fmt, hw_valid, hw_out = self._to_model_input(batch, slot)
-            dev_out = slot.outputs(self.engine, len(batch), max(h for h, _ in hw_out), max(w for _, w in hw_out), self.device_contours)
-            view = {k: v[: len(batch)] for k, v in dev_out.items()}     # leading-dim slices stay contiguous
-            self.engine.forward_raw(images, fmt, hw_valid, hw_out, view)
-            slot.traced = self._contour_policy()
-            if slot.traced:
-                self.engine.trace_contours(view, slot.dev_cont, len(batch))
-            slot.copy_results(len(batch), slot.traced)
-            slot.event.record()
-        except BaseException:
-            # no epilogue task exists yet that would return the slot: the launcher does (the free list lives as long as the
-            # Predictor; predict_on_model logs the image's error and walks on, so a slot lost here would be lost for good)
-            self._give_back(slot, self._free)
-            raise
-        return self._submit_epilogue(batch, slot, pred_subdir, tifpath)
 
     def _submit_epilogue(self, batch, slot: _Slot, pred_subdir, tifpath) -> list:
         """Queues the host epilogue of a launched batch → its futures. Where only the files are wanted (``return_predictions=False``:
@@ -680,16 +700,28 @@ class Predictor:
         slot.pending = len(batch)
         return [self._pool.submit(self._process_and_save_single, b, i, slot, pred_subdir, tifpath, self._free) for i, b in enumerate(batch)]
 
-    def _save_batch(self, batch, slot: _Slot, pred_subdir, tifpath, free: "queue.Queue"):
+    @contextlib.contextmanager
+    def _epilogue_task(self, slot: _Slot, free: "queue.Queue"):
+        """Around the body of every epilogue task: however it ends, the task counts itself off its slot, and the batch's last
+        one gives the slot back to the free list its call captured."""
         try:
+            yield
+        finally:
+            with slot.lock:
+                slot.pending -= 1
+                if slot.pending == 0:
+                    self._give_back(slot, free)
+
+    def _save_batch(self, batch, slot: _Slot, pred_subdir, tifpath, free: "queue.Queue"):
+        with self._epilogue_task(slot, free):
             t0 = time.perf_counter()
             c0 = time.thread_time() if self._cpu_stats else 0.0
             slot.event.synchronize()
             t1 = time.perf_counter()
             self._mark("epi", 0)
-            self._mark("batch_done", getattr(slot, "mark_id", -1))
+            self._mark("batch_done", slot.mark_id)
             n = len(batch)
-            paths = [os.path.join(pred_subdir, f"Prediction_{os.path.basename(b['tile_id'])}.json") for b in batch]
+            paths = [self._prediction_path(pred_subdir, b) for b in batch]
             tr = np.array([b["meta"]["transform"][:6] for b in batch], dtype=np.float64)
             batch_prediction_files(self.device_index, slot.host, n, slot.bits_ptr(0), tr, tifpath, paths, threads=self._epilogue_threads)
             self._mark("epi_done", n - 1)
@@ -699,15 +731,10 @@ class Predictor:
                 if self._cpu_stats:
                     self.stats["epilogue_cpu"] += time.thread_time() - c0      # (this thread only: the call's C threads are in the process total)
             return []
-        finally:
-            with slot.lock:
-                slot.pending -= 1
-                if slot.pending == 0:
-                    self._give_back(slot, free)
 
     def _process_and_save_single(self, b, i, slot: _Slot, pred_subdir, tifpath, free: "queue.Queue"):
         """Reference prediction.py:198-266 for one tile: polygons of its instance masks → Prediction_<tile>.json."""
-        try:
+        with self._epilogue_task(slot, free):
             t0 = time.perf_counter()
             c0 = time.thread_time() if self._cpu_stats else 0.0
             if self._contours_auto:
@@ -716,29 +743,25 @@ class Predictor:
             t1 = time.perf_counter()
             self._mark("epi", i)
             if i == 0:
-                self._mark("batch_done", getattr(slot, "mark_id", -1))      # the batch's results have left the GPU (first worker to see it)
+                self._mark("batch_done", slot.mark_id)      # the batch's results have left the GPU (first worker to see it)
             host = slot.host
-            output_file = os.path.join(pred_subdir, f"Prediction_{os.path.basename(b['tile_id'])}.json")
+            output_file = self._prediction_path(pred_subdir, b)
             n = int(host["count"][i])
+            text = None
             if slot.traced:
                 hc = slot.host_cont
                 args = (hc["points"][i], hc["det_info"][i], hc["contour_info"][i], host["mask_region"][i], host["mask_offset"][i])
                 tail = (host["scores"][i][:n], host["classes"][i], b["meta"]["transform"], tifpath)
                 text = tile_polygons_json_dev(*args, None, *tail)
-                if text is None:
-                    # a detection too large / too fragmented for the device tracer (its region exceeds the 56-KB label image): this
-                    # tile goes through the host path — only the words the paste wrote are fetched, not the worst-case buffer
-                    # (12.8 MB per 1000 x 1000 tile: on the compact-crown fixture most tiles hold one such crown)
-                    tile_prediction_file(self.device_index, host["mask_region"][i], host["mask_offset"][i], slot.bits_ptr(i),
-                                         host["mask_bits"][i], host["scores"][i][:n], host["classes"][i], b["meta"]["transform"],
-                                         tifpath, output_file)
-            else:
-                # rows fetched (only the words written), traced, formatted and written by one call without the GIL
-                text = None
+            if text is None:
+                # the host path — rows fetched (only the words the paste wrote, not the worst-case buffer: 12.8 MB per 1000 x 1000
+                # tile), traced, formatted and written by one call without the GIL. Also for a traced batch's tile with a detection
+                # too large / too fragmented for the device tracer (its region exceeds the 56-KB label image; on the compact-crown
+                # fixture most tiles hold one such crown)
                 tile_prediction_file(self.device_index, host["mask_region"][i], host["mask_offset"][i], slot.bits_ptr(i),
                                      host["mask_bits"][i], host["scores"][i][:n], host["classes"][i], b["meta"]["transform"],
                                      tifpath, output_file)
-            if text is not None:
+            else:
                 with open(output_file, "wb") as f:
                     f.write(text)
             res = []
@@ -754,156 +777,125 @@ class Predictor:
                 if self._cpu_stats:
                     self.stats["epilogue_cpu"] += time.thread_time() - c0
             return res
-        finally:
-            with slot.lock:
-                slot.pending -= 1
-                if slot.pending == 0:
-                    self._give_back(slot, free)
 
-    def _finish_local(self, item, pred_subdir, tifpath, futures, stream=None) -> None:
-        """A batch's last phase is enqueued: packed results → pinned memory (on ``stream``), epilogue tasks queued."""
-        batch, slot, eng = item["batch"], item["slot"], item["eng"]
-        ctx = torch.cuda.stream(stream) if stream is not None else _null_ctx()
-        try:
-            with ctx:
-                slot.traced = self._contour_policy()
-                if slot.traced:
-                    eng.trace_contours({k: v[: len(batch)] for k, v in slot.dev_out.items()}, slot.dev_cont, len(batch))
-                slot.copy_results(len(batch), slot.traced)
-                slot.event.record()
-        except BaseException:
-            self._give_back(slot, self._free)       # no epilogue task will: see _launch_batch
-            raise
+    def _finish_local(self, item: _InFlight, pred_subdir, tifpath, futures) -> None:
+        """``finish`` of a run that writes its own tiles: the batch's forward is enqueued — packed results → pinned memory (on
+        ``item.stream``), epilogue tasks queued."""
+        batch, slot = item.batch, item.slot
+        with torch.cuda.stream(item.stream) if item.stream is not None else contextlib.nullcontext():
+            slot.traced = self._contour_policy()
+            if slot.traced:
+                item.eng.trace_contours({k: v[: len(batch)] for k, v in slot.dev_out.items()}, slot.dev_cont, len(batch))
+            slot.copy_results(len(batch), slot.traced)
+            slot.event.record()
         futures.extend(self._submit_epilogue(batch, slot, pred_subdir, tifpath))
 
-    def _launch_pipelined(self, ready, prepare, finish, total_rounds: Optional[int] = None) -> None:
-        """Launcher loop of a pipelined run. Tick t enqueues, on the main stream, the trunk of batch t, the mask-head
-        convs of batch t-2 and the box-head FCs of batch t-1, and on each batch's own side stream the selection phase
-        that follows; after a batch's last phase ``finish(item)`` runs (single process: copy the packed results to
-        pinned memory on the side stream and queue the epilogue tasks; sharded: the gather to rank 0).
-        ``prepare(item, eng)`` → the engine-output views of a new batch. Batches arrive in order from ``ready``;
-        ``finish`` is called once per batch, in that same order, ALSO for empty or failed batches (``item["failed"]``)
-        — the sharded run pairs one collective with every round on every rank. With ``total_rounds`` the loop ends
-        after that many batches (no end marker is expected)."""
-        if self.schedule == "streams":
-            return self._launch_streams(ready, prepare, finish, total_rounds)
-        if getattr(self, "_main", None) is None:
+    def _launch(self, ready, prepare, finish, rounds: Optional[int], policy: str) -> None:
+        """THE launcher loop: every run's batches go from the reader's ``ready`` queue to the GPU through here. It takes
+        ``(batch, slot)``, has the schedule enqueue the forward (:meth:`_enqueue`; ``prepare(item, hw_out)`` → the engine-output
+        views of a new batch) and then calls ``finish(item)`` — single process: result copies + epilogue tasks
+        (:meth:`_finish_local`); tile-sharded: the gather to rank 0 — once per batch, in arrival order. It ends after
+        ``rounds`` batches, or with ``rounds=None`` at the reader's end marker ``(None, None)``.
+
+        The schedule (``pipeline`` / ``schedule``) decides engine and stream of batch k and nothing else: "plain" = the one
+        engine, whole forwards on the current stream; "streams" = engine k mod 3, the whole forward and ``finish`` on that
+        engine's stream, so an engine's batches follow each other in stream order and nothing else needs ordering; "phases" =
+        engine k mod 3 with up to three batches in flight: a tick enqueues, on the main stream, the trunk of the newest batch,
+        then the mask-head convs of the oldest, then the box-head FCs of the middle one (every contraction then finds the
+        selection phase it waits on enqueued a whole trunk earlier), each followed by its selection phase on the batch's side
+        stream, where ``finish`` runs too. An engine is free for a new batch as soon as its previous batch's last phase is
+        ENQUEUED; the slot — pinned buffers the host epilogue reads — stays busy longer, hence more slots than engines.
+
+        ``policy``: FAIL_IMAGE — an exception object from the reader is re-raised, an empty batch returns its slot and is
+        skipped, a batch whose forward cannot be enqueued raises. EMPTY_ROUND — nothing is raised here: the failure is kept
+        in ``item.failed`` and the round still calls ``finish``, with no detections.
+
+        WHO OWNS A SLOT (the one rule; nothing else in this file gives a launcher's slot back): the launcher holds every slot
+        it has taken from ``ready`` until ``finish`` has returned normally for it — from then on the slot belongs to the
+        epilogue tasks ``finish`` queued (:meth:`_epilogue_task`) or to :meth:`_release_when_done`. If anything raises before
+        that, the launcher gives back every slot it still holds, the current one and the window, then re-raises: no task
+        exists that would, and in a single process the free list lives as long as the Predictor (predict_on_model logs the
+        image's error and walks on, so a slot lost here would be lost for good). Stand-in slots never enter a free list
+        (:meth:`_give_back`). Slots that never reached the launcher are the reader's and :meth:`_drain`'s."""
+        schedule = self.schedule if self.pipeline else "plain"
+        if schedule == "streams" and self._eng_streams is None:
+            self._eng_streams = [torch.cuda.Stream() for _ in self._engines]
+        if schedule == "phases" and self._main is None:
             self._main = torch.cuda.Stream()
             for slot in self._slots:
                 slot.side = torch.cuda.Stream()
-        main = self._main
-        window = []                 # batches in flight, oldest first
-        done = False
+        held: List[_InFlight] = []      # taken from `ready`, not finished: oldest first ("phases": the window; else one at most)
         launched = 0
-        while not done or window:
-            if not done:
-                t0 = time.perf_counter()
-                batch, slot = ready.get()
-                self.stats["launch_wait"] += time.perf_counter() - t0
-                if isinstance(batch, BaseException) and total_rounds is None:
-                    raise batch
-                if batch is None:
-                    done = True
-                elif not batch and total_rounds is None:
-                    self._free.put(slot)
-                    continue
-                else:
-                    # engines rotate over the batches: an engine is free for a new batch as soon as its previous
-                    # batch's last phase is ENQUEUED (phase 0 waits on that batch's events on the device); the slot —
-                    # pinned buffers the host epilogue reads — stays busy longer, hence more slots than engines
-                    item = {"batch": batch, "slot": slot, "phase": 0, "eng": self._engines[launched % len(self._engines)],
-                            "failed": None, "round": launched}
-                    if isinstance(batch, BaseException):
-                        item["failed"], item["batch"] = batch, []
-                    window.append(item)
-                    launched += 1
-                    if total_rounds is not None and launched == total_rounds:
+        done = rounds == 0
+        try:
+            while not done or held:
+                new = None
+                if not done:
+                    t0 = time.perf_counter()
+                    batch, slot = ready.get()
+                    self.stats["launch_wait"] += time.perf_counter() - t0
+                    failed = batch if isinstance(batch, BaseException) else None
+                    if batch is None:
                         done = True
-            t0 = time.perf_counter()
-            # the newest batch's trunk leads the tick, then the mask convs of the oldest, then the FCs of the middle one:
-            # every contraction then finds the selection phase it waits on enqueued a whole trunk earlier
-            for item in sorted(window, key=lambda it: (0, 2, 1)[it["phase"] // 2]):
-                batch, slot, phase, eng = item["batch"], item["slot"], item["phase"], item["eng"]
-                if batch and item["failed"] is None:
-                    try:
-                        if phase == 0:
-                            with torch.cuda.stream(main):      # allocations (and their fills) are ordered with the kernels
-                                images, fmt, hw_valid, hw_out = self._to_model_input(batch, slot, eng)
-                                view = prepare(item, eng, hw_out)
-                            eng.forward_phase(0, main, images, fmt, hw_valid, hw_out, view)
-                        else:
-                            eng.forward_phase(phase, main)
-                        eng.forward_phase(phase + 1, slot.side)
-                    except Exception as e:
-                        if total_rounds is None:
-                            # single process: the image fails as a whole. Every batch still in the window holds a slot that
-                            # no epilogue task will return (finish() never ran for it) — hand them back before raising
-                            for it in window:
-                                self._give_back(it["slot"], self._free)
-                            raise
-                        item["failed"] = e       # sharded: the round still takes part in its gather, with no detections
-                item["phase"] = phase + 2
-            # batches finish in arrival order (a failed or empty one may be "ready" early: it waits for its elders)
-            while window and window[0]["phase"] >= 6:
-                item = window.pop(0)
-                try:
-                    finish(item)
-                except BaseException:
-                    # finish() hands back its OWN slot when it fails (_finish_local); the batches still in the window hold
-                    # slots no epilogue task will ever return — single process: give them back before the image fails
-                    if total_rounds is None:
-                        for it in window:
-                            self._give_back(it["slot"], self._free)
-                        del window[:]
-                    raise
-            self.stats["launch"] += time.perf_counter() - t0
+                    elif policy == FAIL_IMAGE and failed is not None:
+                        raise failed                # (comes without a slot: the reader gave its own back)
+                    elif policy == FAIL_IMAGE and not batch:
+                        self._give_back(slot, self._free)       # every tile of the batch was dropped: nothing to launch
+                        continue
+                    else:
+                        k = launched % len(self._engines)
+                        stream = self._eng_streams[k] if schedule == "streams" else slot.side      # (side: None but under "phases")
+                        new = _InFlight([] if failed else batch, slot, self._engines[k], launched, stream, failed=failed)
+                        held.append(new)
+                        launched += 1
+                        done = launched == rounds
+                        slot.mark_id = new.round
+                        self._mark("launch", new.round)
+                t0 = time.perf_counter()
+                c0 = time.thread_time() if self._cpu_stats else 0.0
+                for item in sorted(held, key=lambda it: (0, 2, 1)[it.phase // 2]):
+                    if item.batch and item.failed is None:
+                        try:
+                            self._enqueue(item, prepare, schedule)
+                        except Exception as e:
+                            if policy == FAIL_IMAGE:
+                                raise
+                            item.failed = e
+                    item.phase += 2 if schedule == "phases" else 6
+                # batches finish in arrival order (a failed or empty one may be "ready" early: it waits for its elders)
+                while held and held[0].phase >= 6:
+                    finish(held[0])
+                    del held[0]
+                self.stats["launch"] += time.perf_counter() - t0
+                if self._cpu_stats:
+                    self.stats["launch_cpu"] += time.thread_time() - c0
+                if new is not None:
+                    self._mark("launch_done", new.round)
+        except BaseException:
+            for item in held:
+                self._give_back(item.slot, self._free)
+            raise
 
-    def _launch_streams(self, ready, prepare, finish, total_rounds: Optional[int] = None) -> None:
-        """Launcher loop of the "streams" schedule: batch k runs as ONE whole forward on the HIP stream of engine
-        k mod 3 (its input copies, the forward and ``finish`` — result copies or the gather — all on that stream, so an
-        engine's batches follow each other in stream order and nothing else needs ordering). Same contract as
-        :meth:`_launch_pipelined`: ``finish`` once per batch in arrival order, also for empty / failed batches."""
-        if getattr(self, "_eng_streams", None) is None:
-            self._eng_streams = [torch.cuda.Stream() for _ in self._engines]
-        launched = 0
-        while total_rounds is None or launched < total_rounds:
-            t0 = time.perf_counter()
-            batch, slot = ready.get()
-            self.stats["launch_wait"] += time.perf_counter() - t0
-            if isinstance(batch, BaseException) and total_rounds is None:
-                raise batch
-            if batch is None:
-                break
-            if not batch and total_rounds is None:
-                self._free.put(slot)
-                continue
-            k = launched % len(self._engines)
-            eng, stream = self._engines[k], self._eng_streams[k]
-            item = {"batch": batch, "slot": slot, "phase": 6, "eng": eng, "failed": None, "round": launched}
-            if isinstance(batch, BaseException):
-                item["failed"], item["batch"] = batch, []
-            launched += 1
-            slot.mark_id = launched - 1
-            self._mark("launch", launched - 1)
-            t0 = time.perf_counter()
-            c0 = time.thread_time() if self._cpu_stats else 0.0
-            slot.side = stream               # where finish() enqueues this batch's copies / gather
-            if item["batch"] and item["failed"] is None:
-                try:
-                    with torch.cuda.stream(stream):      # allocations (and their fills) are ordered with the kernels
-                        images, fmt, hw_valid, hw_out = self._to_model_input(item["batch"], slot, eng)
-                        view = prepare(item, eng, hw_out)
-                        eng.forward_raw(images, fmt, hw_valid, hw_out, view)
-                except Exception as e:
-                    if total_rounds is None:
-                        self._give_back(slot, self._free)       # taken from `ready`, never handed to an epilogue task
-                        raise
-                    item["failed"] = e       # sharded: the round still takes part in its gather, with no detections
-            finish(item)
-            self.stats["launch"] += time.perf_counter() - t0
-            if self._cpu_stats:
-                self.stats["launch_cpu"] += time.thread_time() - c0
-            self._mark("launch_done", launched - 1)
+    def _enqueue(self, item: _InFlight, prepare, schedule: str) -> None:
+        """Enqueues the next part of a batch's forward: all of it on the batch's stream, or under "phases" the contraction
+        phase ``item.phase`` on the main stream and the selection phase after it on the slot's side stream. The input copies
+        and ``prepare`` run inside the stream context of the batch's first kernels: allocations (and their fills) are ordered
+        with the kernels."""
+        eng, slot = item.eng, item.slot
+        if schedule != "phases":
+            with torch.cuda.stream(item.stream) if item.stream is not None else contextlib.nullcontext():
+                images, fmt, hw_valid, hw_out = self._to_model_input(item.batch, slot, eng)
+                view = prepare(item, hw_out)
+                eng.forward_raw(images, fmt, hw_valid, hw_out, view)
+            return
+        if item.phase == 0:
+            with torch.cuda.stream(self._main):
+                images, fmt, hw_valid, hw_out = self._to_model_input(item.batch, slot, eng)
+                view = prepare(item, hw_out)
+            eng.forward_phase(0, self._main, images, fmt, hw_valid, hw_out, view)
+        else:
+            eng.forward_phase(item.phase, self._main)
+        eng.forward_phase(item.phase + 1, slot.side)
 
     @staticmethod
     def _transient_slot() -> _Slot:
@@ -957,22 +949,17 @@ class Predictor:
         except Exception:
             pass
 
-    def _run_single(self, tiles, img: GeoTiff, pred_subdir, tifpath):
-        return self._start_single(tiles, img, pred_subdir, tifpath).result()
-
-    def _start_single(self, tiles, img: GeoTiff, pred_subdir, tifpath) -> "_PendingImage":
-        """Reads and launches every batch of one image; returns when the last batch is ENQUEUED (the raster is no longer
-        needed then). What is still running — the last forwards on the GPU, the epilogue workers of the last batches — is
-        waited for by ``.result()`` of the returned handle; meanwhile the next image may be started: its batches queue up
-        behind these on the engines' streams and its reader takes slots as the epilogue workers return them."""
-        B = self.max_batch_size
-        rounds = [list(range(r * B, min((r + 1) * B, len(tiles)))) for r in range((len(tiles) + B - 1) // B)]
-        self._roll_stats()
-        ready: "queue.Queue" = queue.Queue(maxsize=2)
-        stop = threading.Event()
-        dropped: List[int] = []
-
+    def _start_reader(self, tiles, rounds, img: GeoTiff, ready, stop, policy: str, keep_failed: bool = False,
+                      dropped: Optional[list] = None) -> threading.Thread:
+        """Starts the reader thread of one image: per round (a list of tile indices) it waits for a free slot, crops the
+        round's tiles into it (:meth:`_read_batch`) and puts ``(batch, slot)`` on ``ready``. FAIL_IMAGE: any error ends the
+        image — the reader returns its slot and hands the exception to the launcher; after the last round comes the end
+        marker. EMPTY_ROUND: a read error makes this round an empty one (the exception travels in the batch's place), and
+        when no slot can be had any more every remaining round gets a stand-in slot, NOT one of ``self._slots`` — those may be
+        in flight for other batches, and ``finish`` zeroes / gathers into / pastes from the slot it is given — so the launcher
+        still sees ``len(rounds)`` rounds."""
         def reader():
+            k = 0
             try:
                 for k, indices in enumerate(rounds):
                     self._mark("slot_wait", k)
@@ -986,46 +973,53 @@ class Predictor:
                     t0 = time.perf_counter()
                     c0 = time.thread_time() if self._cpu_stats else 0.0
                     try:
-                        batch = self._read_batch(tiles, indices, img, slot, dropped=dropped)
-                    except BaseException:
-                        self._give_back(slot, self._free)
-                        raise
+                        batch = self._read_batch(tiles, indices, img, slot, keep_failed, dropped)
+                    except Exception as e:
+                        if policy == FAIL_IMAGE:
+                            self._give_back(slot, self._free)
+                            raise
+                        batch = e
                     self.stats["read"] += time.perf_counter() - t0
                     if self._cpu_stats:
                         with self._stats_lock:
                             self.stats["read_cpu"] += time.thread_time() - c0
-                            self.stats["tiles"] += len(batch)
+                            self.stats["tiles"] += len(batch) if isinstance(batch, list) else 0
                     self._mark("read_done", k)
                     ready.put((batch, slot))
-                ready.put((None, None))
-            except BaseException as e:      # surfaces in the launcher thread
-                ready.put((e, None))
+                if policy == FAIL_IMAGE:
+                    ready.put((None, None))
+            except BaseException as e:
+                if policy == FAIL_IMAGE:
+                    ready.put((e, None))        # surfaces in the launcher thread
+                else:
+                    for _ in range(k, len(rounds)):
+                        ready.put((e, self._transient_slot()))
 
-        t = threading.Thread(target=reader, name="td-tile-reader", daemon=True)
-        t.start()
+        th = threading.Thread(target=reader, name="td-tile-reader", daemon=True)
+        th.start()
+        return th
+
+    def _start_single(self, tiles, img: GeoTiff, pred_subdir, tifpath) -> "_PendingImage":
+        """Reads and launches every batch of one image; returns when the last batch is ENQUEUED (the raster is no longer
+        needed then). What is still running — the last forwards on the GPU, the epilogue workers of the last batches — is
+        waited for by ``.result()`` of the returned handle; meanwhile the next image may be started: its batches queue up
+        behind these on the engines' streams and its reader takes slots as the epilogue workers return them."""
+        B = self.max_batch_size
+        rounds = [list(range(r * B, min((r + 1) * B, len(tiles)))) for r in range((len(tiles) + B - 1) // B)]
+        self._roll_stats()
+        ready: "queue.Queue" = queue.Queue(maxsize=2)
+        stop = threading.Event()
+        dropped: List[int] = []
         futures: list = []
+
+        def prepare(item, hw_out):
+            n = len(item.batch)
+            dev_out = item.slot.outputs(item.eng, n, max(h for h, _ in hw_out), max(w for _, w in hw_out), self.device_contours)
+            return {k: v[:n] for k, v in dev_out.items()}      # leading-dim slices stay contiguous
+
+        t = self._start_reader(tiles, rounds, img, ready, stop, FAIL_IMAGE, dropped=dropped)
         try:
-            while not self.pipeline:
-                t0 = time.perf_counter()
-                batch, slot = ready.get()
-                self.stats["launch_wait"] += time.perf_counter() - t0
-                if isinstance(batch, BaseException):
-                    raise batch
-                if batch is None:
-                    break
-                if not batch:
-                    self._free.put(slot)
-                    continue
-                t0 = time.perf_counter()
-                futures.extend(self._launch_batch(batch, slot, pred_subdir, tifpath))
-                self.stats["launch"] += time.perf_counter() - t0
-            if self.pipeline:
-                def prepare(item, eng, hw_out):
-                    slot, n = item["slot"], len(item["batch"])
-                    dev_out = slot.outputs(eng, n, max(h for h, _ in hw_out), max(w for _, w in hw_out), self.device_contours)
-                    return {k: v[:n] for k, v in dev_out.items()}      # leading-dim slices stay contiguous
-                self._launch_pipelined(ready, prepare,
-                                       lambda item: self._finish_local(item, pred_subdir, tifpath, futures, item["slot"].side))
+            self._launch(ready, prepare, lambda item: self._finish_local(item, pred_subdir, tifpath, futures), None, FAIL_IMAGE)
             t.join()
             return _PendingImage(self, futures, dropped)
         except BaseException:
@@ -1040,8 +1034,8 @@ class Predictor:
         return w > 0 and h > 0 and img.count >= 3
 
     def _run_sharded(self, tiles, img: GeoTiff, pred_subdir, tifpath):
-        """Rank r predicts tiles r, r+W, r+2W, ... in batches (the plain loop or, with ``pipeline``, three engines with
-        three batches in flight, exactly as a single process runs them); after a batch's last phase its fixed-shape
+        """Rank r predicts tiles r, r+W, r+2W, ... in batches (the same launcher and schedules as a single process:
+        :meth:`_launch` under the EMPTY_ROUND policy); after a batch's last phase its fixed-shape
         detection tensors (count, boxes, scores, 28x28 probabilities) go to rank 0 with ``torch.distributed.gather``
         (RCCL on GPUs: enqueued on the batch's side stream and ordered on the device, nobody waits on the host).
         Rank 0 pastes each rank's batch with one td_paste_masks_batch launch, copies the packed masks to pinned memory
@@ -1072,50 +1066,29 @@ class Predictor:
         stop = threading.Event()
         errors: List[BaseException] = []
 
-        def reader():
-            k = 0
-            try:
-                for k in range(rounds):
-                    slot = self._free.get()
-                    if stop.is_set():
-                        return
-                    t0 = time.perf_counter()
-                    try:
-                        batch = self._read_batch(tiles, round_tiles(me, k), img, slot, keep_failed=True)
-                    except Exception as e:          # this round runs empty; the image is reported failed at the end
-                        batch = e
-                    self.stats["read"] += time.perf_counter() - t0
-                    ready.put((batch, slot))
-            except BaseException as e:              # cannot get slots any more: fail the remaining rounds, keep the count
-                for _ in range(k, rounds):
-                    # a stand-in slot per failed round, NOT one of self._slots: those may be in flight for other
-                    # batches, and finish() zeroes / gathers into / pastes from the slot it is given
-                    ready.put((e, self._transient_slot()))
-
-        th = threading.Thread(target=reader, name="td-tile-reader", daemon=True)
-        th.start()
+        # (a read or launch failure: this round runs empty, the image is reported failed at the end)
+        th = self._start_reader(tiles, [round_tiles(me, k) for k in range(rounds)], img, ready, stop, EMPTY_ROUND, keep_failed=True)
         futures, predictions = [], []
 
-        def prepare(item, eng, hw_out):
-            slot, n = item["slot"], len(item["batch"])
+        def prepare(item, hw_out):
+            slot, n = item.slot, len(item.batch)
             send = slot.gather_buffers(B, Dn, dev)          # count / boxes / scores / mask_probs padded to B rows
             view = {key: send[key][:n] for key in ("count", "boxes", "scores", "mask_probs")}
             view["classes"] = slot.classes_buffer(B, Dn, dev)[:n]
             return view
 
-        def finish(item, stream=None):
-            """Gather of round item["round"] (+ on rank 0: paste, copies, epilogue tasks) on ``stream``."""
-            slot, k = item["slot"], item["round"]
-            n = 0 if item["failed"] is not None else len(item["batch"])
-            if item["failed"] is not None:
-                errors.append(item["failed"])
-            ctx = torch.cuda.stream(stream) if stream is not None else _null_ctx()
-            with ctx:
+        def finish(item):
+            """Gather of round item.round (+ on rank 0: paste, copies, epilogue tasks) on ``item.stream``."""
+            slot, k = item.slot, item.round
+            n = 0 if item.failed is not None else len(item.batch)
+            if item.failed is not None:
+                errors.append(item.failed)
+            with torch.cuda.stream(item.stream) if item.stream is not None else contextlib.nullcontext():
                 send = slot.gather_buffers(B, Dn, dev)
                 if n < B:
                     send["count"][n:].zero_()
                 for j in range(n):
-                    if item["batch"][j].get("failed"):          # a black stand-in for a tile whose crop failed: no file for it
+                    if item.batch[j].get("failed"):          # a black stand-in for a tile whose crop failed: no file for it
                         send["count"][j:j + 1].fill_(-1)
                 recv = slot.recv_buffers(W, B, Dn, dev, host_backend) if me == 0 else None
                 for key in D.GATHER_KEYS:
@@ -1149,25 +1122,7 @@ class Predictor:
                     futures.append(self._pool.submit(self._save_gathered, slot, pin, j, tiles[ti], pred_subdir, tifpath, free))
 
         try:
-            if self.pipeline:
-                self._launch_pipelined(ready, prepare, lambda item: finish(item, item["slot"].side), total_rounds=rounds)
-            else:
-                for k in range(rounds):
-                    t0 = time.perf_counter()
-                    batch, slot = ready.get()
-                    self.stats["launch_wait"] += time.perf_counter() - t0
-                    t0 = time.perf_counter()
-                    item = {"batch": batch, "slot": slot, "eng": self.engine, "failed": None, "round": k}
-                    if isinstance(batch, BaseException):
-                        item["failed"], item["batch"] = batch, []
-                    if item["batch"]:
-                        try:
-                            images, fmt, hw_valid, hw_out = self._to_model_input(item["batch"], slot)
-                            self.engine.forward_raw(images, fmt, hw_valid, hw_out, prepare(item, self.engine, hw_out))
-                        except Exception as e:
-                            item["failed"] = e
-                    finish(item)
-                    self.stats["launch"] += time.perf_counter() - t0
+            self._launch(ready, prepare, finish, rounds, EMPTY_ROUND)
             th.join()
             for f in futures:
                 try:
@@ -1199,11 +1154,7 @@ class Predictor:
             preds = handle.result()
         except Exception as e:
             err = e
-        written = []
-        for i in mine:
-            fn = os.path.join(pred_subdir, f"Prediction_{os.path.basename(tiles[i]['tile_id'])}.json")
-            if os.path.exists(fn):
-                written.append(i)
+        written = [i for i in mine if os.path.exists(self._prediction_path(pred_subdir, tiles[i]))]
         manifests = D.gather_objects((written, dropped))
         if me == 0 and err is None:
             seen = sorted(i for m, _ in manifests for i in m)
@@ -1229,12 +1180,12 @@ class Predictor:
         return []
 
     def _save_gathered(self, slot: _Slot, pin, j, tile, pred_subdir, tifpath, free: "queue.Queue"):
-        try:
+        with self._epilogue_task(slot, free):
             slot.event.synchronize()
             n = int(pin["count"][j])
             if n < 0:           # the owning rank could not crop this tile: dropped, as the reference drops it (prediction.py:174-176)
                 return []
-            path = os.path.join(pred_subdir, f"Prediction_{os.path.basename(tile['tile_id'])}.json")
+            path = self._prediction_path(pred_subdir, tile)
             tile_prediction_file(self.device_index, pin["mask_region"][j], pin["mask_offset"][j],
                                  pin["bits_base"] + j * pin["bits_stride"], pin["mask_bits"][j], pin["scores"][j][:n],
                                  np.zeros(n, np.int32), tile["meta"]["transform"], tifpath, path)
@@ -1242,11 +1193,6 @@ class Predictor:
                 return []
             with open(path, "rb") as f:
                 return json.loads(f.read())
-        finally:
-            with slot.lock:
-                slot.pending -= 1
-                if slot.pending == 0:
-                    self._give_back(slot, free)
 
     def submit(self, tifpath, tilepath, whole_image: bool = False) -> "_PendingImage":
         """Starts an image THIS process predicts alone and returns once its last batch is enqueued; ``.result()`` of the handle
@@ -1333,14 +1279,6 @@ class _PendingImage:
         return preds
 
 
-class _null_ctx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        return False
-
-
 def _ring_entries(sub: np.ndarray, x0: int, y0: int, score: float, cls: int, transform, tifpath, out: List[dict]) -> None:
     for contour in find_contours(sub):
         if contour.size < 8:
@@ -1380,16 +1318,6 @@ def polygons_from_masks(masks: np.ndarray, regions: np.ndarray, scores, classes,
         x0, y0, x1, y1 = (int(v) for v in regions[d])
         if x1 <= x0 or y1 <= y0:
             continue
-        sub = masks[d, y0:y1, x0:x1]        # the mask is zero outside its paste region
-        for contour in find_contours(sub):
-            if contour.size < 8:
-                continue
-            cx = (contour[:, 0] + x0).tolist()
-            cy = (contour[:, 1] + y0).tolist()
-            if (cx[0], cy[0]) != (cx[-1], cy[-1]):
-                cx.append(cx[0])
-                cy.append(cy[0])
-            gx, gy = xy(transform, rows=cy, cols=cx)
-            evaluations.append({"image_id": tifpath, "category_id": int(classes[d]), "score": float(scores[d]),
-                                "polygon_coords": [[[float(a), float(b)] for a, b in zip(gx, gy)]]})
+        # (the mask is zero outside its paste region)
+        _ring_entries(masks[d, y0:y1, x0:x1], x0, y0, float(scores[d]), int(classes[d]), transform, tifpath, evaluations)
     return evaluations
