@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+from treedetection_amd import _lib
 from treedetection_amd.geotiff import GeoTiff, write_geotiff
 from treedetection_amd.synth import make_tile
 from treedetection_amd.weights import make_synthetic_state_dict
@@ -81,6 +82,11 @@ def test_one_noise_tile_of_many_windows(tmp_path, subseq):
     check = _long_equals_host(path, subseq_bytes=subseq)
     assert check.long_segments == 1 and check.sync_stats[1] == -(-int(g._jpeg_plan()[1][0, 1]) // (64 * subseq))
     assert check.sync_stats[2] > 2 and check.sync_rounds > 1.0
+    # the tile is one complete stream of one segment: the wave counts what the host emulation of its 64 lanes counts (treedet.h)
+    src = np.array(g._mm[g._offs[0]:g._offs[0] + g._counts[0]], dtype=np.uint8)
+    out, shape, stats = np.zeros(512 * 512 * 3, dtype=np.uint8), np.zeros(3, dtype=np.int32), np.zeros(4, dtype=np.int64)
+    n = _lib.load().td_jpeg_decode_sync(src.ctypes.data, src.size, out.ctypes.data, out.size, shape.ctypes.data, subseq, 64, stats.ctypes.data)
+    assert n == out.size and list(check.sync_stats) == [int(v) for v in stats], (check.sync_stats, stats)
 
 
 def test_half_flat_half_noise(tmp_path):
