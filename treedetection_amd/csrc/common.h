@@ -146,7 +146,7 @@ inline constexpr ConvTile TD_CONV_TILES[] = {
     {TILE_IGEMM,   0, TILE_ANY, false, false, 15, 0,   0, 32},     // 31: 256x32, 4 x 1 waves (the thin heads)
     {TILE_IGEMM,   0, TILE_ANY, false, false, 17, 0,   0, 32},     // 32: 128x32
     {TILE_BS,      0, TILE_ANY, false, true,   0, 4, 128,  0},     // 33: conv_bs_kernel (its other tuning rules: conv_bs_ok)
-    {TILE_SPLIT,   0, TILE_F32, false, false, 21, 0,   0,  0},     // 34: conv_split_kernel 128x256 (ranks 21 - 24: timed for launches with w_split only,
+    {TILE_SPLIT,   0, TILE_F32, false, false, 21, 0,   0,  0},     // 34: conv_split_kernel 128x256, 1 x 4 waves of 128x64 (ranks 21 - 24: timed for launches with w_split only,
     {TILE_SPLIT,   1, TILE_F32, false, false, 22, 0,   0,  0},     // 35: 128x128               and then nothing else is — tuned_cfg filters by family)
     {TILE_SPLIT,   2, TILE_F32, false, false, 23, 0,   0,  0},     // 36: 64x256
     {TILE_SPLIT,   3, TILE_F32, false, false, 24, 0,   0,  0},     // 37: 64x128, 2 waves (the M = 5 000 layers: twice the blocks of 35)

@@ -24,18 +24,25 @@
 //     [piece][lane][8 bf16]; one wave instruction = one contiguous 1-KB read straight into the registers the MFMA takes, issued two
 //     slices (one k-chunk of MFMAs) ahead into three register sets of one slice each; no split work for them in the kernel. Plain
 //     loads: hipcc counts their waits itself; only the wait for the LDS-DMA rows is counted by hand (see the loop);
-//   * the waves tile M as well as N (WM x WN waves of 32 MT rows x 32 NT columns): a wave splits only the rows it multiplies.
-// Per k-chunk a wave of the 64 x 128 wave tile (MT 2, NT 4) issues 2 x 6 x 8 = 96 MFMAs (3 072 pipe cycles), reads 4 A fragments
+//   * WM x WN waves of 32 MT rows x 32 NT columns: a wave splits only the rows it multiplies, and loads only its columns' filters.
+// Per k-chunk a wave of the 64 x 128 wave tile (MT 2, NT 4: tile 36) issues 2 x 6 x 8 = 96 MFMAs (3 072 pipe cycles), reads 4 A fragments
 // of 2 x 16 B (ds_read_b128), splits 32 floats per lane (176 VALU instructions, ~700 cycles, in the shadow of the MFMAs) and loads
-// 24 filter fragments (24 KB; the two waves of a block column read the same ones, the second through the vector L1).
-// Registers of that tile: 128 accumulators (AGPRs) + 3 x 48 filter registers + 16 A + 2 x 24 pieces: 211 VGPRs + 128 AGPRs, one
+// 24 filter fragments (24 KB).
+// Registers of that tile: 128 accumulators (AGPRs) + 3 x 48 filter registers + 16 A + 2 x 24 pieces: 208 VGPRs + 128 AGPRs, one
 // wave per SIMD, no scratch; the 64 x 64 wave tile: 198 registers, two waves per SIMD. LDS: 3 x BM x 128 B of stages (49 152 B at
 // 128 rows), re-used by the epilogue's fp32 wave-row staging (64 x 260 x 4 B = 66 560 B for the 256-column tiles, 33 792 B for 64 x 128).
+// Tile 34 (128 x 256) is 1 x 4 waves of 128 x 64 (MT 4, NT 2) instead: the block's waves differ in columns only, so every filter fragment
+// is requested once per CU (12 per wave and k-chunk, not 24) and every wave splits all 128 rows (8 ds_read_b128, 288 - 352 VALU
+// instructions a k-chunk for the same 96 MFMAs). 188 VGPRs + 128 AGPRs, one wave per SIMD, one block per CU; LDS 133 120 B, all of it the
+// epilogue's 128 x 260 floats. Its step states the order of its instructions (PACED, below): that, not the bytes, is what it gains by —
+// the 2 x 2 form already shared the fragments through the vector L1 (profiles/f32_split_tall.txt: same L2 requests, 1 047 us on fc1;
+// this form 1 015 us as hipcc orders it, 857 us paced, the 64 x 256 tile 904 - 949 us).
 // Measured (profiles/f32_split.txt, batch 8): fc1 (8000 x 1024 x 12544) 1 549 -> 900 us = 228 TFLOP/s, fc2 137 -> 89 us. conv1 and the
 // shortcuts of res3 - res5 and the FPN laterals (8 - 64 k-chunks per block; profiles/f32_split_backbone.txt): 2.41 -> 1.95 ms in the layer
 // table, headline 697.6 -> 726.2 tiles/s: on by default with the box head (engine.cpp SPLIT_DEFAULT); conv3 ties on its fp32 tiles: off.
 #include "common.h"
 #include "conv_tiles.h"
+#include <utility>
 
 namespace {
 
@@ -45,6 +52,11 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int SPLIT_CHUNK_BYTES = 6144;      // one 32-column tile x one k-chunk of the split bank: 2 slices x 3 pieces x 1 KB
+
+template <int... R, class F>
+__device__ __forceinline__ void static_for(std::integer_sequence<int, R...>, F&& f) {
+    (f(std::integral_constant<int, R>{}), ...);
+}
 
 // 8 floats (two 16-B pieces of an LDS row) → three bf16x8 pieces, p[0] the leading one
 __device__ __forceinline__ void split8(const f32x4& lo, const f32x4& hi, bf16x8 (&p)[3]) {
@@ -127,6 +139,12 @@ __device__ __forceinline__ void conv_split_body(const ConvArgs& a, char* lds) {
         w_off[j] = nt < ntiles32 ? (unsigned)nt * (unsigned)nit * (unsigned)SPLIT_CHUNK_BYTES + (unsigned)lane * 16u : OOB;
     }
 
+    unsigned w_dead[NT], a_dead[AROWS];               // all ones where the offset is OOB (the paced step's requests)
+#pragma unroll
+    for (int j = 0; j < NT; ++j) w_dead[j] = w_off[j] == OOB ? ~0u : 0u;
+#pragma unroll
+    for (int i = 0; i < AROWS; ++i) a_dead[i] = a_off[i] == OOB ? ~0u : 0u;
+
     typedef __attribute__((address_space(3))) void lds_void;
     const unsigned wave_rows = (unsigned)__builtin_amdgcn_readfirstlane(wave) * 8u;
     // every issue runs whether or not its k-chunk exists (past the end: offset OOB, zeros): each step then puts the same number of
@@ -172,16 +190,19 @@ __device__ __forceinline__ void conv_split_body(const ConvArgs& a, char* lds) {
             split8(lo, up, pa[i]);
         }
     };
-    auto mma = [&](const bf16x8 (&pa)[MT][3], const f32x4 (&fb)[NT][3]) {
-        // the six products, smallest first; the (i, j) tiles inside: MT x NT independent MFMAs between dependent ones
+    // the six products, smallest first; the (i, j) tiles inside: MT x NT independent MFMAs between dependent ones. MFMA q of a slice
+    // (product q / (MT NT), tile q % (MT NT)); [q0, q1) for the tile that places its requests between the first ones
+    auto mma_range = [&](const bf16x8 (&pa)[MT][3], const f32x4 (&fb)[NT][3], auto q0_c, auto q1_c) {
         constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, QB[6] = {2, 0, 1, 1, 0, 0};
+        constexpr int Q0 = decltype(q0_c)::value, Q1 = decltype(q1_c)::value;
 #pragma unroll
-        for (int t = 0; t < 6; ++t)
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int j = 0; j < NT; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa[i][PA[t]], __builtin_bit_cast(bf16x8, fb[j][QB[t]]), acc[i][j], 0, 0, 0);
+        for (int q = Q0; q < Q1; ++q) {
+            const int t = q / (MT * NT), i = (q / NT) % MT, j = q % NT;
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa[i][PA[t]], __builtin_bit_cast(bf16x8, fb[j][QB[t]]), acc[i][j], 0, 0, 0);
+        }
+    };
+    auto mma = [&](const bf16x8 (&pa)[MT][3], const f32x4 (&fb)[NT][3]) {
+        mma_range(pa, fb, std::integral_constant<int, 0>{}, std::integral_constant<int, 6 * MT * NT>{});
     };
 
     // The pipeline runs slice by slice (g = 2 it + s), unrolled over three k-chunks so that every index below is a constant:
@@ -192,6 +213,13 @@ __device__ __forceinline__ void conv_split_body(const ConvArgs& a, char* lds) {
     // hipcc counts the waits for the filter registers itself (plain loads). The LDS-DMA rows it cannot see: step (it, 1) waits until
     // all but the A_YOUNGER newest operations have completed — the filter loads of three steps and the rows of chunk it + 2 are
     // younger than the rows of chunk it + 1 (requested last in step (it - 2, 1)).
+    // The tall wave tile (MT 4) splits twice the rows per MFMA (36 - 44 MT VALU instructions for 6 MT NT MFMAs of 8 passes a step) and
+    // has one wave per SIMD: what the wave issues outside an MFMA's 32 cycles, the pipe waits for. Left to itself hipcc issues the MFMAs
+    // in runs of 20 with the split behind them, and the step's requests (60 - 180 issue cycles each) ahead of all of them. So the order
+    // of a PACED step is stated: the fragment reads; one request behind each of the first MFMAs (fenced pairs: they also cover the LDS
+    // latency); then PACE_VALU instructions of the split behind every other MFMA. Nothing crosses the end of a step.
+    constexpr bool PACED = MT == 4;
+    constexpr int PACE_VALU = 4;
     constexpr int A_YOUNGER = 3 * NT * 3 + AROWS;
     static_assert(A_YOUNGER < 64, "vmcnt immediate");
     f32x4 fb[3][NT][3];
@@ -211,12 +239,59 @@ __device__ __forceinline__ void conv_split_body(const ConvArgs& a, char* lds) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
         }
-        load_b(fb[(G + 2) % 3], it + 1, S);      // slice g + 2 = the same slice of the next chunk
-        if constexpr (S == 1) stage_a(C, it + 3);
-        __builtin_amdgcn_sched_barrier(0);            // the requests go out first (hipcc otherwise sinks them below the MFMAs)
-        if constexpr (S == 0) split_a(C, 1, pa[1]);
-        else split_a((C + 1) % 3, 0, pa[0]);
-        mma(pa[S], fb[G % 3]);
+        if constexpr (!PACED) {
+            load_b(fb[(G + 2) % 3], it + 1, S);      // slice g + 2 = the same slice of the next chunk
+            if constexpr (S == 1) stage_a(C, it + 3);
+            __builtin_amdgcn_sched_barrier(0);            // the requests go out first (hipcc otherwise sinks them below the MFMAs)
+            if constexpr (S == 0) split_a(C, 1, pa[1]);
+            else split_a((C + 1) % 3, 0, pa[0]);
+            mma(pa[S], fb[G % 3]);
+        } else {
+            constexpr int REQS = 3 * NT + (S == 1 ? AROWS : 0), NMMA = 6 * MT * NT;
+            static_assert(REQS < NMMA && PACE_VALU * (NMMA - REQS) >= 36 * MT, "the paced step has a gap for every request and for the split");
+            const char* Ab = &As[(S == 0 ? C : (C + 1) % 3) * BM * CHUNK_BYTES];      // the slice split_a would read in this step
+            f32x4 raw[MT][2];
+#pragma unroll
+            for (int i = 0; i < MT; ++i)
+#pragma unroll
+                for (int h = 0; h < 2; ++h) raw[i][h] = *reinterpret_cast<const f32x4*>(Ab + i * 32 * CHUNK_BYTES + frag_off[2 * (1 - S) + h]);
+            __builtin_amdgcn_sched_barrier(0);
+            f32x4 (&fn)[NT][3] = fb[(G + 2) % 3];          // slice g + 2 = the same slice of the next chunk
+            static_for(std::make_integer_sequence<int, REQS>{}, [&](auto r_c) {
+                constexpr int R = decltype(r_c)::value;
+                mma_range(pa[S], fb[G % 3], std::integral_constant<int, R>{}, std::integral_constant<int, R + 1>{});
+                if constexpr (R < 3 * NT) {
+                    constexpr int j = R / 3, q = R % 3;
+                    const unsigned dead = w_dead[j] | (it + 1 >= nit ? ~0u : 0u);      // bit arithmetic, not `?:`: inside the fences hipcc branches on it
+                    const unsigned off = ((w_off[j] + (unsigned)(it + 1) * (unsigned)SPLIT_CHUNK_BYTES + (unsigned)(3 * S + q) * 1024u) & ~dead) | (OOB & dead);
+                    fn[j][q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, off, 0, 0));
+                } else {
+                    constexpr int i = R - 3 * NT;
+                    const unsigned dead = a_dead[i] | (it + 3 >= nit ? ~0u : 0u);
+                    const unsigned off = ((a_off[i] + (unsigned)(it + 3) * CHUNK_BYTES) & ~dead) | (OOB & dead);
+                    char* dst = As + ((unsigned)C * BM + (unsigned)LDROWS * i + wave_rows) * CHUNK_BYTES;
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(xrsrc, (lds_void*)dst, 16, off, 0, 0, 0);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            });
+            mma_range(pa[S], fb[G % 3], std::integral_constant<int, REQS>{}, std::integral_constant<int, NMMA>{});
+#pragma unroll
+            for (int i = 0; i < MT; ++i) {
+                split8(raw[i][0], raw[i][1], pa[1 - S][i]);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {             // the pieces are finished inside this step (hipcc otherwise sinks the split to their use)
+                    u32x4 pin = __builtin_bit_cast(u32x4, pa[1 - S][i][k]);
+                    asm volatile("" : "+v"(pin));
+                    pa[1 - S][i][k] = __builtin_bit_cast(bf16x8, pin);
+                }
+            }
+#pragma unroll
+            for (int g = REQS; g < NMMA; ++g) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);             // MFMA
+                __builtin_amdgcn_sched_group_barrier(0x002, PACE_VALU, 0);     // VALU
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
     };
     for (int it = 0; it < nit; it += 3) {
         step(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, it);
@@ -242,7 +317,8 @@ void conv_split_kernel(const ConvArgs a) {
     constexpr int STAGE_BYTES = 3 * 32 * MT * WM * CHUNK_BYTES;
     constexpr int EPI_BYTES = conv_epilogue_lds_bytes<float, MT, NT, WM, WN, 1>();
     constexpr int LDS_BYTES = STAGE_BYTES > EPI_BYTES ? STAGE_BYTES : EPI_BYTES;
-    static_assert(LDS_BYTES <= 80 * 1024, "two blocks per CU must fit the LDS");
+    constexpr int BLOCKS_PER_CU = 4 * WPE / (WM * WN) > 0 ? 4 * WPE / (WM * WN) : 1;      // by registers: WPE waves on each of the four SIMDs
+    static_assert(LDS_BYTES * BLOCKS_PER_CU <= 160 * 1024, "the blocks the registers allow on a CU must fit its LDS");
     __shared__ __attribute__((aligned(16))) char lds[LDS_BYTES];
     conv_split_body<MT, NT, WM, WN>(a, lds);
 }
@@ -302,6 +378,6 @@ td_status conv_split_launch(const ConvArgs& a, int variant, hipStream_t stream) 
         case 3: return launch_split<2, 2, 1, 2, 2>(a, stream);     // 64 x 128: 1 x 2 waves of 64 x 64 (M = 5 000 with N <= 512: 158 - 316 blocks, not 80 - 160)
         case 2: return launch_split<2, 4, 1, 2, 1>(a, stream);     // 64 x 256: 1 x 2 waves of 64 x 128 (row counts that leave the 128-row grid short)
         case 1: return launch_split<2, 2, 2, 2, 2>(a, stream);     // 128 x 128: 2 x 2 waves of 64 x 64, two blocks per CU
-        default: return launch_split<2, 4, 2, 2, 1>(a, stream);    // 128 x 256: 2 x 2 waves of 64 x 128, one wave per SIMD
+        default: return launch_split<4, 2, 1, 4, 1>(a, stream);    // 128 x 256: 1 x 4 waves of 128 x 64, one wave per SIMD, one block per CU (every filter fragment read once per CU)
     }
 }
