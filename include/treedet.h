@@ -625,6 +625,34 @@ td_status td_region_relate_dev(const double* ring_xy, const int64_t* ring_start,
 td_status td_crown_stats(const float* raster, int rows, int cols, const double* transform, const int32_t* window,
                          const float* circles, int n, int mode, float radius_scale, float* out, void* stream);
 
+/* Zonal statistics: the same per-crown statistics over the pixels inside the crown's OUTLINE instead of its bounding circle
+ * (config crown_statistics: polygon; csrc/crown_zonal.h is the rule, shared by both functions). raster: float32 [rows][cols], the
+ * whole raster, fewer than 2^31 pixels; transform: HOST (a,b,c,d,e,f), finite. Rings arrive open (without the repeated closing
+ * vertex), concatenated, as for td_ring_pairs_area: xy = n_xy (x, y) pairs, start int64 [n + 1] with crown q in
+ * [start[q], start[q + 1]). Exterior rings only, either winding.
+ * Pixel (row, col) has the centre P.x = (a*(col+0.5) + b*(row+0.5)) + c, P.y = (d*(col+0.5) + e*(row+0.5)) + f in float64, every
+ * operation rounded on its own, and belongs to the crown iff P lies inside the closed ring or on it: even-odd over all edges (a
+ * ring that crosses itself is not an error), half-open in y, every sign exact (csrc/geom_predicates.h).
+ * Out, per crown: out float32 [n][4] = min, max, mean, population variance of the pixels inside (float64 sums, the variance in a
+ * second pass about the float64 mean, each rounded once); pos int32 [n][3] = their count, raster row and column of the maximum.
+ * A NaN inside makes min, max, mean and variance NaN and the position that of the FIRST NaN in row-major order; among numbers the
+ * first occurrence of the maximum is reported and the minimum carries the sign of the first of equal zeros (numpy's order, as
+ * td_crown_stats).
+ * status int32 [n]: 0 computed — a crown with no pixel centre inside has count 0, out -1 in all four fields, both positions -1.
+ * 1 (device only): more than TD_ZONAL_RING_CAP vertices, the wave's LDS region — not computed (out NaN, pos -1); td_crown_zonal
+ * computes such a crown. 2 refused (out NaN, pos -1): fewer than 3 vertices, a non-finite coordinate, start[q] < 0,
+ * start[q + 1] < start[q] or start[q + 1] > n_xy (checked in the kernel before any vertex is read).
+ * td_crown_zonal_dev: raster, xy, start, out, pos, status are DEVICE memory, xy 16-byte aligned; one wave per crown, a bounded grid
+ * with a grid-stride loop (any n is one launch); asynchronous on `stream`. td_crown_zonal: HOST memory, host code, no vertex cap;
+ * status, count, min, max and position equal the device's bit for bit, mean and variance are sums in another order. Both return
+ * TD_ERR_INVALID (with a message, before anything runs) for a null pointer, n < 0 or n_xy < 0, rows or cols < 1 or 2^31 pixels and
+ * more, a non-finite transform or a misaligned xy; n = 0 returns TD_OK and launches nothing. */
+#define TD_ZONAL_RING_CAP 512    /* vertices of an open ring the kernel holds */
+td_status td_crown_zonal_dev(const float* raster, int rows, int cols, const double* transform, const double* xy, int64_t n_xy,
+                             const int64_t* start, int n, float* out, int32_t* pos, int32_t* status, void* stream);
+td_status td_crown_zonal(const float* raster, int rows, int cols, const double* transform, const double* xy, int64_t n_xy,
+                         const int64_t* start, int n, float* out, int32_t* pos, int32_t* status);
+
 /* GDAL's separable triangle-filter resampling (src.read(out_shape=..., resampling=bilinear), reference postprocessing.py:781-797)
  * of a raster that lies in device memory, with the NDVI rule of helpers.ndvi_array_from_rgbi (880-895) fused into the second pass.
  * src: DEVICE uint8 [height][width][c] pixel-interleaved (TD_SAMPLE_U8, c <= 4) or DEVICE float32 [height][width] (TD_SAMPLE_F32,

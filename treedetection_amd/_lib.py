@@ -28,6 +28,7 @@ ZSTD_STATS = ("frames block_raw block_rle block_comp max_blocks_per_frame lit_ra
 RING_PAIR_CAP, RING_PAIR_WPB, RING_PAIR_GRID = 1024, 4, 2048   # ringiou.hip: vertices of a pair in LDS, waves per workgroup, workgroups per launch
 # TD_RELATE_*_CAP (regionrelate.hip): points of a query ring, meeting parameters of one query edge, distinct region rings a query meets
 RELATE_QUERY_CAP, RELATE_MEET_CAP, RELATE_RING_CAP = 256, 254, 64
+ZONAL_RING_CAP = 512   # TD_ZONAL_RING_CAP (crownzonal.hip): vertices of an open crown ring the kernel holds
 
 
 class TdError(RuntimeError):
@@ -104,6 +105,10 @@ SIGNATURES = {
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "td_crown_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_void_p, C.c_int,
                                  C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    "td_crown_zonal_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p, C.c_int64, C.c_void_p, C.c_int,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "td_crown_zonal": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p, C.c_int64, C.c_void_p, C.c_int,
+                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "td_resample_gdal_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int]
                              + [C.c_void_p] * 4 + [C.c_int, C.c_int64] + [C.c_void_p] * 4 + [C.c_int, C.c_int64]
                              + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),

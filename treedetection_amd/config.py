@@ -20,7 +20,10 @@ the reference's ``clean_crowns`` — treedetection_amd.cleaning; false: not one 
 false, default false: the seam strips of ``use_overlap`` between LZW / DEFLATE / ZSTD rasters are cut on the GPU from only the blocks
 they touch — treedetection_amd.merging; same files), ``device_outlines`` (true | false, default false: ``fuse_predictions`` and
 ``exclude_outlines`` relate the crowns to the forest / exclusion outlines on the GPU, a wave per crown — treedetection_amd.fusion,
-Region.relate(device=...); false: not one byte of any output changes; the tile flags of preprocessing stay on the host).
+Region.relate(device=...); false: not one byte of any output changes; the tile flags of preprocessing stay on the host),
+``crown_statistics`` ("circle" | "polygon", default "circle": the reference's statistics inside each crown's bounding circle;
+"polygon": TreeHeight and the NDVI mean / variance from the pixels whose centres lie inside the crown's outline, a wave per crown —
+postprocessing.crown_zonal_stats; "circle": not one byte of any output changes).
 """
 from __future__ import annotations
 
@@ -173,7 +176,7 @@ def get_config(config_path: str):
         "precision": "fp32", "resnet_depth": 101, "sharded_epilogue": "auto", "shard_by": "auto", "eager_stitch": True,
         "fp16_min_batch": 0, "device_contours": "auto", "device_decode": "auto", "device_filters": "auto",
         "device_decode_long_jpeg": False, "device_decode_planar": False, "clean_crowns": False, "device_seams": False,
-        "device_outlines": False,
+        "device_outlines": False, "crown_statistics": "circle",
     }
     for k, v in defaults.items():
         config[k] = config.get(k, v)

@@ -5,8 +5,10 @@ layers — the only consumer of the nDSM side band.
 
 What runs where: the per-crown raster statistics — in the reference a cupy test of every crown against EVERY pixel —
 are one launch of ``td_crown_stats`` per raster (libtreedet_hip.so; a workgroup per crown over its circle's bounding
-box, same membership arithmetic); the N x N box filters and the selection rules are small host numpy, written to follow
-the reference line by line *including* its quirks, which are listed in DESIGN.md §7 and marked ``# ref:`` below; with
+box, same membership arithmetic; with ``crown_statistics: polygon`` instead one launch of ``td_crown_zonal_dev`` per raster over the
+pixels inside each crown's OUTLINE, a wave per crown — :func:`crown_zonal_stats`; off by default: same files); the N x N box
+filters and the selection rules are small host numpy, written to follow the reference line by line *including* its quirks,
+which are listed in DESIGN.md §7 and marked ``# ref:`` below; with
 ``device_filters: true`` the pair tests of the two box filters run on the GPU and only the sparse result comes back
 (``td_crown_pairs_count`` / ``td_crown_pairs_fill``, crownpairs.hip; same arithmetic, same results); with ``clean_crowns: true`` the
 layer is first thinned by the IoU of the crown OUTLINES (:mod:`treedetection_amd.cleaning`; off by default: same files).
@@ -240,6 +242,84 @@ def crown_stats(raster, transform, bounds, circles: np.ndarray, mode: int, radiu
         _lib.check(lib.td_crown_stats(d_r.data_ptr(), rows, cols, tr, win, d_c.data_ptr(), n, mode, float(radius_scale),
                                       d_o.data_ptr(), _lib.stream_ptr()), "td_crown_stats")
     return d_o.cpu().numpy()
+
+
+# ---- zonal statistics over the crown outlines (opt-in: ``crown_statistics: polygon``) ------------------------------------------
+def crown_statistics_setting(value="circle") -> str:
+    """The ``crown_statistics`` config key: "circle" (default, also for None: the reference's bounding circles, td_crown_stats) or
+    "polygon" (the pixels whose centres lie inside the crown's outline, td_crown_zonal_dev). Anything else is refused."""
+    value = "circle" if value is None else value
+    if not isinstance(value, str) or value not in ("circle", "polygon"):
+        raise ValueError(f"crown_statistics must be 'circle' or 'polygon', got {value!r}")
+    return value
+
+
+def _zonal_raster_check(raster) -> None:
+    if isinstance(raster, torch.Tensor) and not (raster.is_cuda and raster.dtype == torch.float32 and raster.dim() == 2 and raster.is_contiguous()):
+        raise ValueError(f"crown_zonal_stats: a raster tensor must be a contiguous float32 CUDA tensor [rows, cols], got {raster.dtype} "
+                         f"{tuple(raster.shape)} on {raster.device}")
+
+
+def _zonal_host(raster: np.ndarray, transform, xy: np.ndarray, start: np.ndarray):
+    """td_crown_zonal on host arrays → (out float32 [n, 4], pos int32 [n, 3], status int32 [n])."""
+    import ctypes as C
+    n = start.size - 1
+    out, pos, status = np.empty((n, 4), np.float32), np.empty((n, 3), np.int32), np.empty(n, np.int32)
+    r = np.ascontiguousarray(raster, dtype=np.float32)
+    pts = xy if xy.size else np.zeros((1, 2))                # (an empty vertex array still needs a pointer the library accepts)
+    tr = (C.c_double * 6)(*[float(v) for v in transform[:6]])
+    _lib.check(_lib.load().td_crown_zonal(r.ctypes.data, r.shape[0], r.shape[1], tr, pts.ctypes.data, xy.shape[0], start.ctypes.data, n,
+                                          out.ctypes.data, pos.ctypes.data, status.ctypes.data), "td_crown_zonal")
+    return out, pos, status
+
+
+def upload_rings(xy: np.ndarray, start: np.ndarray, dev):
+    """Packed rings (cleaning.pack_rings) as the two device tensors td_crown_zonal_dev reads: upload once, pass to every launch."""
+    return (torch.from_numpy(xy if xy.size else np.zeros((1, 2))).to(dev), torch.from_numpy(start).to(dev))
+
+
+def crown_zonal_stats(raster, transform, rings, device: Optional[int] = 0, packed=None, uploaded=None):
+    """Zonal statistics of one raster over crown outlines → (stats float32 [n, 4] = min, max, mean, population variance; count
+    int32 [n]; max_pos int32 [n, 2] = raster row, column of the maximum; status int32 [n]). A pixel belongs to a crown when its
+    centre lies inside the closed ring or on it (include/treedet.h, td_crown_zonal). ``raster``: a numpy array [rows, cols]
+    (copied to ``device``), or a contiguous float32 CUDA tensor, which the kernel reads where it lies. ``rings``: [m, 2] vertex
+    arrays, closed or open, either winding. ``device``: a GPU index (td_crown_zonal_dev, a wave per crown) or None (td_crown_zonal
+    on the host: the same status, count, min, max and position). Crowns the kernel leaves out (status 1: more than
+    ``_lib.ZONAL_RING_CAP`` vertices) are decided by the host function alone and merged, status included. Refused crowns
+    (status 2: fewer than 3 vertices, a non-finite coordinate) come back as NaN / -1. ``packed`` = cleaning.pack_rings(rings) and
+    ``uploaded`` = upload_rings(*packed, dev), when the caller has them already (two rasters, one ring set)."""
+    from .cleaning import pack_rings
+    import ctypes as C
+
+    _zonal_raster_check(raster)
+    xy, start = packed if packed is not None else pack_rings(rings)
+    n = start.size - 1
+    if n == 0:
+        return np.zeros((0, 4), np.float32), np.zeros(0, np.int32), np.zeros((0, 2), np.int32), np.zeros(0, np.int32)
+    on_device = isinstance(raster, torch.Tensor)
+    if device is None:
+        out, pos, status = _zonal_host(raster.cpu().numpy() if on_device else raster, transform, xy, start)
+        return out, pos[:, 0].copy(), pos[:, 1:].copy(), status
+    rows, cols = raster.shape
+    dev = raster.device if on_device else torch.device("cuda", device)
+    with torch.cuda.device(dev):
+        d_r = raster if on_device else torch.from_numpy(np.ascontiguousarray(raster, dtype=np.float32)).to(dev)
+        d_xy, d_start = uploaded if uploaded is not None else upload_rings(xy, start, dev)
+        d_o = torch.empty((n, 4), dtype=torch.float32, device=dev)
+        d_p = torch.empty((n, 3), dtype=torch.int32, device=dev)
+        d_s = torch.empty(n, dtype=torch.int32, device=dev)
+        tr = (C.c_double * 6)(*[float(v) for v in transform[:6]])
+        _lib.check(_lib.load().td_crown_zonal_dev(d_r.data_ptr(), rows, cols, tr, d_xy.data_ptr(), xy.shape[0], d_start.data_ptr(), n,
+                                                  d_o.data_ptr(), d_p.data_ptr(), d_s.data_ptr(), _lib.stream_ptr()), "td_crown_zonal_dev")
+        out, pos, status = d_o.cpu().numpy(), d_p.cpu().numpy(), d_s.cpu().numpy()
+    capped = np.flatnonzero(status == 1)
+    if capped.size:                                          # the host function decides these crowns alone
+        sub = [xy[start[k]:start[k + 1]] for k in capped]
+        sub_start = np.zeros(capped.size + 1, np.int64)
+        np.cumsum([r.shape[0] for r in sub], out=sub_start[1:])
+        h_raster = raster.cpu().numpy() if on_device else raster
+        out[capped], pos[capped], status[capped] = _zonal_host(h_raster, transform, np.ascontiguousarray(np.concatenate(sub)), sub_start)
+    return out, pos[:, 0].copy(), pos[:, 1:].copy(), status
 
 
 # ---- box filters (host numpy, the reference's dtypes) -------------------------------------------------------
@@ -529,6 +609,7 @@ def process_layer(rings: List[np.ndarray], scores: Sequence[Optional[float]], co
     """process_geojson + process_features (postprocessing.py:722-808, 478-720) for the crowns of one image → the list
     of output features ``{"ring": [m,2], "properties": {...}}`` in the reference's order (duplicates included)."""
     device_filters = _device_filters_on(config)
+    zonal = crown_statistics_setting(config.get("crown_statistics", "circle")) == "polygon"
     conf_thr, iou_thr, area_thr = _cfg(config, "confidence_threshold"), _cfg(config, "iou_threshold"), _cfg(config, "area_threshold")
     h_scale, n_scale = float(_cfg(config, "height_scaling_factor")), float(_cfg(config, "ndvi_scaling_factor"))
     # 1-2: confidence filter, ids, areas of the simplify(2) polygons
@@ -576,15 +657,23 @@ def process_layer(rings: List[np.ndarray], scores: Sequence[Optional[float]], co
     if not features:
         return []
     # 4: statistics
-    circles = crown_circles([f["ring"] for f in features])
-    same_grid = all(abs(a - b) < 1e-5 for a, b in zip(h_t[:6], n_t[:6])) and all(abs(a - b) < 1e-3 for a, b in zip(h_b, n_b))
-    if same_grid:     # get_metadata_within_polygon: NDVI in half the radius, both on the NDVI transform / bounds
-        hs = crown_stats(height, n_t, n_b, circles, 0, 1.0, device, clamp_shape=height.shape)
-        ns = crown_stats(ndvi, n_t, n_b, circles, 1, 0.5, device, clamp_shape=height.shape)
+    if zonal:         # crown_statistics: polygon — the pixels inside each outline, every raster on its own transform, no half radius
+        from .cleaning import pack_rings
+        packed = pack_rings([f["ring"] for f in features])
+        uploaded = upload_rings(*packed, torch.device("cuda", device))       # one upload for both launches
+        hz = crown_zonal_stats(height, h_t, None, device, packed, uploaded)[0]
+        nz = crown_zonal_stats(ndvi, n_t, None, device, packed, uploaded)[0]
+        heights, mean_ndvi, var_ndvi = hz[:, 1], nz[:, 2], nz[:, 3]
     else:
-        hs = crown_stats(height, h_t, h_b, circles, 0, 1.0, device)
-        ns = crown_stats(ndvi, n_t, n_b, circles, 1, 1.0, device)
-    heights, mean_ndvi, var_ndvi = hs[:, 0], ns[:, 2], ns[:, 3]
+        circles = crown_circles([f["ring"] for f in features])
+        same_grid = all(abs(a - b) < 1e-5 for a, b in zip(h_t[:6], n_t[:6])) and all(abs(a - b) < 1e-3 for a, b in zip(h_b, n_b))
+        if same_grid:     # get_metadata_within_polygon: NDVI in half the radius, both on the NDVI transform / bounds
+            hs = crown_stats(height, n_t, n_b, circles, 0, 1.0, device, clamp_shape=height.shape)
+            ns = crown_stats(ndvi, n_t, n_b, circles, 1, 0.5, device, clamp_shape=height.shape)
+        else:
+            hs = crown_stats(height, h_t, h_b, circles, 0, 1.0, device)
+            ns = crown_stats(ndvi, n_t, n_b, circles, 1, 1.0, device)
+        heights, mean_ndvi, var_ndvi = hs[:, 0], ns[:, 2], ns[:, 3]
     centroids = [(np.float32(f["ring"][:, 0].astype(np.float32).astype(np.float64).mean()),
                   np.float32(f["ring"][:, 1].astype(np.float32).astype(np.float64).mean())) for f in features]
     # preselection: image-border / overlap rules, height and NDVI thresholds
@@ -662,6 +751,7 @@ def process_single_file(file_path, processed_file_path, height_data_path, rgbi_d
     (printed, like the reference)."""
     from .cleaning import clean_crowns, clean_crowns_setting
     thin = clean_crowns_setting((config or {}).get("clean_crowns", False))      # (a bad value is refused, not printed)
+    crown_statistics_setting((config or {}).get("crown_statistics", "circle"))  # (likewise)
     try:
         layer = read_layer(file_path)
         scores = layer.columns.get("Confidence_score", [None] * len(layer))
@@ -695,6 +785,8 @@ def load_recovery_data_with_params(directory, config, logger=None):
     processed = set()
     params = {k: (_cfg(config, k) if k in DEFAULTS else config.get(k)) for k in _PARAM_KEYS}
     params = {k: (v if not (isinstance(v, float) and math.isinf(v)) else str(v)) for k, v in params.items()}
+    if crown_statistics_setting(config.get("crown_statistics", "circle")) == "polygon":      # (only then: "circle" files stay valid)
+        params["crown_statistics"] = "polygon"
     if os.path.exists(recovery_file):
         try:
             with open(recovery_file) as f:
