@@ -113,19 +113,27 @@ td_status td_engine_forward(td_engine* e, const void* images, int input_format, 
 #define TD_PHASE_STEM 6
 td_status td_engine_forward_phase(td_engine* e, int phase, const void* images, int input_format, const int32_t* hw_valid,
                                   const int32_t* hw_out, int B, int Hp, int Wp, void* stream, td_detections* out);
-/* Expose an internal activation of the last forward() for stage-wise parity tests: names
- * "stem","pool","res2".."res5","p2".."p6","rpn_logits","rpn_deltas","proposals","proposal_scores",
- * "proposal_count","pooled7","cls_logits","box_deltas","det_boxes_net","pooled14","mask_logits"; of the proposal
- * stage also "rpn_head2".."rpn_head6" ([B,h,w,15] float32 in both precisions: 3 logits, then 12 deltas per position),
- * "rpn_cand_idx","rpn_cand_scores","rpn_cand_valid","rpn_cand_boxes" ([B,5,1024(,4)]), "rpn_keep" ([B,5,1024]) and
- * "rpn_keep_count" ([B,5]). The "rpn_head*" pointers may be overwritten between phase 0 and phase 1 of
- * td_engine_forward_phase (after phase 0 has completed on its stream): stage tests feed crafted heads that way.
- * Of the detection stage: "box_pred" ([B*P,6] float32 in both precisions: two logits, foreground first, then four
- * deltas), "det_all_boxes" / "det_all_scores" / "det_flags" ([B,P(,4)], flags int32), "det_sorted_boxes" /
- * "det_sorted_scores" ([B,P(,4)]: the flagged rows by score descending, index ascending) with "det_sorted_count" ([B]
- * int32), "det_keep" ([B,D] int32 positions in the sorted list) with "det_keep_count" ([B] int32), "det_boxes_net";
- * of the mask tail: "mask_deconv" ([B*D,28,28,C], float16 in the fp16 engine), "mask_logits" and
- * "mask_probs_compact" ([B*D,28,28] float32; the first total = sum of counts rows are live). The same way,
+/* Expose an internal buffer of the last forward() for stage-wise parity tests. The names, extents and element types are the
+ * public rows of the engine's workspace plan (csrc/workspace.cpp; td_workspace_plan below lists them for any shape). B, Hp, Wp are
+ * those of the batch in hand, h x w a pyramid level's map (Hp >> 2 .. Hp >> 5; p6 = (p5 - 1) / 2 + 1), P = post_nms_topk,
+ * D = detections_per_image, C the model's widths; "act" = float16 in the fp16 engine, else float32. A name exists once its phase
+ * of td_engine_forward_phase has run in this forward, and until the next phase 0 or a td_engine_reserve that grows the workspace.
+ *   stem pre-phase or phase 0: "stem" [B,Hp/2,Wp/2,C] act, "pool" [B,Hp/4,Wp/4,C] act
+ *   phase 0: "res2".."res5" [B,h,w,C] act, "p2".."p6" [B,h,w,C] act, "rpn_head2".."rpn_head6" [B,h,w,15] float32 in both
+ *            precisions (3 logits, then 12 deltas per position)
+ *   phase 1: "rpn_cand_boxes" [B,5,1024,4] float32, "rpn_cand_scores" [B,5,1024] float32, "rpn_cand_valid" / "rpn_cand_idx" /
+ *            "rpn_keep" [B,5,1024] int32, "rpn_keep_count" [B,5] int32, "proposals" [B,P,4] float32, "proposal_scores" [B,P]
+ *            float32, "proposal_count" [B] int32, "pooled7" [B*P,7,7,C] act
+ *   phase 2: "box_pred" [B*P,6] float32 in both precisions (two logits, foreground first, then four deltas)
+ *   phase 3: "det_all_boxes" [B,P,4] / "det_all_scores" [B,P] float32, "det_flags" [B,P] int32, "det_sorted_boxes" [B,P,4] /
+ *            "det_sorted_scores" [B,P] float32 (the flagged rows by score descending, index ascending) with "det_sorted_count" [B]
+ *            int32, "det_keep" [B,D] int32 (positions in the sorted list) with "det_keep_count" [B] int32, "det_boxes_net" [B,D,4]
+ *            float32, "pooled14" [B*D,14,14,C] act
+ *   phase 4: "mask_total_rows" [1] int32 (the device row count the mask head reads), "mask_fcn3" / "mask_fcn4" [B*D,14,14,C] act,
+ *            "mask_deconv" [B*D,28,28,C] act
+ *   phase 5: "mask_logits" / "mask_probs_compact" [B*D,28,28] float32 (the first total = sum of counts rows are live)
+ * The "rpn_head*" pointers may be overwritten between phase 0 and phase 1 of
+ * td_engine_forward_phase (after phase 0 has completed on its stream): stage tests feed crafted heads that way. The same way,
  * "proposals", "proposal_count" (int32, every entry within [0, P]) and "box_pred" may be overwritten between phase 2
  * and phase 3, and "mask_deconv" between phase 4 and phase 5, each after the earlier phase has completed on its
  * stream: the later phases then run on the crafted values. No other buffer may be written.
@@ -278,6 +286,23 @@ td_status td_conv2d_winograd_head_nhwc(const float* x, const float* w, const flo
  *               (TD_TUNE_CACHE lines: cout, cin, kh*16+kw, rows, flags), tiles per F(2x2) slab, images per fold group */
 td_status td_conv_path(const int32_t* rules, int64_t wino_elems, const int32_t* layer, const int32_t* call, const int32_t* head,
                        int32_t* out);
+/* Diagnostic (tests; host only, needs no engine and no GPU): the workspace plan of an engine — every device buffer td_engine_reserve
+ * would allocate for (B, Hp, Wp), one row each, from the table the engine itself walks (csrc/workspace.cpp). widths[16] = what the
+ * loader reads off the weights: stem channels; cout of conv1, of conv2 and of conv3 in the first block of res2 .. res5 (4 + 4 + 4);
+ * FPN channels; box-head FC width; mask deconv output channels. winograd: the TD_WINOGRAD switch (fp32 engine: 1 by default).
+ * Fills min(cap, *n_rows) rows; TD_ERR_CAPACITY when cap is short (*n_rows still says how many there are). */
+typedef struct td_workspace_row {
+    char name[32];         /* the engine's buffer; "res[2]" for a member of an indexed family */
+    char public_name[32];  /* td_engine_tensor's name for it, or "" */
+    int32_t kind;          /* 0 activation (engine precision), 1 float32, 2 int32, 3 uint32, 4 uint64 */
+    int32_t elem_size;     /* bytes */
+    int32_t phase;         /* the public name exists after this phase (6: after the stem pre-phase or phase 0); -1 without one */
+    int32_t pad_;
+    int64_t dims[4];       /* extents at (B, Hp, Wp), 0-padded: what td_engine_tensor reports after a forward of that shape */
+    int64_t alloc_bytes;   /* size of the allocation */
+} td_workspace_row;
+td_status td_workspace_plan(int precision, int winograd, int post_nms_topk, int detections_per_image, const int32_t* widths, int B,
+                            int Hp, int Wp, td_workspace_row* rows, int cap, int* n_rows);
 /* Greedy NMS of n boxes (dev [n,4], scores dev [n]); keep_idx dev int32 [n] receives the kept
  * indices in descending-score order (ties: lower index first), *keep_count (dev) their number. */
 td_status td_nms(const float* boxes, const float* scores, int n, float iou_thresh, int32_t* keep_idx,

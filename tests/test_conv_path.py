@@ -20,6 +20,13 @@ def reserve_elems(B):
     return 16 * need
 
 
+def test_reserve_elems_is_the_plans_winograd_allocation():
+    """The restatement above against the engine's own workspace plan (td_workspace_plan): B = 8 at 800 x 800, R50 widths."""
+    mid = [64, 128, 256, 512]
+    rows = _lib.workspace_plan(FP32, 1, 1000, D, [64] + mid + mid + [4 * m for m in mid] + [256, 1024, 256], 8, 800, 800)
+    assert {r["name"]: r["alloc_bytes"] for r in rows}["wino_v"] == 4 * reserve_elems(8)
+
+
 def layer(cout, cin, k, scale=0, out_f32=0, banks=""):
     """banks: "2" F(2x2) filters, "4" F(4x4) filters, "s" split-bf16 (what the loader gives the layer under the default rules)"""
     return [cout, cin, k, k, scale, out_f32, "2" in banks, "4" in banks, "s" in banks]

@@ -53,6 +53,12 @@ class SeamSource(C.Structure):
                 ("own", C.c_double)]
 
 
+class WorkspaceRow(C.Structure):
+    """td_workspace_row: one buffer of td_workspace_plan."""
+    _fields_ = [("name", C.c_char * 32), ("public_name", C.c_char * 32), ("kind", C.c_int32), ("elem_size", C.c_int32),
+                ("phase", C.c_int32), ("pad_", C.c_int32), ("dims", C.c_int64 * 4), ("alloc_bytes", C.c_int64)]
+
+
 class Detections(C.Structure):
     _fields_ = [("boxes", C.c_void_p), ("scores", C.c_void_p), ("classes", C.c_void_p), ("count", C.c_void_p),
                 ("mask_probs", C.c_void_p), ("mask_region", C.c_void_p), ("mask_offset", C.c_void_p),
@@ -96,6 +102,7 @@ SIGNATURES = {
     "td_conv2d_winograd_nhwc": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 6 + [C.c_void_p]),
     "td_conv_path": (C.c_int, [C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                C.POINTER(C.c_int32)]),
+    "td_workspace_plan": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_int32)] + [C.c_int] * 3 + [C.POINTER(WorkspaceRow), C.c_int, C.POINTER(C.c_int)]),
     "td_nms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "td_roi_align": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_int,
                                C.c_void_p, C.c_int, C.c_void_p]),
@@ -238,6 +245,20 @@ def conv_path(rules, wino_elems, layer, call, head=None) -> dict:
           "td_conv_path")
     return {"form": CONV_FORMS[out[0]], "head": CONV_HEADS[out[1]], "key": tuple(out[3:8]) if out[2] else None,
             "slab_tiles": out[8], "fold_group": out[9]}
+
+
+WORKSPACE_KINDS = ("act", "f32", "i32", "u32", "u64")   # WsKind (csrc/workspace.h), in order
+
+
+def workspace_plan(precision, winograd, post_nms_topk, detections_per_image, widths, B, Hp, Wp) -> list:
+    """td_workspace_plan (include/treedet.h): the rows of the engine's workspace plan at one shape. No engine, no GPU.
+    widths: 16 integers (stem; conv1, conv2, conv3 of res2 .. res5; FPN; FC; mask deconv output)
+    → [{"name", "public" ("" if none), "kind" (names above), "elem", "dims" (4, 0-padded), "alloc_bytes", "phase"}]"""
+    rows, n = (WorkspaceRow * 128)(), C.c_int()
+    check(load().td_workspace_plan(int(precision), int(winograd), int(post_nms_topk), int(detections_per_image),
+                                   (C.c_int32 * 16)(*[int(x) for x in widths]), int(B), int(Hp), int(Wp), rows, 128, C.byref(n)), "td_workspace_plan")
+    return [{"name": r.name.decode(), "public": r.public_name.decode(), "kind": WORKSPACE_KINDS[r.kind], "elem": r.elem_size,
+             "dims": list(r.dims), "alloc_bytes": r.alloc_bytes, "phase": r.phase} for r in rows[:n.value]]
 
 
 def stream_ptr() -> int:

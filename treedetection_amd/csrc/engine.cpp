@@ -7,6 +7,7 @@
 // (proposals, detections) stay on the device and bound the later kernels, so there is no host sync inside.
 #include "common.h"
 #include "detect.h"
+#include "workspace.h"
 
 #include <cmath>
 #include <cstdio>
@@ -54,15 +55,11 @@ struct Block {
     int stride = 1;
 };
 
-struct NamedTensor {
-    void* p = nullptr;
-    int64_t dims[4] = {0, 0, 0, 0};
-    int elem = 4;
-};
+struct NamedTensor { void* p; WsDims dims; int elem; };     // what td_engine_tensor answers
 
 }  // namespace
 
-struct td_engine {
+struct td_engine : Workspace {          // (the workspace pointers: workspace.h)
     td_model_desc desc{};
     int device = 0;
     bool loaded = false;
@@ -85,35 +82,7 @@ struct td_engine {
     float mask_pred_b = 0.f;
     int fpn_c = 256, fc_dim = 1024;
 
-    // workspace (sized by reserve)
-    int rB = 0, rHp = 0, rWp = 0;
-    // activations (element type = engine precision)
-    void *stem_out = nullptr, *pool_out = nullptr;
-    void *t1[4] = {}, *t2[4] = {}, *scb[4] = {}, *res[4] = {}, *xtmp[4] = {};
-    void *inner[4] = {}, *pfeat[5] = {};
-    void* rpn_t = nullptr;
-    float* rpn_headbuf[5] = {};
-    uint32_t* key_ws = nullptr;
-    float *cand_boxes = nullptr, *cand_scores = nullptr;
-    int *cand_valid = nullptr, *cand_idx = nullptr;
-    unsigned long long* nms_mask = nullptr;
-    int *rpn_keep = nullptr, *rpn_keep_count = nullptr;
-    float *props = nullptr, *prop_scores = nullptr;
-    int* prop_count = nullptr;
-    void *pooled7 = nullptr, *fc1_out = nullptr, *fc2_out = nullptr;
-    float* pred_out = nullptr;
-    float *dboxes = nullptr, *dscores = nullptr;
-    int* dflags = nullptr;
-    float *sboxes = nullptr, *sscores = nullptr;
-    int *sidx = nullptr, *scount = nullptr, *det_keep = nullptr, *det_keep_count = nullptr;
-    float* det_boxes_net = nullptr;
-    void *pooled14 = nullptr, *mbuf0 = nullptr, *mbuf1 = nullptr, *deconv_out = nullptr;
-    float *mask_logits = nullptr, *mask_probs_compact = nullptr;
-    int* total_rows = nullptr;
-    // fallback outputs when the caller passes NULL fields
-    float *o_boxes = nullptr, *o_scores = nullptr, *o_mask_probs = nullptr;
-    int *o_classes = nullptr, *o_count = nullptr;
-
+    int rB = 0, rHp = 0, rWp = 0;          // what the workspace is sized for (td_engine_reserve)
     std::map<std::string, NamedTensor> named;
 
     int backbone_subbatch = 0;    // 0 = whole batch; else images per backbone pass (TD_BACKBONE_SUBBATCH)
@@ -123,7 +92,6 @@ struct td_engine {
     // winograd, wino_fused, wino_slab, wino_minc, wino43_min, wino_fold and fuse_head below, with the precision and wino_elems, are
     // the rules of conv_path (conv_path.h): which form a layer takes is that function's answer and nothing else's.
     bool winograd = true;         // TD_WINOGRAD=0 disables the Winograd path (diagnostics)
-    float *wino_v = nullptr, *wino_m = nullptr;
     size_t wino_elems = 0;
     bool group_levels = true;     // TD_GROUP_LEVELS=0: the FPN output convs / the RPN conv + head as one launch per pyramid level (fp16 engine)
     bool fuse_head = true;        // TD_FUSE_HEAD=0: the RPN's 1x1 head as a launch of its own at every level (diagnostics, tests)
@@ -382,13 +350,23 @@ td_status load_conv_bias(td_engine* e, const TensorMap& tm, const std::string& p
     return upload(e, std::vector<float>(b->data, b->data + L.cout), &L.bias);
 }
 
-void set_named(td_engine* e, const char* name, void* p, int64_t d0, int64_t d1 = 0, int64_t d2 = 0, int64_t d3 = 0,
-               int elem = 4) {
-    NamedTensor t;
-    t.p = p;
-    t.dims[0] = d0; t.dims[1] = d1; t.dims[2] = d2; t.dims[3] = d3;
-    t.elem = elem;
-    e->named[name] = t;
+// The geometry of the workspace plan (workspace.h) for this engine's model at one batch shape
+WsGeom engine_geom(const td_engine* e, int B, int Hp, int Wp) {
+    int32_t c[WS_WIDTHS] = {e->stem_c};
+    for (int s = 0; s < 4; ++s) { c[1 + s] = e->stages[s][0].c1.cout; c[5 + s] = e->stages[s][0].c2.cout; c[9 + s] = e->stages[s][0].c3.cout; }
+    c[13] = e->fpn_c; c[14] = e->fc_dim; c[15] = e->deconv.cout / 4;
+    return ws_geom(e->desc.precision, e->winograd, e->desc.post_nms_topk, e->desc.detections_per_image, c, B, Hp, Wp);
+}
+
+// td_engine_tensor's names of the rows a finished phase fills, at the geometry of the batch in hand (phase 0 brings the stem
+// pre-phase's two along: it runs the stem itself when nobody ran the pre-phase)
+void publish(td_engine* e, const WsGeom& g, int phase) {
+    for (const WsRow& r : ws_rows())
+        for (int i = 0; r.pub && (r.phase == phase || (phase == 0 && r.phase == TD_PHASE_STEM)) && i < r.count; ++i) {
+            char name[32];
+            snprintf(name, sizeof name, r.pub, i + 2);
+            e->named[name] = NamedTensor{*ws_slot(e, r, i), r.dims(g, i), (int)ws_elem_bytes(r, g)};
+        }
 }
 
 hipEvent_t prof_event(td_engine* e) {
@@ -753,99 +731,14 @@ td_status td_engine_reserve(td_engine* e, int B, int Hp, int Wp) {
     Wp = Wp > e->rWp ? Wp : e->rWp;
     TD_HIP_CHECK(hipSetDevice(e->device));
     free_pool(e->ws_allocs);
+    e->named.clear();           // the names of the last forward point into what was just freed
     e->rB = e->rHp = e->rWp = 0;
-    auto A = [&](auto** p, size_t elems) -> td_status {
-        void* q = nullptr;
-        td_status st = dev_alloc(e->ws_allocs, &q, elems * sizeof(**p));
-        *p = static_cast<std::remove_reference_t<decltype(*p)>>(q);
-        return st;
-    };
-    const size_t es = e->desc.precision == TD_PRECISION_FP16 ? 2 : 4;
-    auto AA = [&](void** p, size_t elems) -> td_status { return dev_alloc(e->ws_allocs, p, elems * es); };
-    td_status st;
-    const size_t b = B;
-    const int H2 = Hp / 4, W2 = Wp / 4;
-    if ((st = AA(&e->stem_out, b * (Hp / 2) * (Wp / 2) * e->stem_c)) < 0) return st;
-    if ((st = AA(&e->pool_out, b * H2 * W2 * e->stem_c)) < 0) return st;
-    int hs[5], wsz[5];
-    for (int l = 0; l < 4; ++l) {
-        hs[l] = Hp >> (l + 2);
-        wsz[l] = Wp >> (l + 2);
-    }
-    hs[4] = (hs[3] - 1) / 2 + 1;
-    wsz[4] = (wsz[3] - 1) / 2 + 1;
-    for (int s = 0; s < 4; ++s) {
-        const size_t px = b * hs[s] * wsz[s];
-        const int mid = e->stages[s][0].c1.cout, co = e->stages[s][0].c3.cout;
-        if ((st = AA(&e->t1[s], px * mid)) < 0) return st;
-        if ((st = AA(&e->t2[s], px * mid)) < 0) return st;
-        if ((st = AA(&e->scb[s], px * co)) < 0) return st;
-        if ((st = AA(&e->res[s], px * co)) < 0) return st;
-        if ((st = AA(&e->xtmp[s], px * co)) < 0) return st;
-        if ((st = AA(&e->inner[s], px * e->fpn_c)) < 0) return st;
-    }
-    size_t total_anchors = 0;
-    for (int l = 0; l < 5; ++l) {
-        const size_t px = b * hs[l] * wsz[l];
-        if ((st = AA(&e->pfeat[l], px * e->fpn_c)) < 0) return st;
-        if ((st = A(&e->rpn_headbuf[l], px * RPN_HEAD_C)) < 0) return st;
-        total_anchors += (size_t)hs[l] * wsz[l] * RPN_A;
-    }
-    if ((st = AA(&e->rpn_t, b * hs[0] * wsz[0] * e->fpn_c)) < 0) return st;
-    if ((st = A(&e->key_ws, rpn_topk_ws_elems((int)b, (int)total_anchors))) < 0) return st;
-    const size_t nc = b * RPN_LEVELS * RPN_CAND;
-    if ((st = A(&e->cand_boxes, nc * 4)) < 0) return st;
-    if ((st = A(&e->cand_scores, nc)) < 0) return st;
-    if ((st = A(&e->cand_valid, nc)) < 0) return st;
-    if ((st = A(&e->cand_idx, nc)) < 0) return st;
-    if ((st = A(&e->nms_mask, nc * (RPN_CAND / 64))) < 0) return st;
-    if ((st = A(&e->rpn_keep, nc)) < 0) return st;
-    if ((st = A(&e->rpn_keep_count, b * RPN_LEVELS)) < 0) return st;
-    const int P = e->desc.post_nms_topk, D = e->desc.detections_per_image;
-    if ((st = A(&e->props, b * P * 4)) < 0) return st;
-    if ((st = A(&e->prop_scores, b * P)) < 0) return st;
-    if ((st = A(&e->prop_count, b)) < 0) return st;
-    if ((st = AA(&e->pooled7, b * P * 49 * e->fpn_c)) < 0) return st;
-    if ((st = AA(&e->fc1_out, b * P * e->fc_dim)) < 0) return st;
-    if ((st = AA(&e->fc2_out, b * P * e->fc_dim)) < 0) return st;
-    if ((st = A(&e->pred_out, b * P * 6)) < 0) return st;
-    if ((st = A(&e->dboxes, b * P * 4)) < 0) return st;
-    if ((st = A(&e->dscores, b * P)) < 0) return st;
-    if ((st = A(&e->dflags, b * P)) < 0) return st;
-    if ((st = A(&e->sboxes, b * P * 4)) < 0) return st;
-    if ((st = A(&e->sscores, b * P)) < 0) return st;
-    if ((st = A(&e->sidx, b * P)) < 0) return st;
-    if ((st = A(&e->scount, b)) < 0) return st;
-    if ((st = A(&e->det_keep, b * D)) < 0) return st;
-    if ((st = A(&e->det_keep_count, b)) < 0) return st;
-    if ((st = A(&e->det_boxes_net, b * D * 4)) < 0) return st;
-    const size_t mrows = b * D;
-    if ((st = AA(&e->pooled14, mrows * 196 * e->fpn_c)) < 0) return st;
-    if ((st = AA(&e->mbuf0, mrows * 196 * e->fpn_c)) < 0) return st;
-    if ((st = AA(&e->mbuf1, mrows * 196 * e->fpn_c)) < 0) return st;
-    if ((st = AA(&e->deconv_out, mrows * 784 * (e->deconv.cout / 4))) < 0) return st;
-    if ((st = A(&e->mask_logits, mrows * 784)) < 0) return st;
-    if ((st = A(&e->mask_probs_compact, mrows * 784)) < 0) return st;
-    if ((st = A(&e->total_rows, 4)) < 0) return st;
-    if ((st = A(&e->o_boxes, b * D * 4)) < 0) return st;
-    if ((st = A(&e->o_scores, b * D)) < 0) return st;
-    if ((st = A(&e->o_classes, b * D)) < 0) return st;
-    if ((st = A(&e->o_count, b)) < 0) return st;
-    if ((st = A(&e->o_mask_probs, mrows * 784)) < 0) return st;
+    const WsGeom g = engine_geom(e, B, Hp, Wp);
     e->wino_v = e->wino_m = nullptr;
-    e->wino_elems = 0;
-    if (e->desc.precision == TD_PRECISION_FP32 && e->winograd) {
-        // Winograd workspace: 16 planes of [tiles][channels] for V and for M of the largest 3x3 layer that takes the path
-        // (FPN / RPN at p2, the bottleneck conv2 of every stage, the mask head over B*D RoIs of 14x14)
-        auto tiles = [](int h, int w) { return (size_t)((h + 1) / 2) * ((w + 1) / 2); };
-        size_t need = 0;
-        for (int l = 0; l < 5; ++l) need = std::max(need, b * tiles(hs[l], wsz[l]) * (size_t)e->fpn_c);
-        for (int s = 0; s < 4; ++s) need = std::max(need, b * tiles(hs[s], wsz[s]) * (size_t)e->stages[s][0].c2.cout);
-        need = std::max(need, mrows * tiles(14, 14) * (size_t)e->fpn_c);
-        e->wino_elems = 16 * need;
-        if ((st = A(&e->wino_v, e->wino_elems)) < 0) return st;
-        if ((st = A(&e->wino_m, e->wino_elems)) < 0) return st;
-    }
+    for (size_t k = 0; k < ws_row_count(g); ++k)
+        for (int i = 0; i < ws_rows()[k].count; ++i)
+            if (td_status st = dev_alloc(e->ws_allocs, ws_slot(e, ws_rows()[k], i), ws_alloc_bytes(ws_rows()[k], g, i)); st < 0) return st;
+    e->wino_elems = ws_wino_elems(g);
     e->rB = B;
     e->rHp = Hp;
     e->rWp = Wp;
@@ -1134,15 +1027,9 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
     // Runs in sub-batches of `sb` images (stem → res5 per sub-batch): the stage-2/3 activations of a sub-batch
     // (≈ 80 MB per 256-channel tensor and image at fp32) then hand over from layer to layer through the 256 MiB
     // Infinity Cache instead of HBM. sb comes from TD_BACKBONE_SUBBATCH (default: the whole batch at once).
-    int hs[5], wsz[5];
-    for (int l = 0; l < 4; ++l) {
-        hs[l] = Hp >> (l + 2);
-        wsz[l] = Wp >> (l + 2);
-    }
-    hs[4] = (hs[3] - 1) / 2 + 1;
-    wsz[4] = (wsz[3] - 1) / 2 + 1;
-    const size_t esz = prec == TD_PRECISION_FP16 ? 2 : 4;
-    auto off = [&](void* p, size_t elems) -> void* { return static_cast<char*>(p) + elems * esz; };
+    const WsGeom g = engine_geom(e, B, Hp, Wp);
+    const int *hs = g.h, *wsz = g.w;
+    auto off = [&](void* p, size_t elems) -> void* { return static_cast<char*>(p) + elems * g.es; };
     int sb = e->backbone_subbatch > 0 ? e->backbone_subbatch : B;
     if (sb > B) sb = B;
     const bool do_stem = PH(6) || (PH(0) && !e->stem_done);
@@ -1212,15 +1099,7 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
             }
         }
     }
-    if (PH(0) || PH(6)) {      // the stem pre-phase publishes its two tensors too (a stage test may stop after it)
-        set_named(e, "stem", e->stem_out, B, Hp / 2, Wp / 2, e->stem_c, (int)esz);
-        set_named(e, "pool", e->pool_out, B, Hp / 4, Wp / 4, e->stem_c, (int)esz);
-    }
     if (PH(0)) {
-    for (int si = 0; si < 4; ++si) {
-        const std::string nm = "res" + std::to_string(si + 2);
-        set_named(e, nm.c_str(), e->res[si], B, hs[si], wsz[si], e->stages[si][0].c3.cout, (int)esz);
-    }
     // ---- FPN (top-down; the nearest-2x upsampled add rides in the lateral conv's epilogue) ---------------------
     {
     ProfScope fpn_group(e, s, 0, 0.0, 0.0, true);
@@ -1242,10 +1121,6 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
     }
     { ProfScope ps(e, s, 2);
     if ((st = subsample2_launch(e->pfeat[3], e->pfeat[4], B, hs[3], wsz[3], e->fpn_c, prec, s)) < 0) return st; }
-    for (int l = 0; l < 5; ++l) {
-        const std::string nm = "p" + std::to_string(l + 2);
-        set_named(e, nm.c_str(), e->pfeat[l], B, hs[l], wsz[l], e->fpn_c, (e->desc.precision == TD_PRECISION_FP16 ? 2 : 4));
-    }
     // ---- RPN -----------------------------------------------------------------------------------------------------
     {
         ProfScope rpn_group(e, s, 0, 0.0, 0.0, true);
@@ -1257,18 +1132,11 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
             float* hy[5] = {e->rpn_headbuf[0], e->rpn_headbuf[1], e->rpn_headbuf[2], e->rpn_headbuf[3], e->rpn_headbuf[4]};
             if ((st = run_grouped(Ls, xs, nullptr, hy, 5, hs, wsz, true, &e->rpn_head, s)) < 0) return st;
         }
-        for (int l = 0; l < 5; ++l) {
-            if (group_rpn) {
-                const std::string nm = "rpn_head" + std::to_string(l + 2);
-                set_named(e, nm.c_str(), e->rpn_headbuf[l], B, hs[l], wsz[l], RPN_HEAD_C);
-                continue;
-            }
+        for (int l = 0; l < 5 && !group_rpn; ++l) {
             bool fused = false;
             if ((st = run_conv(e, e->rpn_conv, e->pfeat[l], B, hs[l], wsz[l], 1, 1, true, e->rpn_t, nullptr, 0, s, nullptr, 1, 0,
                                &e->rpn_head, e->rpn_headbuf[l], &fused)) < 0) return st;
             if (!fused && (st = run_conv(e, e->rpn_head, e->rpn_t, B, hs[l], wsz[l], 1, 0, false, e->rpn_headbuf[l], nullptr, 0, s)) < 0) return st;
-            const std::string nm = "rpn_head" + std::to_string(l + 2);
-            set_named(e, nm.c_str(), e->rpn_headbuf[l], B, hs[l], wsz[l], RPN_HEAD_C);
         }
     }
     trunk_group.reset();
@@ -1297,7 +1165,7 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
         }
         lv.total_anchors = off;
     }
-    const int P = e->desc.post_nms_topk, D = e->desc.detections_per_image;
+    const int P = g.P, D = g.D, mrows = g.mrows;
     FeatLevels fl{};
     for (int l = 0; l < 4; ++l) {
         fl.feat[l] = e->pfeat[l];
@@ -1311,30 +1179,19 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
     int* o_classes = out->classes ? out->classes : e->o_classes;
     int* o_count = out->count ? out->count : e->o_count;
     float* o_probs = out->mask_probs ? out->mask_probs : e->o_mask_probs;
-    const int mrows = B * D;
     if (PH(1)) {
     { ProfScope ps(e, s, 3);
     if ((st = rpn_topk_decode_launch(lv, valid, B, e->desc.pre_nms_topk, e->key_ws, e->cand_boxes, e->cand_scores,
                                      e->cand_valid, e->cand_idx, s)) < 0) return st; }
-    set_named(e, "rpn_cand_boxes", e->cand_boxes, B, RPN_LEVELS, RPN_CAND, 4);
-    set_named(e, "rpn_cand_scores", e->cand_scores, B, RPN_LEVELS, RPN_CAND);
-    set_named(e, "rpn_cand_valid", e->cand_valid, B, RPN_LEVELS, RPN_CAND);
-    set_named(e, "rpn_cand_idx", e->cand_idx, B, RPN_LEVELS, RPN_CAND);
     { ProfScope ps(e, s, 3);
     if ((st = nms_launch(e->cand_boxes, nullptr, e->cand_valid, B * RPN_LEVELS, RPN_CAND, e->desc.rpn_nms_thresh,
                          e->nms_mask, e->rpn_keep, e->rpn_keep_count, RPN_CAND, s)) < 0) return st; }
-    set_named(e, "rpn_keep", e->rpn_keep, B, RPN_LEVELS, RPN_CAND);
-    set_named(e, "rpn_keep_count", e->rpn_keep_count, B, RPN_LEVELS);
     { ProfScope ps(e, s, 3);
     if ((st = rpn_merge_launch(e->cand_boxes, e->cand_scores, e->rpn_keep, e->rpn_keep_count, B, P, e->props,
                                e->prop_scores, e->prop_count, P, s)) < 0) return st; }
-    set_named(e, "proposals", e->props, B, P, 4);
-    set_named(e, "proposal_scores", e->prop_scores, B, P);
-    set_named(e, "proposal_count", e->prop_count, B);
     // ---- box head -----------------------------------------------------------------------------------------------
     { ProfScope ps(e, s, 4);
     if ((st = roi_align_launch(fl, e->props, e->prop_count, B, P, 7, 0, e->pooled7, nullptr, prec, s)) < 0) return st; }
-    set_named(e, "pooled7", e->pooled7, (int64_t)B * P, 7, 7, e->fpn_c, (e->desc.precision == TD_PRECISION_FP16 ? 2 : 4));
     }   // phase 1
     if (PH(2)) {
     {
@@ -1343,34 +1200,23 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
     if ((st = run_conv(e, e->fc2, e->fc1_out, B * P, 1, 1, 1, 0, true, e->fc2_out, nullptr, 0, s)) < 0) return st;
     if ((st = run_conv(e, e->pred, e->fc2_out, B * P, 1, 1, 1, 0, false, e->pred_out, nullptr, 0, s)) < 0) return st;
     }
-    set_named(e, "box_pred", e->pred_out, (int64_t)B * P, 6);
     }   // phase 2
     if (PH(3)) {
     { ProfScope ps(e, s, 5);
     if ((st = det_decode_launch(e->pred_out, 6, e->props, e->prop_count, valid, B, P, e->desc.score_thresh, e->dboxes,
                                 e->dscores, e->dflags, s)) < 0) return st; }
-    set_named(e, "det_all_boxes", e->dboxes, B, P, 4);
-    set_named(e, "det_all_scores", e->dscores, B, P);
-    set_named(e, "det_flags", e->dflags, B, P);
     { ProfScope ps(e, s, 5);
     if ((st = sort_boxes_launch(e->dboxes, e->dscores, e->dflags, e->prop_count, B, P, e->sboxes, e->sscores, e->sidx,
                                 e->scount, s)) < 0) return st; }
-    set_named(e, "det_sorted_boxes", e->sboxes, B, P, 4);
-    set_named(e, "det_sorted_scores", e->sscores, B, P);
-    set_named(e, "det_sorted_count", e->scount, B);
     { ProfScope ps(e, s, 5);
     if ((st = nms_launch(e->sboxes, e->scount, nullptr, B, P, e->desc.nms_thresh, e->nms_mask, e->det_keep,
                          e->det_keep_count, D, s)) < 0) return st; }
-    set_named(e, "det_keep", e->det_keep, B, D);
-    set_named(e, "det_keep_count", e->det_keep_count, B);
     { ProfScope ps(e, s, 5);
     if ((st = det_finalize_launch(e->sboxes, e->sscores, e->det_keep, e->det_keep_count, valid, outsz, B, P, D,
                                   e->det_boxes_net, o_boxes, o_scores, o_classes, o_count, s)) < 0) return st; }
-    set_named(e, "det_boxes_net", e->det_boxes_net, B, D, 4);
     // ---- mask head (compact rows: only live detections are computed) ------------------------------------------
     { ProfScope ps(e, s, 4);
     if ((st = roi_align_launch(fl, e->det_boxes_net, o_count, B, D, 14, 1, e->pooled14, e->total_rows, prec, s)) < 0) return st; }
-    set_named(e, "pooled14", e->pooled14, mrows, 14, 14, e->fpn_c, (e->desc.precision == TD_PRECISION_FP16 ? 2 : 4));
     }   // phase 3
     if (PH(4)) {
     const void* mx = e->pooled14;
@@ -1383,19 +1229,11 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
     }
     if ((st = run_conv(e, e->deconv, mx, mrows, 14, 14, 1, 0, true, e->deconv_out, nullptr, 0, s, e->total_rows, 196, 1)) < 0) return st;
     }
-    // (stage tests: the device row count every launch above reads, and the last two layers' outputs as stored)
-    set_named(e, "mask_total_rows", e->total_rows, 1);
-    set_named(e, "mask_fcn3", e->mbuf0, mrows, 14, 14, e->fpn_c, (e->desc.precision == TD_PRECISION_FP16 ? 2 : 4));
-    set_named(e, "mask_fcn4", e->mbuf1, mrows, 14, 14, e->fpn_c, (e->desc.precision == TD_PRECISION_FP16 ? 2 : 4));
-    // pixel-shuffle store of the deconv (conv_tiles.h, out_mode 1): [rows, 28, 28, C / 4]
-    set_named(e, "mask_deconv", e->deconv_out, mrows, 28, 28, e->deconv.cout / 4, (e->desc.precision == TD_PRECISION_FP16 ? 2 : 4));
     }   // phase 4
     if (PH(5)) {
     { ProfScope ps(e, s, 6);
     if ((st = mask_predict_launch(e->deconv_out, e->mask_pred_w, e->mask_pred_b, e->deconv.cout / 4, mrows * 784,
                                   e->total_rows, 784, e->mask_logits, e->mask_probs_compact, prec, s)) < 0) return st; }
-    set_named(e, "mask_logits", e->mask_logits, mrows, 28, 28);
-    set_named(e, "mask_probs_compact", e->mask_probs_compact, mrows, 28, 28);
     { ProfScope ps(e, s, 6);
     if ((st = mask_scatter_launch(e->mask_probs_compact, o_count, B, D, o_probs, s)) < 0) return st; }
     if (out->mask_bits) {
@@ -1405,6 +1243,8 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
                                      out->mask_words_per_image, s)) < 0) return st; }
     }
     }   // phase 5
+    // every phase asked for has run: its names exist now (the stem pre-phase publishes its two too: a stage test may stop after it)
+    for (int k = 0; k <= TD_PHASE_STEM; ++k) if (PH(k)) publish(e, g, k);
     return TD_OK;
 }
 
@@ -1519,7 +1359,7 @@ td_status td_engine_tensor(td_engine* e, const char* name, void** dev_ptr, int64
         return TD_ERR_INVALID;
     }
     *dev_ptr = it->second.p;
-    for (int i = 0; i < 4; ++i) dims[i] = it->second.dims[i];
+    for (int i = 0; i < 4; ++i) dims[i] = it->second.dims.d[i];
     if (elem_size) *elem_size = it->second.elem;
     return TD_OK;
 }
@@ -1592,7 +1432,7 @@ td_status td_engine_read_tensor(td_engine* e, const char* name, void* dst_dev, i
     }
     int64_t n = it->second.elem;
     for (int i = 0; i < 4; ++i)
-        if (it->second.dims[i] > 0) n *= it->second.dims[i];
+        if (it->second.dims.d[i] > 0) n *= it->second.dims.d[i];
     TD_REQUIRE(bytes == n, "td_engine_read_tensor: '%s' is %lld bytes, caller passed %lld", name, (long long)n, (long long)bytes);
     TD_HIP_CHECK(hipMemcpyAsync(dst_dev, it->second.p, (size_t)n, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
     return TD_OK;
