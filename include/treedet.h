@@ -678,6 +678,27 @@ td_status td_crown_zonal_dev(const float* raster, int rows, int cols, const doub
 td_status td_crown_zonal(const float* raster, int rows, int cols, const double* transform, const double* xy, int64_t n_xy,
                          const int64_t* start, int n, float* out, int32_t* pos, int32_t* status);
 
+/* Crown label raster: the inverse question — which crown owns this pixel. The grid (rows, cols, HOST transform), the rings (xy,
+ * n_xy, start, n) and pixel membership are td_crown_zonal's above, unchanged (csrc/crown_zonal.h: pixel_centre, point_in_query,
+ * pixel_box as the search box). value: uint32 [n], one per ring; labels: uint32 [rows][cols]. The rule:
+ *   labels[r][c] = max( labels_before[r][c], max{ value[q] : status[q] == 0 and the centre of (r, c) belongs to ring q } )
+ * The call does NOT clear labels — the caller does —, so several calls, and the host function after the device one, composite
+ * into one raster. The maximum is unsigned and does not depend on the order of the rings or of the waves that draw them: the
+ * raster is reproducible bit for bit and the same from both functions for any values, equal ones and values >= 2^31 included. A
+ * value of 0 changes nothing.
+ * status int32 [n]: 0 drawn (a crown with no pixel centre inside draws nothing). 1 (device only): more than TD_ZONAL_RING_CAP
+ * vertices — nothing drawn; td_crown_labels draws such a crown. 2 refused, nothing drawn: fewer than 3 vertices, a non-finite
+ * coordinate, start[q] < 0, start[q + 1] < start[q] or start[q + 1] > n_xy (checked in the kernel before any vertex is read).
+ * td_crown_labels_dev: xy, start, value, labels, status are DEVICE memory, xy 16-byte aligned; one wave per crown, a bounded grid
+ * with a grid-stride loop, one relaxed agent-scope atomic maximum per pixel inside (csrc/crownzonal.hip); asynchronous on `stream`.
+ * td_crown_labels: HOST memory, host code, no vertex cap. Both return TD_ERR_INVALID (with a message, before anything runs) for a
+ * null pointer, n < 0 or n_xy < 0, rows or cols < 1 or 2^31 pixels and more, a non-finite transform or a misaligned xy; n = 0
+ * returns TD_OK and launches nothing. */
+td_status td_crown_labels_dev(int rows, int cols, const double* transform, const double* xy, int64_t n_xy, const int64_t* start,
+                              const uint32_t* value, int n, uint32_t* labels, int32_t* status, void* stream);
+td_status td_crown_labels(int rows, int cols, const double* transform, const double* xy, int64_t n_xy, const int64_t* start,
+                          const uint32_t* value, int n, uint32_t* labels, int32_t* status);
+
 /* GDAL's separable triangle-filter resampling (src.read(out_shape=..., resampling=bilinear), reference postprocessing.py:781-797)
  * of a raster that lies in device memory, with the NDVI rule of helpers.ndvi_array_from_rgbi (880-895) fused into the second pass.
  * src: DEVICE uint8 [height][width][c] pixel-interleaved (TD_SAMPLE_U8, c <= 4) or DEVICE float32 [height][width] (TD_SAMPLE_F32,

@@ -116,6 +116,10 @@ SIGNATURES = {
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "td_crown_zonal": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p, C.c_int64, C.c_void_p, C.c_int,
                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    "td_crown_labels_dev": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "td_crown_labels": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
+                                  C.c_void_p, C.c_void_p]),
     "td_resample_gdal_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int]
                              + [C.c_void_p] * 4 + [C.c_int, C.c_int64] + [C.c_void_p] * 4 + [C.c_int, C.c_int64]
                              + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),

@@ -23,7 +23,10 @@ they touch — treedetection_amd.merging; same files), ``device_outlines`` (true
 Region.relate(device=...); false: not one byte of any output changes; the tile flags of preprocessing stay on the host),
 ``crown_statistics`` ("circle" | "polygon", default "circle": the reference's statistics inside each crown's bounding circle;
 "polygon": TreeHeight and the NDVI mean / variance from the pixels whose centres lie inside the crown's outline, a wave per crown —
-postprocessing.crown_zonal_stats; "circle": not one byte of any output changes).
+postprocessing.crown_zonal_stats; "circle": not one byte of any output changes), ``crown_rasters`` (false | "height" | "image",
+default false: beside every ``processed_<name>.gpkg`` a label raster ``processed_<name>_crowns.tif`` on the full grid of the height
+or of the image raster — uint32, label k + 1 for the k-th feature of the layer, 0 = no crown, the higher Confidence_score on top,
+drawn on the GPU a wave per crown — postprocessing.crown_label_raster; the layers are the same bytes either way).
 """
 from __future__ import annotations
 
@@ -176,7 +179,7 @@ def get_config(config_path: str):
         "precision": "fp32", "resnet_depth": 101, "sharded_epilogue": "auto", "shard_by": "auto", "eager_stitch": True,
         "fp16_min_batch": 0, "device_contours": "auto", "device_decode": "auto", "device_filters": "auto",
         "device_decode_long_jpeg": False, "device_decode_planar": False, "clean_crowns": False, "device_seams": False,
-        "device_outlines": False, "crown_statistics": "circle",
+        "device_outlines": False, "crown_statistics": "circle", "crown_rasters": False,
     }
     for k, v in defaults.items():
         config[k] = config.get(k, v)

@@ -23,6 +23,9 @@
 //
 // Reads: raster[row * cols + col] only for 0 <= row < rows, 0 <= col < cols (the box is clamped to the raster); xy only inside
 // [start[q], start[q + 1]) after 0 <= start[q] <= start[q + 1] <= n_xy was checked — a wrong index gives status 2, not a load.
+//
+// td_crown_labels_dev, at the end of the file, is the same walk with a visitor that draws: the crown's value into a uint32 label
+// raster by atomic maximum (the inverse question: which crown owns this pixel).
 #include "common.h"
 #include "crown_zonal.h"
 
@@ -85,12 +88,54 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
+// Crown q's ring, checked and closed into L.ring[0 .. *m] → its status (0, 1 over ZN_CAP, 2 refused); with status 0 also its
+// float64 bounding box, the same in every lane. start is checked before any vertex is read. (Args: ZonalArgs or LabelArgs.)
+template <class Args>
+__device__ __forceinline__ int ring_to_lds(const Args& A, ZonalLds& L, int64_t q, int lane, int* m_out, double* bx0, double* by0, double* bx1,
+                                           double* by1) {
+    const int64_t s = A.start[q], e = A.start[q + 1];
+    int st = 0;
+    if (s < 0 || e < s || e > A.n_xy || e - s < 3) st = 2;
+    else if (e - s > ZN_CAP) st = 1;
+    const int m = st == 0 ? (int)(e - s) : 0;
+    const double inf = __builtin_inf();
+    double x0 = inf, y0 = inf, x1 = -inf, y1 = -inf;
+    if (st == 0) {
+        bool bad = false;
+        TD_WAVE_SYNC();                                                // the previous crown's reads are over
+        for (int k = lane; k <= m; k += 64) {
+            const double2 p = A.xy[s + (k == m ? 0 : k)];
+            bad |= !is_finite(p.x) || !is_finite(p.y);
+            L.ring[k] = Pt{p.x, p.y};
+            x0 = p.x < x0 ? p.x : x0;
+            y0 = p.y < y0 ? p.y : y0;
+            x1 = p.x > x1 ? p.x : x1;
+            y1 = p.y > y1 ? p.y : y1;
+        }
+        TD_WAVE_SYNC();
+        if (__any(bad)) st = 2;
+    }
+    if (st == 0) {
+        x0 = wave_min(x0);
+        y0 = wave_min(y0);
+        x1 = wave_max(x1);
+        y1 = wave_max(y1);
+    }
+    *m_out = m;
+    *bx0 = x0;
+    *by0 = y0;
+    *bx1 = x1;
+    *by1 = y1;
+    return st;
+}
+
+// (Args: ZonalArgs, or LabelArgs below — the walk reads A.t and A.cols only.)
 // visit(row, col) for every pixel of box B that belongs to the ring (L.ring[0 .. m], closed; bounding box x0 .. y1). The calls come
 // from divergent lanes: visit holds no wave intrinsic. With `runs` the verdicts of the walk are kept: every run of 64 pixels with
 // a pixel inside becomes an entry of L.runs, and *runs counts them — a count above ZN_RUNS says that the list is incomplete (the
 // rotated walk, whose lanes do not share a row, always says so).
-template <class Visit>
-__device__ __forceinline__ void zonal_walk(const ZonalArgs& A, ZonalLds& L, int m, const Box& B, double x0, double y0, double x1, double y1,
+template <class Args, class Visit>
+__device__ __forceinline__ void zonal_walk(const Args& A, ZonalLds& L, int m, const Box& B, double x0, double y0, double x1, double y1,
                                            int lane, int* runs, Visit&& visit) {
     if (runs) *runs = 0;
     if (B.r0 > B.r1 || B.c0 > B.c1) return;
@@ -168,28 +213,9 @@ __global__ __launch_bounds__(64 * ZN_WPB) void crown_zonal_kernel(const ZonalArg
     ZonalLds& L = lds[wave];
     const float nanf_ = __builtin_nanf("");
     for (int64_t q = (int64_t)blockIdx.x * ZN_WPB + wave; q < A.n; q += (int64_t)gridDim.x * ZN_WPB) {
-        const int64_t s = A.start[q], e = A.start[q + 1];
-        int st = 0;
-        if (s < 0 || e < s || e > A.n_xy || e - s < 3) st = 2;
-        else if (e - s > ZN_CAP) st = 1;
-        const int m = st == 0 ? (int)(e - s) : 0;
-        const double inf = __builtin_inf();
-        double x0 = inf, y0 = inf, x1 = -inf, y1 = -inf;
-        if (st == 0) {
-            bool bad = false;
-            TD_WAVE_SYNC();                                            // the previous crown's reads are over
-            for (int k = lane; k <= m; k += 64) {
-                const double2 p = A.xy[s + (k == m ? 0 : k)];
-                bad |= !is_finite(p.x) || !is_finite(p.y);
-                L.ring[k] = Pt{p.x, p.y};
-                x0 = p.x < x0 ? p.x : x0;
-                y0 = p.y < y0 ? p.y : y0;
-                x1 = p.x > x1 ? p.x : x1;
-                y1 = p.y > y1 ? p.y : y1;
-            }
-            TD_WAVE_SYNC();
-            if (__any(bad)) st = 2;
-        }
+        int m;
+        double x0, y0, x1, y1;
+        const int st = ring_to_lds(A, L, q, lane, &m, &x0, &y0, &x1, &y1);
         float* o = A.out + 4 * q;
         int32_t* ps = A.pos + 3 * q;
         if (st != 0) {
@@ -200,10 +226,6 @@ __global__ __launch_bounds__(64 * ZN_WPB) void crown_zonal_kernel(const ZonalArg
             }
             continue;
         }
-        x0 = wave_min(x0);
-        y0 = wave_min(y0);
-        x1 = wave_max(x1);
-        y1 = wave_max(y1);
         const Box B = pixel_box(A.t, x0, y0, x1, y1, A.rows, A.cols);
 
         float vmax = 0.f, vmin = 0.f;
@@ -279,7 +301,71 @@ __global__ __launch_bounds__(64 * ZN_WPB) void crown_zonal_kernel(const ZonalArg
     }
 }
 
+// ---- td_crown_labels_dev: the same walk, drawing. labels[r][c] = max(labels[r][c], value[q]) for every pixel whose centre belongs to
+// crown q: one relaxed agent-scope atomicMax per pixel inside, issued from the walk's visitor — on the axis-aligned path a run of 64
+// pixels is one wave instruction over 256 contiguous bytes. The unsigned maximum does not depend on the order in which waves
+// arrive, so the raster is the host twin's (crownlabels_host.cpp) bit for bit. No second pass, no `runs` list, nothing cleared.
+// Writes: labels[row * cols + col] only for pixels of the box, which pixel_box clamps to the raster; status[q].
+struct LabelArgs {
+    int rows, cols;
+    Affine t;
+    const double2* xy;
+    int64_t n_xy;
+    const int64_t* start;
+    const uint32_t* value;
+    int n;
+    unsigned* labels;
+    int32_t* status;
+};
+
+__global__ __launch_bounds__(64 * ZN_WPB) void crown_labels_kernel(const LabelArgs A) {
+    __shared__ __attribute__((aligned(16))) ZonalLds lds[ZN_WPB];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    ZonalLds& L = lds[wave];
+    for (int64_t q = (int64_t)blockIdx.x * ZN_WPB + wave; q < A.n; q += (int64_t)gridDim.x * ZN_WPB) {
+        int m;
+        double x0, y0, x1, y1;
+        const int st = ring_to_lds(A, L, q, lane, &m, &x0, &y0, &x1, &y1);
+        if (lane == 0) A.status[q] = st;
+        if (st != 0) continue;
+        const unsigned v = A.value[q];
+        if (v == 0u) continue;                                         // the maximum with 0 changes nothing
+        const Box B = pixel_box(A.t, x0, y0, x1, y1, A.rows, A.cols);
+        zonal_walk(A, L, m, B, x0, y0, x1, y1, lane, nullptr, [&](int r, int col) {
+            __hip_atomic_fetch_max(A.labels + ((long long)r * A.cols + col), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        });
+    }
+}
+
 }  // namespace
+
+extern "C" td_status td_crown_labels_dev(int rows, int cols, const double* transform, const double* xy, int64_t n_xy, const int64_t* start,
+                                         const uint32_t* value, int n, uint32_t* labels, int32_t* status, void* stream) {
+    TD_REQUIRE(transform && xy && start && value && labels && status, "td_crown_labels_dev: null pointer");
+    TD_REQUIRE(n >= 0 && n_xy >= 0, "td_crown_labels_dev: n = %d, n_xy = %lld, counts cannot be negative", n, (long long)n_xy);
+    TD_REQUIRE(rows >= 1 && cols >= 1 && (int64_t)rows * cols <= (int64_t)INT32_MAX,
+               "td_crown_labels_dev: a %d x %d raster: both at least 1 and fewer than 2^31 pixels", rows, cols);
+    for (int k = 0; k < 6; ++k)
+        TD_REQUIRE(is_finite(transform[k]), "td_crown_labels_dev: transform[%d] is not finite", k);
+    TD_REQUIRE(reinterpret_cast<uintptr_t>(xy) % 16 == 0, "td_crown_labels_dev: xy must be 16-byte aligned (vertices are read as double2)");
+    if (n == 0) return TD_OK;
+    LabelArgs A{};
+    A.rows = rows;
+    A.cols = cols;
+    A.t = Affine{transform[0], transform[1], transform[2], transform[3], transform[4], transform[5]};
+    A.xy = reinterpret_cast<const double2*>(xy);
+    A.n_xy = n_xy;
+    A.start = start;
+    A.value = value;
+    A.n = n;
+    A.labels = labels;
+    A.status = status;
+    const int64_t groups = ((int64_t)n + ZN_WPB - 1) / ZN_WPB;
+    hipLaunchKernelGGL(crown_labels_kernel, dim3((unsigned)(groups < ZN_GRID_MAX ? groups : ZN_GRID_MAX)), dim3(64 * ZN_WPB), 0,
+                       static_cast<hipStream_t>(stream), A);
+    TD_KERNEL_CHECK();
+    return TD_OK;
+}
 
 extern "C" td_status td_crown_zonal_dev(const float* raster, int rows, int cols, const double* transform, const double* xy, int64_t n_xy,
                                         const int64_t* start, int n, float* out, int32_t* pos, int32_t* status, void* stream) {

@@ -23,7 +23,7 @@ from .preprocessing import tile_data
 from .recoveries import load_prediction_recovery_data, save_prediction_recovery_data
 from .fusion import exclude_outlines, fuse_predictions, outline_device  # noqa: F401
 from .merging import merge_and_crop_images
-from .postprocessing import process_files_in_directory
+from .postprocessing import crown_raster_path, crown_rasters_setting, process_files_in_directory
 from .stitching import process_and_stitch_predictions
 
 
@@ -405,11 +405,16 @@ def postprocess_files(config):
     for name in sorted(os.listdir(pred_dir)):
         if not (name.endswith(".geojson") or name.endswith(".gpkg")) or not name.startswith("processed_"):
             continue
-        plain = name.replace("processed_", "")
-        if config.get("timestamped_output_directory"):
-            os.makedirs(os.path.join(config["output_directory"], stamp), exist_ok=True)
-            shutil.copy(os.path.join(pred_dir, name), os.path.join(config["output_directory"], stamp, plain))
-        shutil.copy(os.path.join(pred_dir, name), os.path.join(config["output_directory"], plain))
+        copies = [name]
+        raster = os.path.basename(crown_raster_path(name))          # ``crown_rasters``: the label raster goes next to its layer
+        if crown_rasters_setting(config.get("crown_rasters", False)) and os.path.exists(os.path.join(pred_dir, raster)):
+            copies.append(raster)
+        for item in copies:
+            plain = item.replace("processed_", "")
+            if config.get("timestamped_output_directory"):
+                os.makedirs(os.path.join(config["output_directory"], stamp), exist_ok=True)
+                shutil.copy(os.path.join(pred_dir, item), os.path.join(config["output_directory"], stamp, plain))
+            shutil.copy(os.path.join(pred_dir, item), os.path.join(config["output_directory"], plain))
 
 
 def cleanup_files(config):

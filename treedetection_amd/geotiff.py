@@ -167,7 +167,7 @@ class GeoTiff:
         self._flat = None
         self._fd = None
         item = self.dtype.itemsize
-        if self.compression == 1 and self.planar == 1 and self._strips and self._predictor != 3:
+        if self.compression == 1 and self.planar == 1 and self._strips and self._predictor == 1:     # (a predictor is undone per block)
             row_bytes = W * self.count * item
             offs = self._offs
             if all(offs[i + 1] - offs[i] == self._bh * row_bytes for i in range(len(offs) - 1)):
@@ -924,7 +924,7 @@ def write_geotiff(path: str, data: np.ndarray, transform: Sequence[float], epsg:
                   nodata: Optional[float] = None, jpeg_tables: bool = False, jpeg_restart: int = 0,
                   jpeg_quality: int = 90, jpeg_subsampling: int = 2, zstd_level: int = 9) -> None:
     """Classic little-endian TIFF with the GeoTIFF tags the reader understands. data: [bands, rows, cols] or
-    [rows, cols]; uint8 / uint16 / float32. Defaults: one uncompressed pixel-interleaved strip (what the tile reader
+    [rows, cols]; uint8 / uint16 / uint32 (label rasters: SampleFormat 1, 32 bits; no JPEG, no predictor 3) / float32. Defaults: one uncompressed pixel-interleaved strip (what the tile reader
     maps without copying). Options: ``tile=(tile_rows, tile_cols)`` (multiples of 16) or ``rows_per_strip``,
     ``compression`` None / "deflate" / "lzw" (td_tiff_lzw_encode, blocks encoded on host threads) / "jpeg" (lossy; Pillow's encoder per
     block) / "zstd" (test rasters and the bench only: libzstd's one-shot ZSTD_compress at ``zstd_level`` through ctypes, the system's
@@ -938,7 +938,8 @@ def write_geotiff(path: str, data: np.ndarray, transform: Sequence[float], epsg:
     if arr.ndim == 2:
         arr = arr[None]
     C, H, W = arr.shape
-    fmt = {np.dtype(np.uint8): (1, 8), np.dtype(np.uint16): (1, 16), np.dtype(np.float32): (3, 32)}[arr.dtype]
+    fmt = {np.dtype(np.uint8): (1, 8), np.dtype(np.uint16): (1, 16), np.dtype(np.uint32): (1, 32),
+           np.dtype(np.float32): (3, 32)}[arr.dtype]
     if compression not in (None, "deflate", "lzw", "jpeg", "zstd"):
         raise ValueError("compression must be None, 'deflate', 'lzw', 'jpeg' or 'zstd'")
     if predictor not in (1, 2, 3):
@@ -1041,7 +1042,7 @@ def write_geotiff(path: str, data: np.ndarray, transform: Sequence[float], epsg:
     add(33922, 12, [0.0, 0.0, 0.0, c, f, 0.0])
     add(34735, 3, [1, 1, 0, 3, 1024, 0, 1, 1, 1025, 0, 1, 1, 3072, 0, 1, int(epsg)])
     if nodata is not None:
-        add(42113, 2, repr(float(nodata)))
+        add(42113, 2, str(int(nodata)) if fmt == (1, 32) and float(nodata).is_integer() else repr(float(nodata)))
     entries.sort(key=lambda t: t[0])
     n = len(entries)
     ifd_off = 8

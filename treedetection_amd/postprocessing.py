@@ -11,7 +11,9 @@ filters and the selection rules are small host numpy, written to follow the refe
 which are listed in DESIGN.md §7 and marked ``# ref:`` below; with
 ``device_filters: true`` the pair tests of the two box filters run on the GPU and only the sparse result comes back
 (``td_crown_pairs_count`` / ``td_crown_pairs_fill``, crownpairs.hip; same arithmetic, same results); with ``clean_crowns: true`` the
-layer is first thinned by the IoU of the crown OUTLINES (:mod:`treedetection_amd.cleaning`; off by default: same files).
+layer is first thinned by the IoU of the crown OUTLINES (:mod:`treedetection_amd.cleaning`; off by default: same files); with
+``crown_rasters: height | image`` a uint32 label raster of the layer's crowns is drawn on the GPU and written beside it
+(``td_crown_labels_dev``, :func:`crown_label_raster`, :func:`write_crown_raster`; off by default: no such file, same layers).
 GDAL's bilinear decimation of the rasters (``ndvi_scaling_factor`` 0.2 in the example config) is restated from its
 published algorithm (:func:`resample_bilinear_gdal`, both directions); with ``device_decode: true`` the rasters are decoded in
 HBM and the same taps are applied there, NDVI included (:func:`resample_on_device`, ``td_resample_gdal_dev``). Not reproduced: fiona's
@@ -320,6 +322,132 @@ def crown_zonal_stats(raster, transform, rings, device: Optional[int] = 0, packe
         h_raster = raster.cpu().numpy() if on_device else raster
         out[capped], pos[capped], status[capped] = _zonal_host(h_raster, transform, np.ascontiguousarray(np.concatenate(sub)), sub_start)
     return out, pos[:, 0].copy(), pos[:, 1:].copy(), status
+
+
+# ---- crown label rasters (opt-in: ``crown_rasters``) ---------------------------------------------------------------------------
+def crown_rasters_setting(value=False):
+    """The ``crown_rasters`` config key: False (default, also for None: no raster), "height" or "image" (the grid the labels are
+    drawn on). Anything else is refused."""
+    if value is None or value is False:
+        return False
+    if not isinstance(value, str) or value not in ("height", "image"):
+        raise ValueError(f"crown_rasters must be false, 'height' or 'image', got {value!r}")
+    return value
+
+
+def _u32_values(values, n: int) -> np.ndarray:
+    """``values`` as uint32 [n]: integers in [0, 2^32) only."""
+    v = np.asarray(values)
+    if n == 0 and v.size == 0:
+        return np.zeros(0, np.uint32)
+    if v.shape != (n,) or v.dtype.kind not in "iu":
+        raise ValueError(f"crown_label_raster: values must be {n} unsigned integers below 2^32, got {v.dtype} {v.shape}")
+    if n and (int(v.min()) < 0 or int(v.max()) >= 1 << 32):
+        raise ValueError("crown_label_raster: values must be unsigned integers below 2^32")
+    return np.array(v, dtype=np.uint32)                      # (a copy of its own: writable, C-contiguous)
+
+
+def _labels_host(labels: np.ndarray, transform, xy: np.ndarray, start: np.ndarray, values: np.ndarray) -> np.ndarray:
+    """td_crown_labels over ``labels`` (uint32 [rows, cols], C-contiguous) in place → status int32 [n]."""
+    import ctypes as C
+    n = start.size - 1
+    status = np.empty(n, np.int32)
+    pts = xy if xy.size else np.zeros((1, 2))                # (an empty vertex array still needs a pointer the library accepts)
+    vals = values if n else np.zeros(1, np.uint32)
+    tr = (C.c_double * 6)(*[float(v) for v in transform[:6]])
+    _lib.check(_lib.load().td_crown_labels(labels.shape[0], labels.shape[1], tr, pts.ctypes.data, xy.shape[0], start.ctypes.data,
+                                           vals.ctypes.data, n, labels.ctypes.data, status.ctypes.data), "td_crown_labels")
+    return status
+
+
+def crown_label_raster(rings, values, transform, shape, device: Optional[int] = 0, out=None, packed=None, uploaded=None):
+    """Crown outlines drawn into a label raster → (labels uint32 [rows, cols], status int32 [n]):
+    ``labels[r, c] = max(labels before, max{values[q] : the centre of pixel (r, c) belongs to ring q})`` (include/treedet.h,
+    td_crown_labels; membership is crown_zonal_stats's). The maximum is unsigned and order-free, so the raster is the same bits on
+    the host and on the device. ``values``: one unsigned integer below 2^32 per ring (anything else: ValueError); 0 draws nothing.
+    ``transform``, ``shape`` = (rows, cols): the grid. ``device``: None — td_crown_labels on numpy arrays; ``out``, a C-contiguous
+    uint32 array [rows, cols], is composited over in place. A GPU index — td_crown_labels_dev, a wave per crown, on a tensor that is
+    allocated and zeroed unless ``out`` is given: a contiguous CUDA tensor [rows, cols] of 32-bit integers (int32 holds the bits
+    where torch.uint32 lacks an op), drawn over where it lies and returned as it is; without ``out`` the labels come back as a
+    numpy uint32 array. Crowns the kernel leaves out (status 1: more than ``_lib.ZONAL_RING_CAP`` vertices) are drawn by the host
+    function after the download and merged with np.maximum — the same raster, the rule being order-free —, their status the
+    host's. Refused crowns (status 2) draw nothing. ``packed`` / ``uploaded`` as for crown_zonal_stats."""
+    from .cleaning import pack_rings
+    import ctypes as C
+
+    xy, start = packed if packed is not None else pack_rings(rings)
+    n = start.size - 1
+    vals = _u32_values(values, n)
+    rows, cols = int(shape[0]), int(shape[1])
+    if rows < 1 or cols < 1 or rows * cols >= 1 << 31:
+        raise ValueError(f"crown_label_raster: a {rows} x {cols} raster: both at least 1 and fewer than 2^31 pixels")
+    if device is None:
+        if out is None:
+            out = np.zeros((rows, cols), np.uint32)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.uint32 and out.shape == (rows, cols) and out.flags.c_contiguous):
+            raise ValueError(f"crown_label_raster: out must be a C-contiguous uint32 array [{rows}, {cols}]")
+        return out, _labels_host(out, transform, xy, start, vals)
+    given = out is not None
+    if given and not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype in (torch.int32, torch.uint32) and tuple(out.shape) == (rows, cols)
+                      and out.is_contiguous()):
+        raise ValueError(f"crown_label_raster: out must be a contiguous int32 / uint32 CUDA tensor [{rows}, {cols}]")
+    dev = out.device if given else torch.device("cuda", device)
+    with torch.cuda.device(dev):
+        d_l = out if given else torch.zeros((rows, cols), dtype=torch.int32, device=dev)
+        if n == 0:
+            return (d_l if given else np.zeros((rows, cols), np.uint32)), np.zeros(0, np.int32)
+        d_xy, d_start = uploaded if uploaded is not None else upload_rings(xy, start, dev)
+        d_v = torch.from_numpy(vals.view(np.int32)).to(dev)
+        d_s = torch.empty(n, dtype=torch.int32, device=dev)
+        tr = (C.c_double * 6)(*[float(v) for v in transform[:6]])
+        _lib.check(_lib.load().td_crown_labels_dev(rows, cols, tr, d_xy.data_ptr(), xy.shape[0], d_start.data_ptr(), d_v.data_ptr(), n,
+                                                   d_l.data_ptr(), d_s.data_ptr(), _lib.stream_ptr()), "td_crown_labels_dev")
+        status = d_s.cpu().numpy()
+        capped = np.flatnonzero(status == 1)
+        if not capped.size:
+            return (d_l if given else d_l.cpu().numpy().view(np.uint32)), status
+        # the host function draws these crowns alone, into a raster of their own; the maximum of the two is the whole rule
+        sub = [xy[start[k]:start[k + 1]] for k in capped]
+        sub_start = np.zeros(capped.size + 1, np.int64)
+        np.cumsum([r.shape[0] for r in sub], out=sub_start[1:])
+        extra = np.zeros((rows, cols), np.uint32)
+        status[capped] = _labels_host(extra, transform, np.ascontiguousarray(np.concatenate(sub)), sub_start, np.ascontiguousarray(vals[capped]))
+        merged = np.maximum(d_l.cpu().numpy().view(np.uint32), extra)
+        if not given:
+            return merged, status
+        d_l.copy_(torch.from_numpy(merged.view(np.int32)).to(dev).view(d_l.dtype))
+        return d_l, status
+
+
+def crown_priorities(scores, labels=None):
+    """Distinct drawing priorities for crowns that may overlap → (priority uint32 [n], table uint32 [n + 1]). The higher score gets
+    the higher priority; among equal scores the LOWER index does; the priorities are 1 .. n, so under crown_label_raster's maximum
+    a pixel goes to the best crown that holds it. ``table[priority[k]] = labels[k]`` (default k + 1) and ``table[0] = 0`` take a
+    raster of composited priorities back to labels (labels_from_priorities). NaN scores are refused."""
+    s = np.asarray(scores, dtype=np.float64).reshape(-1)
+    n = s.size
+    if np.isnan(s).any():
+        raise ValueError("crown_priorities: a score is NaN")
+    if n >= (1 << 31) - 1:
+        raise ValueError("crown_priorities: too many crowns")
+    order = np.lexsort((-np.arange(n), s))                  # ascending score; among equal scores descending index
+    priority = np.empty(n, np.uint32)
+    priority[order] = np.arange(1, n + 1, dtype=np.uint32)
+    table = np.zeros(n + 1, np.uint32)
+    table[priority] = np.arange(1, n + 1, dtype=np.uint32) if labels is None else _u32_values(labels, n)
+    return priority, table
+
+
+def labels_from_priorities(raster, table: np.ndarray):
+    """A raster of composited priorities (crown_label_raster over crown_priorities' values) → the labels, ``table[raster]``. A CUDA
+    tensor of 32-bit integers is looked up on the device, through 32-bit indices — no temporary larger than the raster — and comes
+    back as a tensor of the same dtype; a numpy array gives a numpy uint32 array."""
+    table = np.ascontiguousarray(table, dtype=np.uint32)
+    if isinstance(raster, torch.Tensor):
+        d_t = torch.from_numpy(table.view(np.int32)).to(raster.device)
+        idx = raster.view(torch.int32).reshape(-1)          # priorities are at most n < 2^31: the bits are the index
+        return torch.index_select(d_t, 0, idx).view(raster.dtype).reshape(raster.shape)
+    return table[np.asarray(raster)]
 
 
 # ---- box filters (host numpy, the reference's dtypes) -------------------------------------------------------
@@ -752,15 +880,16 @@ def process_single_file(file_path, processed_file_path, height_data_path, rgbi_d
     from .cleaning import clean_crowns, clean_crowns_setting
     thin = clean_crowns_setting((config or {}).get("clean_crowns", False))      # (a bad value is refused, not printed)
     crown_statistics_setting((config or {}).get("crown_statistics", "circle"))  # (likewise)
+    rasters = crown_rasters_setting((config or {}).get("crown_rasters", False)) # (likewise)
     try:
+        device = int(str(device_id).replace("cuda:", "") or 0) if str(device_id) != "cpu" else 0
         layer = read_layer(file_path)
         scores = layer.columns.get("Confidence_score", [None] * len(layer))
         layer_rings = layer.rings()
         if thin:        # ``clean_crowns: true``: the layer is thinned by polygon IoU first, rings and scores together (host functions)
             kept = clean_crowns(layer_rings, scores, iou_threshold=0.7, confidence=0, area_threshold=0, device=None)
             layer_rings, scores = [layer_rings[i] for i in kept], [scores[i] for i in kept]
-        feats = process_layer(layer_rings, scores, config, height_data_path, rgbi_data_path,
-                              int(str(device_id).replace("cuda:", "") or 0) if str(device_id) != "cpu" else 0)
+        feats = process_layer(layer_rings, scores, config, height_data_path, rgbi_data_path, device)
         rings = [f["ring"] for f in feats]
         cols = {c: [f["properties"][c] for f in feats] for c in COLUMNS}
         if rings:
@@ -769,10 +898,43 @@ def process_single_file(file_path, processed_file_path, height_data_path, rgbi_d
         else:
             extent, cols = None, {}
         write_blobs(processed_file_path, (polygon_blob(r, layer.srs_id) for r in rings), cols, layer.srs_id, extent)
-        return file_path
     except Exception as e:
         print(f"Error postprocessing file {file_path}: {e}")
         return None
+    if rasters:         # ``crown_rasters``: the layer is written; a failure here is printed and does not lose it
+        try:
+            write_crown_raster(crown_raster_path(processed_file_path), rings, cols.get("Confidence_score", []),
+                               height_data_path if rasters == "height" else rgbi_data_path, device, layer.srs_id)
+        except Exception as e:
+            print(f"Error writing the crown raster of {file_path}: {e}")
+    return file_path
+
+
+def crown_raster_path(layer_path: str) -> str:
+    """``processed_<name>.gpkg`` → ``processed_<name>_crowns.tif``."""
+    return os.path.splitext(layer_path)[0] + "_crowns.tif"
+
+
+def write_crown_raster(path: str, rings, scores, grid_path: str, device: int = 0, fallback_epsg: Optional[int] = None) -> None:
+    """The label raster of one processed layer: single-band uint32 on the FULL grid of the raster at ``grid_path`` (size, transform
+    and EPSG from its header), label k + 1 for ``rings[k]``, 0 = no crown (GDAL_NODATA 0), tiled, LZW. Where crowns overlap, the
+    higher score wins and among equal scores the lower index (crown_priorities): the priorities are composited on the GPU
+    (crown_label_raster) and taken back to labels there (labels_from_priorities)."""
+    from .geotiff import write_geotiff
+    g = GeoTiff(grid_path)
+    rows, cols, t, epsg = g.height, g.width, g.transform, g.epsg
+    g.close()
+    if t[1] != 0.0 or t[3] != 0.0:
+        raise ValueError(f"{grid_path}: a rotated grid cannot be written as a crown raster")
+    priority, table = crown_priorities(scores)
+    dev = torch.device("cuda", device)
+    with torch.cuda.device(dev):
+        d_l = torch.zeros((rows, cols), dtype=torch.int32, device=dev)
+        d_l, _ = crown_label_raster(rings, priority, t, (rows, cols), device, out=d_l)
+        labels = labels_from_priorities(d_l, table).cpu().numpy().view(np.uint32)
+    tmp = path + ".part"
+    write_geotiff(tmp, labels, t, int(epsg if epsg is not None else fallback_epsg), tile=(256, 256), compression="lzw", nodata=0)
+    os.replace(tmp, path)
 
 
 # ---- resume file (postprocessing.py:827-874) -----------------------------------------------------------------
