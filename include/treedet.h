@@ -218,6 +218,21 @@ void td_resize_shape(int h, int w, int short_edge, int max_size, int* out_h, int
 td_status td_bottleneck_tail_nhwc(const void* x, const void* w2, const float* scale2, const float* bias2, const void* w3,
                                   const float* scale3, const float* bias3, const void* shortcut, void* y, int B, int H, int W,
                                   int mid, int cout, int precision, void* stream);
+/* The split form of the float32 tail (mid = 64, cout = 256; what the fp32 engine runs in res2 by default): the 3x3 contracts on
+ * the bf16 matrix cores with both operands as three bf16 pieces (w2 is split here, the engine splits once at load), the 1x1 and
+ * its epilogue are td_bottleneck_tail_nhwc's. Same tensors; another rounding of the 3x3 than the fp32 form (inside the same
+ * float64 bound). mid_out NULL: the fused launch, y is written. mid_out [B,H,W,mid] (DEVICE float32): the unfused twin — the
+ * launch stops behind conv2 + FrozenBN + ReLU and stores that tensor; w3 / scale3 / bias3 / shortcut / y are ignored (may be
+ * NULL). The fused y is bit-identical to the mid_out launch followed by td_conv2d_nhwc(1x1, residual, relu) on a float32 tile. */
+td_status td_bottleneck_tail_split_nhwc(const void* x, const void* w2, const float* scale2, const float* bias2, const void* w3,
+                                        const float* scale3, const float* bias3, const void* shortcut, void* y, void* mid_out,
+                                        int B, int H, int W, int mid, int cout, void* stream);
+/* Host only: the split-bf16 filter bank of conv_split.hip / the split tail from float32 filters w [cout][taps][cin] (taps = 1:
+ * a 1x1 / FC bank; 9: a 3x3 bank), cin a multiple of 32: [ceil(cout/32)][taps * cin/32 k-chunks, channel chunk outer, tap
+ * inner][2 slices][3 pieces][64 lanes][8 bf16]; lane l = (r = l & 31, h = l >> 5) of (tile t, chunk cc * taps + tap, slice s, piece
+ * p) holds piece p of w[32 t + r][tap][32 cc + 16 s + 4 h .. + 3] and [.. + 8 + 4 h .. + 3]. Returns the bank's size in bytes
+ * (what `out` must hold; nothing is written when out is NULL or out_bytes is smaller), < 0 on bad arguments. */
+int64_t td_conv_split_pack(const float* w, int cout, int cin, int taps, uint8_t* out, int64_t out_bytes);
 /* NHWC convolution: y = act(conv(x, w) * scale + bias [+ residual]).
  * x [B,H,W,Cin], w [Cout,KH,KW,Cin], scale/bias [Cout] (NULL = 1 / 0), residual [B,Ho>>rs,Wo>>rs,Cout]
  * (rs = res_shift: 1 = nearest-2x upsampled add, the FPN top-down path), y [B,Ho,Wo,Cout].

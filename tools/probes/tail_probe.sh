@@ -1,4 +1,5 @@
 # bash tools/probes/tail_probe.sh [fp16|fp32]: bottleneck_tail_kernel on the res2 shape — product build and the two ablation builds
+# bash tools/probes/tail_probe.sh split|splitmid with DIAGS=1:0: the split form of the fp32 tail (product library), fused / mid-store mode
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 P=${1:-fp16}

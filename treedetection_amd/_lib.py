@@ -90,6 +90,8 @@ SIGNATURES = {
     "td_resize_batch_u8": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                      C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
     "td_bottleneck_tail_nhwc": (C.c_int, [C.c_void_p] * 9 + [C.c_int] * 6 + [C.c_void_p]),
+    "td_bottleneck_tail_split_nhwc": (C.c_int, [C.c_void_p] * 10 + [C.c_int] * 5 + [C.c_void_p]),
+    "td_conv_split_pack": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64]),
     "td_resize_bilinear_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p]),
     "td_windows_u16_to_input": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                           C.c_int, C.c_int64, C.c_int64, C.c_void_p]),

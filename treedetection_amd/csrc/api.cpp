@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 // (td_set_error / td_last_error: error.cpp — shared with the host-only sanitizer build)
@@ -222,6 +223,45 @@ td_status td_bottleneck_tail_nhwc(const void* x, const void* w2, const float* sc
     a.x = x; a.w2 = w2; a.scale2 = scale2; a.bias2 = bias2; a.w3 = w3; a.scale3 = scale3; a.bias3 = bias3; a.res = shortcut; a.y = y;
     a.B = B; a.H = H; a.W = W; a.MID = mid; a.COUT = cout; a.M = B * H * W;
     return bottleneck_tail_launch(a, precision, static_cast<hipStream_t>(stream));
+}
+
+td_status td_bottleneck_tail_split_nhwc(const void* x, const void* w2, const float* scale2, const float* bias2, const void* w3,
+                                        const float* scale3, const float* bias3, const void* shortcut, void* y, void* mid_out,
+                                        int B, int H, int W, int mid, int cout, void* stream) {
+    TD_REQUIRE(x && w2 && B > 0 && H > 0 && W > 0, "td_bottleneck_tail_split_nhwc: null argument or empty tensor");
+    TD_REQUIRE(mid_out || (w3 && shortcut && y), "td_bottleneck_tail_split_nhwc: the fused launch needs w3, shortcut and y");
+    TD_REQUIRE(bottleneck_tail_split_ok(TD_PRECISION_FP32, mid, cout, (long long)B * H * W), "td_bottleneck_tail_split_nhwc: mid 64, cout 256, output below 4 GB");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // tests: conv2's bank is split here from the caller's fp32 [mid][3][3][mid] filters (the engine splits once at load time)
+    const size_t n = (size_t)mid * 9 * mid;
+    std::vector<float> wh(n);
+    std::vector<unsigned char> packed;
+    TD_HIP_CHECK(hipStreamSynchronize(s));
+    TD_HIP_CHECK(hipMemcpy(wh.data(), w2, n * sizeof(float), hipMemcpyDeviceToHost));
+    conv_split_pack(wh.data(), mid, mid, packed, 9);
+    void* ws = nullptr;
+    td_status st = scratch(&ws, packed.size());
+    if (st < 0) return st;
+    hipError_t herr = hipMemcpy(ws, packed.data(), packed.size(), hipMemcpyHostToDevice);
+    TailArgs a{};
+    a.x = x; a.w2 = w2; a.w2_split = ws; a.scale2 = scale2; a.bias2 = bias2; a.B = B; a.H = H; a.W = W; a.MID = mid; a.COUT = cout; a.M = B * H * W;
+    if (mid_out) a.mid_out = static_cast<float*>(mid_out);
+    else { a.w3 = w3; a.scale3 = scale3; a.bias3 = bias3; a.res = shortcut; a.y = y; }
+    if (herr == hipSuccess) st = bottleneck_tail_launch(a, TD_PRECISION_FP32, s);
+    hipError_t herr2 = hipStreamSynchronize(s);
+    (void)hipFree(ws);
+    if (st < 0) return st;
+    TD_HIP_CHECK(herr);
+    TD_HIP_CHECK(herr2);
+    return TD_OK;
+}
+
+int64_t td_conv_split_pack(const float* w, int cout, int cin, int taps, uint8_t* out, int64_t out_bytes) {
+    TD_REQUIRE(w && cout >= 1 && cin >= 32 && cin % 32 == 0 && taps >= 1 && taps <= 64, "td_conv_split_pack: cout >= 1, cin a multiple of 32, 1 <= taps <= 64");
+    std::vector<unsigned char> packed;
+    conv_split_pack(w, cout, cin, packed, taps);
+    if (out && out_bytes >= (int64_t)packed.size()) memcpy(out, packed.data(), packed.size());
+    return (int64_t)packed.size();
 }
 
 td_status td_resize_bilinear_f64(const double* src, int c, int h, int w, float* dst, int out_h, int out_w, int dst_pitch_px,

@@ -16,6 +16,23 @@
 // all engine-level parity statements carry over unchanged.
 // HBM traffic per block of a stage: t1 (read, halo through L2) + shortcut (read) + y (write) instead of those plus one write
 // and one read of the mid tensor; one launch instead of two.
+//
+// The split form (template parameter SPLIT; fp32, mid 64, 64-row blocks: what the fp32 engine runs in res2 by default, engine.cpp
+// f32_split_tail). Phase 1 is 0.63 of the fp32 tail's launch and MFMA-bound; phases 2 / 3 move the shortcut and the output and are
+// memory-bound. So only the 3x3 changes pipe: both operands as three bf16 pieces, six piece products per 16 k on
+// v_mfma_f32_32x32x16_bf16 (conv_split.hip's split8, piece order and product order), fp32 accumulators; conv2's bank is split once on
+// the host (conv_split_pack with taps = 9, 221 KB per block) and read as fragments straight into registers. Activations are split at
+// the fragment read; a wave owns 32 rows x ALL 64 mid channels so that one split feeds two column tiles (3.7 split instructions
+// per MFMA; the 2 x 2 layout's 32 x 32 wave tile would need 7.3 and be VALU-bound), and the block's four waves divide the rows in
+// two and the input's two channel chunks in two. k order: per wave its chunk's nine taps ascending, slices ascending, the six
+// products smallest first; then ONE fp32 addition S(chunk 0) + S(chunk 1) through LDS — commutative, so the value of a pixel does not
+// depend on where it falls in a block. Behind that addition a wave holds the 32 x 32 tile the fp32 form holds, and phases 2 and 3
+// are the fp32 form's code: scale / bias / ReLU, the mid tile in LDS, the fp32 1x1 with streamed filters, the wave-private epilogue.
+// Its twin: the same kernel with TailArgs::mid_out stops behind phase 2 and stores the mid tile as the [row][64] fp32 tensor (rows
+// below M only). "Fused" = "mid-store launch, then the fp32 1x1 launch with shortcut" bit for bit, by the argument above: the mid
+// values are the same registers, and phase 3 is bit-identical to conv2d_launch(1x1 + residual) as it always was
+// (tests/test_tail_split_gpu.py). NOT bit-identical to the fp32 form (another rounding of the 3x3, inside the same float64 bound).
+// 139 VGPRs, 49 152 B of LDS, no scratch, three blocks per CU like the fp32 form (profiles/f32_split_tail.txt).
 #include "common.h"
 #include "conv_tiles.h"
 #include <cstdlib>
@@ -58,9 +75,10 @@ struct TailGeom {
 
 // The body is a __device__ function (the __global__ entry below only owns the LDS array): with the staging lambdas called
 // straight from a __global__ template, hipcc (ROCm 7.2) silently dropped the kernel's HOST stub from the object file.
-template <typename T, int MID, bool OVERLAP, int MT, bool FAST>
+template <typename T, int MID, bool OVERLAP, int MT, bool FAST, bool SPLIT = false>
 __device__ __forceinline__ void bottleneck_tail_body(const TailArgs& a, char* lds) {
     typedef TailGeom<T, MID, OVERLAP, MT, FAST> G;
+    static_assert(!SPLIT || (FAST && sizeof(T) == 4 && MID == 64 && MT == 1), "the split form is the fp32 64-row tail's");
     constexpr int ES = G::ES, KE = G::KE, KC = G::KC, BM = G::BM, LDROWS = G::LDROWS, NT1 = G::NT1;
     constexpr int AROWS = BM / LDROWS, BROWS1 = MID / LDROWS, BROWS3 = 128 / LDROWS;
     char* As = lds;                                   // phase 1: [2][BM][128 B]
@@ -179,6 +197,94 @@ __device__ __forceinline__ void bottleneck_tail_body(const TailArgs& a, char* ld
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc2[i][j][r] = 0.f;
 
+    [[maybe_unused]] bool mid_only = false;            // split form: the unfused twin (stop behind phase 2, store the mid tile)
+    if constexpr (SPLIT) mid_only = a.mid_out != nullptr;
+    if constexpr (SPLIT) {
+        // ---- phase 1, split form: the 3x3 on v_mfma_f32_32x32x16_bf16, both operands as three bf16 pieces (conv_split.hip) ----
+        // Wave (wm, wk = wn) owns rows 32 wm .. + 31, ALL 64 mid channels (two 32-column tiles: one split of a row fragment feeds
+        // 12 MFMAs) and channel chunk wk of the input: k order per wave = its chunk's nine taps ascending, the two 16-k slices of
+        // a tap ascending, the six piece products of a slice in conv_split_kernel's order (p0q2, p2q0, p1q1, p0q1, p1q0, p0q0).
+        // The two chunk sums of an output meet once, through LDS: mid = S(chunk 0) + S(chunk 1), one fp32 addition — after
+        // it wave (wm, wn) holds the 32 x 32 tile phase 2 expects, so phases 2 and 3 are the fp32 tail's, instruction for instruction.
+        // One barrier per TAP (both chunks of the block's rows staged together: [2 bufs][chunk][64 rows][128 B], the region of
+        // the fp32 form's stages); the filters never touch LDS: each wave reads its fragments (1 KB per wave instruction,
+        // [32-column tile][chunk * 9 + tap][slice][piece][lane][8 bf16]) one slice ahead into two register sets.
+        // Padding taps and rows past M are OOB rows = zeros in LDS = three zero pieces: exact zeros.
+        const int wk = wn;
+        const __amdgpu_buffer_rsrc_t wsrsrc = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<void*>(a.w2_split), 0, (MID / 32) * 9 * KC * SPLIT_CHUNK_BYTES, 0x00020000);
+        unsigned ws_off[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) ws_off[j] = (unsigned)((j * KC + wk) * 9) * (unsigned)SPLIT_CHUNK_BYTES + (unsigned)lane * 16u;
+        auto stage_s = [&](int buf, int tap) {
+            const int ky = tap / 3, kx = tap - 3 * ky;
+            const unsigned xs = (unsigned)(ky * a.W + kx) * pix_bytes;
+#pragma unroll
+            for (int cc = 0; cc < KC; ++cc)
+#pragma unroll
+                for (int i = 0; i < AROWS; ++i) {
+                    const unsigned off = ((a_ok[i] >> tap) & 1u) ? a_off[i] + xs + (unsigned)cc * CHUNK_BYTES : OOB;
+                    char* dst = As + (((unsigned)buf * KC + (unsigned)cc) * BM + (unsigned)LDROWS * i + wave_rows) * CHUNK_BYTES;
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(xrsrc, (lds_void*)dst, 16, off, 0, 0, 0);
+                }
+        };
+        // (the lane's part of the address is loop-invariant, the tap's and the piece's part is a scalar offset: no VALU work per load)
+        auto load_f = [&](f32x4 (&f)[2][3], int tap, int sl) {     // the three pieces of both column tiles, slice sl of this wave's k-chunk `tap` < 9
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int q = 0; q < 3; ++q)
+                    f[j][q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                        wsrsrc, ws_off[j], tap * SPLIT_CHUNK_BYTES + (3 * sl + q) * 1024, 0));
+        };
+        auto mma6 = [&](const bf16x8 (&pa)[3], const f32x4 (&f)[2][3], f32x16 (&acc)[2]) {
+            constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, QB[6] = {2, 0, 1, 1, 0, 0};
+#pragma unroll
+            for (int t = 0; t < 6; ++t)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa[PA[t]], __builtin_bit_cast(bf16x8, f[j][QB[t]]), acc[j], 0, 0, 0);
+        };
+        f32x16 accs[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) accs[j][r] = 0.f;
+        f32x4 fb[2][2][3];
+        stage_s(0, 0);
+        load_f(fb[0], 0, 0);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        for (int tap = 0; tap < 9; ++tap) {
+            const int cur = tap & 1;
+            load_f(fb[1], tap, 1);                     // ahead of the rows in the in-order queue: the wait for it does not include them
+            if (tap + 1 < 9) stage_s(cur ^ 1, tap + 1);
+            const char* Ab = As + ((cur * KC + wk) * BM + wm * 32) * CHUNK_BYTES;
+            bf16x8 pa[2][3];
+#pragma unroll
+            for (int sl = 0; sl < 2; ++sl)
+                split8(*reinterpret_cast<const f32x4*>(Ab + frag_off[2 * sl]), *reinterpret_cast<const f32x4*>(Ab + frag_off[2 * sl + 1]), pa[sl]);
+            mma6(pa[0], fb[0], accs);
+            if (tap + 1 < 9) load_f(fb[0], tap + 1, 0);
+            mma6(pa[1], fb[1], accs);
+            // the next tap's rows have landed: all but the six filter loads behind them in the in-order queue (hipcc waits for
+            // those where the next tap multiplies them); the last tap has neither: its wait is for nothing younger than fb[1]
+            asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // this wave's fragment reads of buf[cur] are done
+            __builtin_amdgcn_s_barrier();
+        }
+        // the two chunk sums meet: each wave hands the column tile it does not keep to its partner (wave ^ 1) through the mid tile's
+        // region (16 KB, written by phase 2 only behind the second barrier), in the accumulator layout: conflict-free both ways
+        float* X = reinterpret_cast<float*>(T2s);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) X[wave * 1024 + r * 64 + lane] = wk ? accs[0][r] : accs[1][r];
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc2[0][0][r] = __fadd_rn(wk ? accs[1][r] : accs[0][r], X[(wave ^ 1) * 1024 + r * 64 + lane]);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+    } else {
 #if defined(TD_TAIL_DIAG) && (TD_TAIL_DIAG & 1)      // timing builds only (tools/tail_probe.py): no phase 1 (the 3x3)
     if (false)
 #endif
@@ -212,6 +318,7 @@ __device__ __forceinline__ void bottleneck_tail_body(const TailArgs& a, char* ld
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // this wave's fragment reads of buf[cur] are done
         __builtin_amdgcn_s_barrier();
     }
+    }
 
     // ---- the 1x1's filters of output piece `nc` (128 channels x MID): KC pieces of [128 rows][128 B] -------------------------
     auto stage_w3 = [&](int nc) {
@@ -225,7 +332,7 @@ __device__ __forceinline__ void bottleneck_tail_body(const TailArgs& a, char* ld
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(w3rsrc, (lds_void*)dst, 16, off, 0, 0, 0);
             }
     };
-    stage_w3(0);                                       // the phase-1 stages are free (barrier above); lands under phase 2
+    if (!mid_only) stage_w3(0);                        // the phase-1 stages are free (barrier above); lands under phase 2
 
     // FAST: the shortcut rows this lane finishes (8 channels = 16 B of 4 rows per 128-channel piece) are requested here, two
     // pieces ahead of their use — behind the filters in the queue, so that the counted wait below does not include them.
@@ -298,6 +405,9 @@ __device__ __forceinline__ void bottleneck_tail_body(const TailArgs& a, char* ld
                     t = t > 0.f ? t : 0.f;
                     const unsigned row = (unsigned)(wm * 32 * MT + i * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5));
                     *reinterpret_cast<float*>(T2s + (c * BM + row) * CHUNK_BYTES + ((piece ^ ((row >> 1) & 7)) << 4) + inb) = t;
+                    if constexpr (SPLIT) {
+                        if (mid_only && m0 + (int)row < M) a.mid_out[(size_t)(m0 + (int)row) * MID + n] = t;
+                    }
                 }
             } else {
                 // fp16: neighbouring lanes hold neighbouring channels of the same rows — swap one value (DPP quad_perm) so that
@@ -331,6 +441,9 @@ __device__ __forceinline__ void bottleneck_tail_body(const TailArgs& a, char* ld
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     }
     __builtin_amdgcn_s_barrier();                      // mid tile visible to every wave, filters of piece 0 landed
+    if constexpr (SPLIT) {
+        if (mid_only) return;                          // the unfused twin: the mid tensor is in memory, the 1x1 is a launch of its own
+    }
 
 #if defined(TD_TAIL_DIAG) && (TD_TAIL_DIAG & 2)      // timing builds only: stop after phase 2 (no 1x1, no epilogue)
     if (tid == 0 && m0 == 0x7fffff00) static_cast<T*>(a.y)[0] = *reinterpret_cast<const T*>(T2s);
@@ -577,19 +690,19 @@ __device__ __forceinline__ void bottleneck_tail_body(const TailArgs& a, char* ld
 }
 
 // BPC = blocks per CU the LDS footprint allows (__launch_bounds__' second argument is waves per SIMD = BPC for 4-wave blocks)
-template <typename T, int MID, bool OVERLAP, int MT, bool FAST, int BPC>
+template <typename T, int MID, bool OVERLAP, int MT, bool FAST, int BPC, bool SPLIT = false>
 __global__ __launch_bounds__(256, BPC)
 void bottleneck_tail_kernel(const TailArgs a) {
     static_assert(BPC >= 1 && BPC * TailGeom<T, MID, OVERLAP, MT, FAST>::LDS_BYTES <= 160 * 1024, "LDS footprint does not allow that many blocks per CU");
     __shared__ __attribute__((aligned(16))) char lds[TailGeom<T, MID, OVERLAP, MT, FAST>::LDS_BYTES];
-    bottleneck_tail_body<T, MID, OVERLAP, MT, FAST>(a, lds);
+    bottleneck_tail_body<T, MID, OVERLAP, MT, FAST, SPLIT>(a, lds);
 }
 
-template <typename T, int MID, bool OVERLAP, int MT, bool FAST = false>
+template <typename T, int MID, bool OVERLAP, int MT, bool FAST = false, bool SPLIT = false>
 td_status launch_tail(const TailArgs& a, hipStream_t stream) {
     typedef TailGeom<T, MID, OVERLAP, MT, FAST> G;
     const int tiles = td_cdiv(a.M, G::BM);
-    hipLaunchKernelGGL((bottleneck_tail_kernel<T, MID, OVERLAP, MT, FAST, G::BPC>), dim3(tiles), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL((bottleneck_tail_kernel<T, MID, OVERLAP, MT, FAST, G::BPC, SPLIT>), dim3(tiles), dim3(256), 0, stream, a);
     TD_KERNEL_CHECK();
     return TD_OK;
 }
@@ -602,11 +715,22 @@ bool bottleneck_tail_ok(int precision, int mid, int cout) {
     return mid == 64 || mid == 128;
 }
 
+// the split form's shapes: the fp32 64-row tail with the wave-private epilogue (32-bit buffer offsets into the shortcut / output)
+bool bottleneck_tail_split_ok(int precision, int mid, int cout, long long M) {
+    return precision == TD_PRECISION_FP32 && mid == 64 && cout == 4 * mid && M > 0 && (size_t)M * cout * 4 < 0xfffffff0ull - (1u << 20);
+}
+
 td_status bottleneck_tail_launch(const TailArgs& a, int precision, hipStream_t stream) {
     TD_REQUIRE(bottleneck_tail_ok(precision, a.MID, a.COUT), "bottleneck tail: unsupported shape (precision %d, mid %d, out %d)", precision, a.MID, a.COUT);
     TD_REQUIRE(a.M == a.B * a.H * a.W && a.M > 0, "bottleneck tail: M must be B*H*W");
     const size_t es = precision == TD_PRECISION_FP16 ? 2 : 4;
     TD_REQUIRE((size_t)a.M * a.MID * es < 0xfffffff0ull - (1u << 20), "bottleneck tail: input tensor must stay below 4 GB (32-bit buffer offsets)");
+    if (a.w2_split) {
+        TD_REQUIRE(bottleneck_tail_split_ok(precision, a.MID, a.COUT, a.M), "bottleneck tail: the split form runs fp32, mid 64, outputs below 4 GB");
+        TD_REQUIRE(a.mid_out || (a.w3 && a.y), "bottleneck tail: the split form needs the 1x1's filters and an output, or mid_out");
+        return launch_tail<float, 64, false, 1, true, true>(a, stream);
+    }
+    TD_REQUIRE(!a.mid_out, "bottleneck tail: mid_out is the split form's (w2_split)");
     // rows per block: 64 (three or four blocks per CU: more independent latency chains in flight) or 128 (half the filter
     // re-reads); TD_TAIL_BM picks for experiments, the default is what measured faster per shape (profiles/)
     static const int forced = getenv("TD_TAIL_BM") ? atoi(getenv("TD_TAIL_BM")) : 0;

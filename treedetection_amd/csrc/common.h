@@ -168,7 +168,8 @@ td_status conv_bd_launch(const ConvArgs& a, int precision, int variant, hipStrea
 bool conv_bs_ok(const ConvArgs& a, int precision);
 td_status conv_bs_launch(const ConvArgs& a, int precision, hipStream_t stream);
 // split-bf16 form (conv_split.hip, tile ids 34 - 37): w [cout][cin] fp32 → the three-piece fragment bank (6 bytes per weight)
-void conv_split_pack(const float* w, int cout, int cin, std::vector<unsigned char>& out);
+// (taps = 9 with w [cout][3][3][cin]: the 3x3 bank of the split bottleneck tail, k-chunks channel chunk outer / tap inner)
+void conv_split_pack(const float* w, int cout, int cin, std::vector<unsigned char>& out, int taps = 1);
 bool conv_split_ok(const ConvArgs& a, int precision);
 td_status conv_split_launch(const ConvArgs& a, int variant, hipStream_t stream);
 td_status wino_gemm_launch(const ConvArgs& a, hipStream_t stream);     // Winograd plane contractions, input transform fused (fp32)
@@ -185,8 +186,14 @@ struct TailArgs {
     const void* res;      // NHWC [B,H,W,COUT]: the block's shortcut (same size)
     void* y;              // NHWC [B,H,W,COUT]
     int B, H, W, MID, COUT, M;
+    // the split form (fp32, MID 64): conv2's bank as three bf16 pieces per weight (conv_split_pack with taps = 9); the 3x3 then runs
+    // on the bf16 matrix cores, the 1x1 as before. mid_out set = the unfused twin: the launch stops behind phase 2 and stores the
+    // mid tile as the [M][MID] fp32 tensor (w3 / scale3 / bias3 / res / y unused).
+    const void* w2_split;
+    float* mid_out;
 };
 bool bottleneck_tail_ok(int precision, int mid, int cout);          // shapes the fused kernel is built for
+bool bottleneck_tail_split_ok(int precision, int mid, int cout, long long M);      // ... and its split form (TailArgs::w2_split)
 td_status bottleneck_tail_launch(const TailArgs& a, int precision, hipStream_t stream);
 
 // ---- Winograd F(2x2,3x3) transforms (winograd.hip; fp32 engine) ---------------------------------

@@ -37,6 +37,8 @@
 // epilogue's 128 x 260 floats. Its step states the order of its instructions (PACED, below): that, not the bytes, is what it gains by —
 // the 2 x 2 form already shared the fragments through the vector L1 (profiles/f32_split_tall.txt: same L2 requests, 1 047 us on fc1;
 // this form 1 015 us as hipcc orders it, 857 us paced, the 64 x 256 tile 904 - 949 us).
+// The 3x3 of res2 (64 -> 64) runs the same arithmetic inside the fused bottleneck tail, not here: bottleneck.hip's split form uses
+// split8 (conv_tiles.h), this piece and product order and conv_split_pack with taps = 9; no 3x3 form of conv_split_kernel exists.
 // Measured (profiles/f32_split.txt, batch 8): fc1 (8000 x 1024 x 12544) 1 549 -> 900 us = 228 TFLOP/s, fc2 137 -> 89 us. conv1 and the
 // shortcuts of res3 - res5 and the FPN laterals (8 - 64 k-chunks per block; profiles/f32_split_backbone.txt): 2.41 -> 1.95 ms in the layer
 // table, headline 697.6 -> 726.2 tiles/s: on by default with the box head (engine.cpp SPLIT_DEFAULT); conv3 ties on its fp32 tiles: off.
@@ -46,36 +48,11 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int SPLIT_CHUNK_BYTES = 6144;      // one 32-column tile x one k-chunk of the split bank: 2 slices x 3 pieces x 1 KB
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));      // (the piece types, SPLIT_CHUNK_BYTES and split8: conv_tiles.h)
 
 template <int... R, class F>
 __device__ __forceinline__ void static_for(std::integer_sequence<int, R...>, F&& f) {
     (f(std::integral_constant<int, R>{}), ...);
-}
-
-// 8 floats (two 16-B pieces of an LDS row) → three bf16x8 pieces, p[0] the leading one
-__device__ __forceinline__ void split8(const f32x4& lo, const f32x4& hi, bf16x8 (&p)[3]) {
-    u32x4 w[3];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        f32x2 v = e < 2 ? f32x2{lo[2 * e], lo[2 * e + 1]} : f32x2{hi[2 * e - 4], hi[2 * e - 3]};
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const unsigned u = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));      // round to nearest even
-            w[k][e] = u;
-            if (k < 2) {
-                const f32x2 back = {__builtin_bit_cast(float, u << 16), __builtin_bit_cast(float, u & 0xffff0000u)};
-                v = v - back;                         // exact
-            }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) p[k] = __builtin_bit_cast(bf16x8, w[k]);
 }
 
 template <int MT, int NT, int WM, int WN>
@@ -345,8 +322,10 @@ inline unsigned short bf16_rne(float f) {
 // Lane l = (r = l & 31, h = l >> 5) of (tile t, chunk c, slice s, piece p) holds piece p of the eight weights
 // W[t*32 + r][c*32 + 16 s + 4 h .. + 3] and W[t*32 + r][c*32 + 16 s + 8 + 4 h .. + 3] — the floats the kernel's A-fragment reads hand
 // that lane; columns past Cout are zero.
-void conv_split_pack(const float* w, int cout, int cin, std::vector<unsigned char>& out) {
-    const int nit = cin / 32, nt32 = (cout + 31) / 32;
+// taps > 1 (the 3x3 bank [Cout][taps][Cin] of the split tail, bottleneck.hip): taps * Cin/32 k-chunks, channel chunk outer and
+// filter tap inner — k-chunk c = cc * taps + tap holds W[n][tap][cc*32 ..], the order in which that kernel's waves walk them.
+void conv_split_pack(const float* w, int cout, int cin, std::vector<unsigned char>& out, int taps) {
+    const int nit = taps * (cin / 32), nt32 = (cout + 31) / 32;
     out.assign((size_t)nt32 * nit * SPLIT_CHUNK_BYTES, (unsigned char)0);
     unsigned short* o = reinterpret_cast<unsigned short*>(out.data());
     for (int t = 0; t < nt32; ++t)
@@ -355,8 +334,9 @@ void conv_split_pack(const float* w, int cout, int cin, std::vector<unsigned cha
                 for (int l = 0; l < 64; ++l) {
                     const int n = t * 32 + (l & 31), h = l >> 5;
                     if (n >= cout) continue;
+                    const int cc = c / taps, tap = c - cc * taps;
                     for (int e = 0; e < 8; ++e) {
-                        float v = w[(size_t)n * cin + (size_t)c * 32 + 16 * s + 8 * (e >> 2) + 4 * h + (e & 3)];
+                        float v = w[((size_t)n * taps + tap) * cin + (size_t)cc * 32 + 16 * s + 8 * (e >> 2) + 4 * h + (e & 3)];
                         for (int p = 0; p < 3; ++p) {
                             const unsigned short b = bf16_rne(v);
                             o[(((((size_t)t * nit + c) * 2 + s) * 3 + p) * 64 + l) * 8 + e] = b;

@@ -62,6 +62,34 @@ struct Elem<_Float16> {
     static __device__ __forceinline__ float to_f32(_Float16 v) { return (float)v; }
 };
 
+// ---- split-bf16 operands (conv_split.hip, the split tail of bottleneck.hip) ---------------------------------------------
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+constexpr int SPLIT_CHUNK_BYTES = 6144;      // one 32-column tile x one k-chunk of a split bank: 2 slices x 3 pieces x 1 KB
+
+// 8 floats (two 16-B pieces of an LDS row) → three bf16x8 pieces, p[0] the leading one
+__device__ __forceinline__ void split8(const f32x4& lo, const f32x4& hi, bf16x8 (&p)[3]) {
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    u32x4 w[3];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        f32x2 v = e < 2 ? f32x2{lo[2 * e], lo[2 * e + 1]} : f32x2{hi[2 * e - 4], hi[2 * e - 3]};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const unsigned u = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));      // round to nearest even
+            w[k][e] = u;
+            if (k < 2) {
+                const f32x2 back = {__builtin_bit_cast(float, u << 16), __builtin_bit_cast(float, u & 0xffff0000u)};
+                v = v - back;                         // exact
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) p[k] = __builtin_bit_cast(bf16x8, w[k]);
+}
+
 // ---- epilogue ---------------------------------------------------------------------------------------------------------
 // y = act(acc * scale + bias (+ residual)), one IEEE op per step (no fma contraction), identical in both paths below.
 // The MFMA layout (a lane = one column, 16 scattered rows of a 32 x 32 tile) is turned into whole row segments through

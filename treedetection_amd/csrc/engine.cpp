@@ -45,6 +45,8 @@ struct ConvLayer {
     void* w_frag = nullptr;   // fp16 engine: the filters in MFMA fragment order (conv_bdirect.hip), layers with cin % 64 == 0
     void* w_split = nullptr;  // fp32 engine, the layers of the split rule (td_engine::f32_split): three bf16 pieces per weight in fragment
                               // order (conv_split.hip); a layer that has it runs the TILE_SPLIT ids and nothing else
+    void* w_tail_split = nullptr;   // fp32 engine, conv2 of the res2 blocks (td_engine::f32_split_tail): the 3x3 bank as three bf16 pieces per weight
+                              // in the split tail's fragment order (bottleneck.hip). Not w_split: the layer is no conv_path SPLIT layer
     float* wino_u = nullptr;  // fp32 engine, 3x3 layers: Winograd-transformed filters U [16][cout][cin] (winograd.hip)
     float* wino_u43 = nullptr;  // the same for F(4x4,3x3): U [36][cout][cin] (layers with >= 128 channels on both sides)
 };
@@ -121,12 +123,20 @@ struct td_engine : Workspace {          // (the workspace pointers: workspace.h)
     // fp32 engine: the 1x1 / FC layers that run on the bf16 matrix cores with both operands as three bf16 pieces (conv_split.hip:
     // its own rounding, so a FIXED rule on the layer — its place in the network and K >= 256 —, never a timing). Bit mask of layer
     // classes (TD_F32_SPLIT; 0 = none, for an A/B on one build): SPLIT_FC the box head's fc1 / fc2, SPLIT_LATERAL the four FPN
-    // laterals, SPLIT_CONV1 / SPLIT_CONV3 / SPLIT_SHORTCUT the 1x1 layers of res3 - res5. Never: layers that also exist inside a
-    // fused kernel or have a bit-identity twin (res2, the RPN head, the box and mask predictors), K < 256, the fp16 engine.
+    // laterals, SPLIT_CONV1 / SPLIT_CONV3 / SPLIT_SHORTCUT the 1x1 layers of res3 - res5. Never through this rule: layers that also
+    // exist inside a fused kernel or have a bit-identity twin (the RPN head, the box and mask predictors; res2: its 3x3 has a rule of
+    // its own, f32_split_tail below), K < 256, the fp16 engine.
     // The default is the box head, the FPN laterals, conv1 and the shortcuts (23): the classes whose gain on the headline was
     // measured (profiles/f32_split.txt, profiles/f32_split_backbone.txt). conv3 stays off: res4 ties or loses in the per-layer table.
     // Cost: the split banks, 6 B per weight, about 48 MB per fp32 engine beside the fp32 filters.
     int f32_split = SPLIT_DEFAULT;
+    // fp32 engine: conv2 (3x3, 64 -> 64) of the res2 blocks on the bf16 matrix cores the same way, inside the fused tail
+    // (bottleneck.hip, the split form; the 1x1 behind it stays on the fp32 MFMA: it is memory-bound). A switch of its own
+    // (TD_F32_SPLIT_TAIL, default 1; 0 = the fp32 tail), not a bit of f32_split, and like it a FIXED rule on the layer, never a timing:
+    // no tile is chosen, nothing is written to the tune cache. The bit-identity twin of the fused launch is kept by construction:
+    // with TD_FUSE_TAIL=0 conv2 runs as the SAME kernel's mid-store launch (it stops behind phase 2 and writes t2) and conv3 as the
+    // fp32 1x1 launch it always was, which the fused kernel's phase 3 equals bit for bit. Cost: 221 KB per block, +0.66 MB per engine.
+    bool f32_split_tail = true;
     std::string tune_cache;       // TD_TUNE_CACHE: load / append measured choices (keeps profiled runs free of tuning launches)
     // The tuner times every candidate tile with the L2 (8 x 4 MB) emptied before each launch (a fill of this scratch on the same
     // stream): in the forward a layer's filters and most of its input are NOT in L2 — 50-odd other launches ran since — and a loop of
@@ -240,6 +250,20 @@ td_status upload_split(td_engine* e, const std::vector<float>& h, ConvLayer& L, 
     unsigned char* d = nullptr;
     td_status st = upload(e, packed, &d);
     L.w_split = d;
+    return st;
+}
+
+// the split tail's bank of a res2 conv2 (3x3, 64 -> 64 in front of a 64 -> 256 conv3) when the rule is on: fp32 engine only
+td_status upload_tail_split(td_engine* e, const std::vector<float>& w_ohwi, ConvLayer& L, int cout3) {
+    L.w_tail_split = nullptr;
+    if (!e->f32_split_tail || L.kh != 3 || L.kw != 3 || L.cin != L.cout || !bottleneck_tail_split_ok(e->desc.precision, L.cout, cout3, 1) ||
+        (size_t)L.cout * 9 * L.cin != w_ohwi.size())
+        return TD_OK;
+    std::vector<unsigned char> packed;
+    conv_split_pack(w_ohwi.data(), L.cout, L.cin, packed, 9);
+    unsigned char* d = nullptr;
+    td_status st = upload(e, packed, &d);
+    L.w_tail_split = d;
     return st;
 }
 
@@ -493,6 +517,7 @@ td_status td_engine_create(const td_model_desc* desc, int device, td_engine** ou
     if (const char* gl = getenv("TD_GROUP_LEVELS")) e->group_levels = atoi(gl) != 0;
     if (const char* ft = getenv("TD_FUSE_TAIL")) { e->fuse_tail = atoi(ft) != 0; e->fuse_tail_fp16 = atoi(ft) == 2; }
     if (const char* sp = getenv("TD_F32_SPLIT")) e->f32_split = atoi(sp);
+    if (const char* spt = getenv("TD_F32_SPLIT_TAIL")) e->f32_split_tail = atoi(spt) != 0;
     e->desc = d;
     read_rule_switches(e);
     load_tune_cache(e);
@@ -591,10 +616,12 @@ td_status td_engine_load_weights(td_engine* e, const td_tensor_desc* tensors, si
             if (tm.find(p + ".conv1.weight") == tm.end()) break;
             Block blk;
             blk.stride = (bi == 0 && si > 0) ? 2 : 1;
-            // (the split rule: res3 - res5 only — conv2 / conv3 of res2 also exist inside bottleneck_tail_kernel)
+            // (the split rule: res3 - res5 only — conv2 / conv3 of res2 also exist inside bottleneck_tail_kernel; its conv2 takes the
+            // split tail's bank below)
             if ((st = load_conv_bn(e, tm, p + ".conv1", blk.c1, si > 0 ? SPLIT_CONV1 : 0)) < 0) return st;
             if ((st = load_conv_bn(e, tm, p + ".conv2", blk.c2)) < 0) return st;
             if ((st = load_conv_bn(e, tm, p + ".conv3", blk.c3, si > 0 ? SPLIT_CONV3 : 0)) < 0) return st;
+            if (si == 0 && (st = upload_tail_split(e, pack_ohwi(tm.at(p + ".conv2.weight")), blk.c2, blk.c3.cout)) < 0) return st;
             blk.has_sc = tm.find(p + ".shortcut.weight") != tm.end();
             if (blk.has_sc && (st = load_conv_bn(e, tm, p + ".shortcut", blk.sc, si > 0 ? SPLIT_SHORTCUT : 0)) < 0) return st;
             e->stages[si].push_back(blk);
@@ -1005,22 +1032,38 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
         return conv_pp8_grouped_launch(a, s_);
     };
     // conv2 (3x3) → conv3 (1x1) + shortcut + ReLU of a bottleneck block as one launch (bottleneck_tail_kernel)
-    auto run_tail = [&](const Block& blk, const void* t1_, int B_, int H_, int W_, void* y_, const void* shortcut_, hipStream_t s_) -> td_status {
+    // split_ (the res2 blocks of the fp32 engine under f32_split_tail): the 3x3 on the bf16 matrix cores. mid_out_ set: that kernel's
+    // mid-store launch, the unfused twin's conv2 (t2 written, no conv3)
+    auto run_tail = [&](const Block& blk, const void* t1_, int B_, int H_, int W_, void* y_, const void* shortcut_, hipStream_t s_,
+                        bool split_ = false, void* mid_out_ = nullptr) -> td_status {
         TailArgs a{};
         a.x = t1_; a.w2 = blk.c2.w; a.scale2 = blk.c2.scale; a.bias2 = blk.c2.bias;
         a.w3 = blk.c3.w; a.scale3 = blk.c3.scale; a.bias3 = blk.c3.bias; a.res = shortcut_; a.y = y_;
         a.B = B_; a.H = H_; a.W = W_; a.MID = blk.c2.cout; a.COUT = blk.c3.cout; a.M = B_ * H_ * W_;
+        if (split_) a.w2_split = blk.c2.w_tail_split;
         const double M = (double)a.M, mid = a.MID, co = a.COUT, es = prec == TD_PRECISION_FP16 ? 2.0 : 4.0;
-        const double flops = 2.0 * M * mid * (9.0 * mid) + 2.0 * M * co * mid;
-        const double bytes = es * (M * mid + 2.0 * M * co + 9.0 * mid * mid + co * mid);       // t1 in, shortcut in, y out, both filter banks
+        // (the split 3x3: six bf16 MFMAs per 16 k — its pipe time in units of the fp32 rate, as run_conv counts a split layer; its
+        // filters cross as three bf16 pieces: 6 bytes per weight)
+        const double f2 = 2.0 * M * mid * (9.0 * mid), f2pipe = split_ ? f2 * 6.0 / 16.0 : f2, w2b = (split_ ? 6.0 : es) * 9.0 * mid * mid;
+        if (mid_out_) {
+            a.mid_out = static_cast<float*>(mid_out_);
+            a.w3 = nullptr; a.scale3 = nullptr; a.bias3 = nullptr; a.res = nullptr; a.y = nullptr;
+            const double bytes = es * 2.0 * M * mid + w2b;         // t1 in, t2 out, conv2's bank
+            ProfScope ps(e, s_, 0, f2, bytes);
+            if (e->prof) e->prof_flops[8] += f2pipe;
+            ClassScope cs(e, s_, TD_CLS_CONV3X3, f2pipe, bytes);
+            return bottleneck_tail_launch(a, prec, s_);
+        }
+        const double f3 = 2.0 * M * co * mid, flops = f2 + f3;
+        const double bytes = es * (M * mid + 2.0 * M * co + co * mid) + w2b;       // t1 in, shortcut in, y out, both filter banks
         ProfScope ps(e, s_, 0, flops, bytes);
         if (e->prof) {
-            e->prof_flops[8] += flops;
+            e->prof_flops[8] += f2pipe + f3;
             e->prof_launches[0] += 1;          // two layers of the reference in one launch: keep "launches" = layers
             // the unfused pair's algorithmic bytes (what `bytes` of category 0 means: every tensor of every LAYER once)
             e->prof_bytes[0] += es * 2.0 * M * mid;
         }
-        ClassScope cs(e, s_, TD_CLS_TAIL, flops, bytes);
+        ClassScope cs(e, s_, TD_CLS_TAIL, f2pipe + f3, bytes);
         return bottleneck_tail_launch(a, prec, s_);
     };
     // ---- backbone ------------------------------------------------------------------------------------------
@@ -1084,11 +1127,20 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
                 // fp16 res2 130 us against 54 + 87; fp16 res3 111 us against 41 + 47 — slower (a fused block is a chain of short
                 // latency-bound steps, and with 128 mid channels only two blocks fit a CU), so res3 fuses only on request
                 // (TD_FUSE_TAIL=2). Either way the result is bit-identical, so this IS allowed to follow a measurement.
-                if (e->fuse_tail && (blk.c2.cout == 64 || e->fuse_tail_fp16) && blk.c2.kh == 3 && blk.c2.kw == 3 &&
-                    blk.c2.cin == blk.c2.cout && blk.c3.cin == blk.c2.cout && bottleneck_tail_ok(prec, blk.c2.cout, blk.c3.cout)) {
+                // The split tail (f32_split_tail: fp32 engine, res2): a fixed rule on the layer — it has the bank — and the launch's
+                // size; fused or not, conv2 is bottleneck_tail_kernel's split form (the mid-store launch below is the fused launch's
+                // phases 1 and 2), so the two stay bit-identical here too.
+                const bool tail_shape = blk.c2.kh == 3 && blk.c2.kw == 3 && blk.c2.cin == blk.c2.cout && blk.c3.cin == blk.c2.cout &&
+                                        bottleneck_tail_ok(prec, blk.c2.cout, blk.c3.cout);
+                const bool split_tail = tail_shape && blk.c2.w_tail_split &&
+                                        bottleneck_tail_split_ok(prec, blk.c2.cout, blk.c3.cout, (long long)nb_img * oh * ow);
+                if (e->fuse_tail && (blk.c2.cout == 64 || e->fuse_tail_fp16) && tail_shape) {
                     // conv2 + conv3 + shortcut add in one launch, bit-identical to the two launches below (bottleneck.hip); the mid
                     // tensor t2 never reaches HBM
-                    if ((st = run_tail(blk, t1, nb_img, oh, ow, y, shortcut, s)) < 0) return st;
+                    if ((st = run_tail(blk, t1, nb_img, oh, ow, y, shortcut, s, split_tail)) < 0) return st;
+                } else if (split_tail) {
+                    if ((st = run_tail(blk, t1, nb_img, oh, ow, nullptr, nullptr, s, true, t2)) < 0) return st;
+                    if ((st = run_conv(e, blk.c3, t2, nb_img, oh, ow, 1, 0, true, y, shortcut, 0, s)) < 0) return st;
                 } else {
                     if ((st = run_conv(e, blk.c2, t1, nb_img, oh, ow, 1, 1, true, t2, nullptr, 0, s)) < 0) return st;
                     if ((st = run_conv(e, blk.c3, t2, nb_img, oh, ow, 1, 0, true, y, shortcut, 0, s)) < 0) return st;
