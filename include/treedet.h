@@ -275,7 +275,9 @@ td_status td_conv2d_head_nhwc(const void* x, const void* w, const float* bias, c
 /* The same 3x3 / stride 1 / pad 1 convolution (float32) through the Winograd F(2x2,3x3) path the fp32 engine uses where it
  * measures faster (input transform, 16 batched plane contractions on the MFMA kernel, output transform): x [B,H,W,Cin],
  * w [Cout,3,3,Cin], y [B,H,W,Cout] = act(conv * scale + bias), all DEVICE pointers; Cin % 32 == 0, Cout % 4 == 0.
- * Synchronous (allocates its own scratch): parity tests only. */
+ * Synchronous (allocates its own scratch): parity tests only. Test switches of the environment: TD_WINO_TILE=4 the F(4x4,3x3) form,
+ * TD_WINO_FOLD=1 its folded launch, TD_WINO_SPLIT=1 the 36 planes of the unfolded F(4x4) form on the split-bf16 tiles (the twin bank
+ * is packed in scratch; also read by td_conv2d_winograd_head_nhwc), TD_CONV_CFG the block tile of the plane contraction. */
 td_status td_conv2d_winograd_nhwc(const float* x, const float* w, const float* scale, const float* bias, float* y, int B,
                                   int H, int W, int Cin, int Cout, int relu, void* stream);
 /* F(4x4,3x3) form of td_conv2d_head_nhwc for float32 tensors (how the fp32 engine runs the RPN, reference StandardRPNHead behind
@@ -293,6 +295,8 @@ td_status td_conv2d_winograd_head_nhwc(const float* x, const float* w, const flo
  *               Winograd workspace plane (td_engine_reserve: 16 x the largest [tiles of 2x2 outputs] x [channels] of the 3x3
  *               layers, which never runs short for the engine's own layers; 0 for the fp16 engine)
  *   layer[9]  = cout, cin, kh, kw, has a scale, writes float32, and which banks it has: F(2x2) filters, F(4x4) filters, split-bf16
+ *               (of a 3x3 layer with F(4x4) filters: the split-bf16 twin of that bank — form 3 then contracts its 36 planes on the
+ *               split-bf16 tiles where the rows are static, and its tune key carries flag 128 on top of 64)
  *   call[10]  = B, H, W, stride, pad, relu, has a residual, out_mode, device-side row count, rows_mul
  *   head[9]   = the same facts of a 1x1 layer that is this layer's only consumer, or NULL
  *   out[10]   = form (0 direct, 1 split-bf16, 2 Winograd F(2x2), 3 F(4x4) in three launches, 4 F(4x4) folded),

@@ -126,6 +126,8 @@ def main(path, depth=50, fp32=False, B=8, size=800):
                                     kn.split("conv_igemm_")[1].split("(")[0][:28])
         if k == 3:
             assert "wino43_input" in kn and "wino43_output" in rs[2]["Kernel_Name"], (name, kn)
+            if "conv_split" in rs[1]["Kernel_Name"]:       # the 36 planes on the split-bf16 tiles (TD_F32_SPLIT_WINO)
+                kern += " split planes"
             kern += f" [{ts[0]:.0f}+{ts[1]:.0f}+{ts[2]:.0f}]"
         elif k == 2 and label and "folded" in label:
             assert "wino43_input" in kn and "wino43_fused" in rs[1]["Kernel_Name"], (name, kn, rs[1]["Kernel_Name"])

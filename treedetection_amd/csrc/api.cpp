@@ -183,6 +183,20 @@ static td_status wino_api(const float* x, const float* w, const float* scale, co
         return st;
     }
     TD_HIP_CHECK(hipMemcpy(U, uh.data(), uh.size() * 4, hipMemcpyHostToDevice));
+    // tests: TD_WINO_SPLIT=1 contracts the 36 planes of the unfolded F(4x4) form on the split-bf16 tiles; the twin bank is packed
+    // here from U (the engine packs once at load time)
+    const char* spe = getenv("TD_WINO_SPLIT");
+    void* Us = nullptr;
+    auto free_all = [&]() { (void)hipFree(U); (void)hipFree(V); (void)hipFree(Mb); (void)hipFree(Us); };
+    if (f43 && spe && atoi(spe) != 0) {
+        std::vector<unsigned char> packed;
+        conv_split_pack_planes(uh.data(), 36, Cout, Cin, packed);
+        if ((st = scratch(&Us, packed.size())) < 0 || hipMemcpy(Us, packed.data(), packed.size(), hipMemcpyHostToDevice) != hipSuccess) {
+            free_all();
+            if (st < 0) return st;
+            TD_REQUIRE(false, "td_conv2d_winograd_nhwc: copying the split twin of the filter bank failed");
+        }
+    }
     const char* folde = getenv("TD_WINO_FOLD");           // tests: F(4x4) contraction + output transform in one launch (wino_fused.hip)
     const bool fold = f43 && !head_w && folde && atoi(folde) != 0;
     if (fold) TD_REQUIRE(wino43_fused_ok(B, H, W, Cin, Cout), "td_conv2d_winograd_nhwc: TD_WINO_FOLD needs Cin %% 128 == 0, Cout %% 64 == 0");
@@ -192,13 +206,13 @@ static td_status wino_api(const float* x, const float* w, const float* scale, co
     r.form = fold ? CONV_WINO43_FOLD : f43 ? CONV_WINO43 : CONV_WINO22;
     r.fused_input = !fenv || atoi(fenv) != 0;
     r.slab_tiles = (int)T; r.fold_group = B;
-    r.x = x; r.U = static_cast<float*>(U); r.scale = scale; r.bias = bias; r.y = y;
+    r.x = x; r.U = static_cast<float*>(U); r.U_split = Us; r.scale = scale; r.bias = bias; r.y = y;
     r.B = B; r.H = H; r.W = W; r.cin = Cin; r.cout = Cout; r.relu = relu;
     r.V = static_cast<float*>(V); r.M = static_cast<float*>(Mb); r.m_mul = 1; r.gemm_cfg = -1;
     r.head_w = head_w; r.head_b = head_b; r.head_y = head_y; r.head_n = head_n;
     st = wino_run(r, s);
     hipError_t herr = hipStreamSynchronize(s);
-    (void)hipFree(U); (void)hipFree(V); (void)hipFree(Mb);
+    free_all();
     if (st < 0) return st;
     TD_HIP_CHECK(herr);
     return TD_OK;

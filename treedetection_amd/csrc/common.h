@@ -63,6 +63,7 @@ struct ConvArgs {
     long long x_bs, w_bs, y_bs;
     const void* w_frag;   // the same filters in MFMA fragment order (the tiles with ConvTile::frag), or nullptr
     const void* w_split;  // fp32 1x1 / FC filters as three bf16 pieces per weight in fragment order (conv_split_pack; the TILE_SPLIT ids), or nullptr
+                          // (batched: the planes' banks concatenated, and w_bs counts BYTES of one plane's bank — conv_split_bank_bytes)
     int tile_cfg;         // -1 = heuristic; else an id of TD_CONV_TILES (engine autotunes)
     int tile_strict;      // 1: a forced tile_cfg this launch cannot run is an error, not a silent switch to the heuristic tile (tests)
     // fused 1x1 head (fp16 engine, block tiles that own all 256 output channels: ConvTile::head): the finished fp16
@@ -150,6 +151,8 @@ inline constexpr ConvTile TD_CONV_TILES[] = {
     {TILE_SPLIT,   1, TILE_F32, false, false, 22, 0,   0,  0},     // 35: 128x128               and then nothing else is — tuned_cfg filters by family)
     {TILE_SPLIT,   2, TILE_F32, false, false, 23, 0,   0,  0},     // 36: 64x256
     {TILE_SPLIT,   3, TILE_F32, false, false, 24, 0,   0,  0},     // 37: 64x128, 2 waves (the M = 5 000 layers: twice the blocks of 35)
+    // 34 - 37 also run batched launches of plain planes (batch_count > 1, static rows, no residual, w_bs = bytes of one plane's split
+    // bank: the unfolded F(4x4) layers' 36 planes); a batched launch with w_split runs no other family (conv_tile_refusal)
 };
 static inline const ConvTile* conv_tile(int id) { return id >= 0 && id < (int)(sizeof TD_CONV_TILES / sizeof *TD_CONV_TILES) ? &TD_CONV_TILES[id] : nullptr; }
 static inline bool conv_head_capable(int id, int precision) { return precision == TD_PRECISION_FP16 && conv_tile(id) && conv_tile(id)->head; }
@@ -170,6 +173,10 @@ td_status conv_bs_launch(const ConvArgs& a, int precision, hipStream_t stream);
 // split-bf16 form (conv_split.hip, tile ids 34 - 37): w [cout][cin] fp32 → the three-piece fragment bank (6 bytes per weight)
 // (taps = 9 with w [cout][3][3][cin]: the 3x3 bank of the split bottleneck tail, k-chunks channel chunk outer / tap inner)
 void conv_split_pack(const float* w, int cout, int cin, std::vector<unsigned char>& out, int taps = 1);
+// bytes of the split bank of one [cout][cin] plane; a batched launch (batch_count > 1: the 36 planes of an F(4x4) layer, each packed
+// on its own and concatenated — conv_split_pack_planes) carries it as w_bs
+size_t conv_split_bank_bytes(int cout, int cin);
+void conv_split_pack_planes(const float* u, int planes, int cout, int cin, std::vector<unsigned char>& out);
 bool conv_split_ok(const ConvArgs& a, int precision);
 td_status conv_split_launch(const ConvArgs& a, int variant, hipStream_t stream);
 td_status wino_gemm_launch(const ConvArgs& a, hipStream_t stream);     // Winograd plane contractions, input transform fused (fp32)
@@ -226,6 +233,8 @@ struct WinoRun {
     int slab_tiles;            // F(2x2): tiles per slab
     int fold_group;            // folded F(4x4): images per launch pair
     const float *x, *U, *scale, *bias;      // U: the layer's filter bank of the form, [16] or [36][cout][cin]
+    const void* U_split;       // F(4x4) in three launches only: the split-bf16 twin of U (conv_split_pack_planes) — the 36 plane
+                               // contractions then run on the TILE_SPLIT ids (another rounding: a fixed rule of the caller's), or nullptr
     float* y;
     int B, H, W, cin, cout, relu;
     float *V, *M;              // workspace planes

@@ -1090,7 +1090,9 @@ const char* conv_tile_refusal(int id, const ConvArgs& a, int precision) {
         return "conv_bs_ok failed (1x1, stride 1, 1 / 2 / 4 k-chunks, 128 <= Cout <= 2048, Cout % 8 == 0, packed filters)";
     if (t->family == TILE_BD && !conv_bd_ok(a, precision)) return "conv_bd_ok failed (packed filters, plain output)";
     if (t->family == TILE_SPLIT && !conv_split_ok(a, precision))
-        return "conv_split_ok failed (fp32 1x1 without padding, plain output, Cin a multiple of 32, split filter bank)";
+        return "conv_split_ok failed (fp32 1x1 without padding, plain output, Cin a multiple of 32, split filter bank; batched: plain planes with static rows)";
+    // batched split planes count w_bs in bytes of the split bank: no other family can walk them
+    if (t->family != TILE_SPLIT && a.w_split && a.batch_count > 1) return "batched split planes run the split-bf16 tiles only";
     return nullptr;
 }
 
@@ -1122,6 +1124,11 @@ td_status conv2d_launch(const ConvArgs& a, int precision, hipStream_t stream) {
     // resolution of the tile id would silently write y and leave head_y untouched
     TD_REQUIRE(!a.head_w || (conv_head_capable(cfg, precision) && a.Cout == 256 && !a.res && a.out_mode == 0 && a.head_y && a.head_n >= 1 && a.head_n <= 32),
                "conv2d: a fused head needs a 256-channel fp16 layer on a tile that owns all its channels (tile id %d)", cfg);
+    if (cfg < 0 && a.w_split && a.batch_count > 1) {
+        // batched split planes (the op-level Winograd entry; the engine measures): a split tile or nothing — their strides are the split bank's
+        TD_REQUIRE(conv_split_ok(a, precision), "conv2d: batched split planes need plain fp32 planes with static rows and the split bank's byte stride");
+        cfg = a.M <= 2048 ? 37 : 35;
+    }
     if (cfg < 0) {
         // heuristic (the engine replaces it by a measured choice per layer shape): wide N for wide layers, 64-row
         // tiles when there is less than one 128-row tile per CU

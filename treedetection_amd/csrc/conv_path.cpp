@@ -69,7 +69,10 @@ ConvPath conv_path(const ConvRules& r, const ConvSite& s) {
         return p;
     }
     p.form = CONV_WINO43;
-    key(1 * 16 + 1, T43, 4 + 64);
+    // the split twin of the F(4x4) bank (td_engine::f32_split_wino): the planes contract on the split-bf16 tiles. Static rows only;
+    // the layer and the per-image map decide, never the batch (rows accumulate independently of T)
+    p.split_planes = L.w_split && !dyn;
+    key(1 * 16 + 1, T43, 4 + 64 + (p.split_planes ? 128 : 0));
     // the head rides in the output transform: bit-identical to the separate launch
     if (head1x1) p.head = HEAD_IN_TRANSFORM;
     return p;

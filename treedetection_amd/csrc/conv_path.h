@@ -20,7 +20,7 @@ struct ConvRules {
 struct ConvLayerFacts {
     int cout, cin, kh, kw;
     bool scale, out_f32;
-    bool wino_u, wino_u43, w_split;     // which filter banks the layer has beside its own
+    bool wino_u, wino_u43, w_split;     // which filter banks the layer has beside its own (w_split of a 3x3 layer: the split twin of its F(4x4) bank)
 };
 struct ConvSite {
     ConvLayerFacts L;
@@ -50,6 +50,9 @@ struct ConvPath {
     // folded F(4x4): images per launch pair. The kernel's 32-bit plane offsets hold 4 GB of V: a larger batch runs in image groups,
     // so the layer takes the SAME form at every batch size. (Device-side RoI count: all B reserved RoIs are one group.)
     int fold_group;
+    // CONV_WINO43 only: the 36 plane contractions run on the split-bf16 tiles (the layer has the split twin of its F(4x4) bank —
+    // ConvLayerFacts::w_split of a 3x3 layer — and static rows); the key then carries flag 128 on top of 64. Not the folded form.
+    bool split_planes;
 };
 
 ConvPath conv_path(const ConvRules& r, const ConvSite& s);

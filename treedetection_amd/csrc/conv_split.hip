@@ -39,12 +39,19 @@
 // this form 1 015 us as hipcc orders it, 857 us paced, the 64 x 256 tile 904 - 949 us).
 // The 3x3 of res2 (64 -> 64) runs the same arithmetic inside the fused bottleneck tail, not here: bottleneck.hip's split form uses
 // split8 (conv_tiles.h), this piece and product order and conv_split_pack with taps = 9; no 3x3 form of conv_split_kernel exists.
+// Batched form (ConvArgs::batch_count > 1, grid.y = the plane): the 36 plane contractions V[p] [T x C] . U[p]^T of an F(4x4,3x3) layer
+// that does not fold (wino_seq.cpp; the twin bank: conv_split_pack_planes, the rule: engine.cpp f32_split_wino). Plane blockIdx.y
+// advances x, w_split (by w_bs BYTES) and y in 64-bit arithmetic on the kernel's own copy of the arguments; everything below then
+// sees one plane — its buffer resources, xcd_remap, the k-loop and the epilogue are those of a plain launch, so ids 34 - 37 stay
+// bit-identical to each other on planes. Registers, LDS and scratch of the four instantiations are unchanged.
 // Measured (profiles/f32_split.txt, batch 8): fc1 (8000 x 1024 x 12544) 1 549 -> 900 us = 228 TFLOP/s, fc2 137 -> 89 us. conv1 and the
 // shortcuts of res3 - res5 and the FPN laterals (8 - 64 k-chunks per block; profiles/f32_split_backbone.txt): 2.41 -> 1.95 ms in the layer
 // table, headline 697.6 -> 726.2 tiles/s: on by default with the box head (engine.cpp SPLIT_DEFAULT); conv3 ties on its fp32 tiles: off.
 #include "common.h"
 #include "conv_tiles.h"
+#include <algorithm>
 #include <utility>
+#include <vector>
 
 namespace {
 
@@ -290,7 +297,14 @@ __device__ __forceinline__ void conv_split_body(const ConvArgs& a, char* lds) {
 
 template <int MT, int NT, int WM, int WN, int WPE>
 __global__ __launch_bounds__(64 * WM * WN, WPE)
-void conv_split_kernel(const ConvArgs a) {
+void conv_split_kernel(const ConvArgs a_in) {
+    ConvArgs a = a_in;
+    if (a.batch_count > 1) {                          // batched planes (F(4x4) Winograd): plane blockIdx.y of x / w_split / y; the buffer
+        const long long bz = blockIdx.y;              // resources of the body are built on the advanced bases, 32-bit offsets stay in one plane
+        a.x = static_cast<const float*>(a.x) + bz * a.x_bs;
+        a.w_split = static_cast<const char*>(a.w_split) + bz * a.w_bs;      // (w_bs: BYTES of one plane's split bank)
+        a.y = static_cast<float*>(a.y) + bz * a.y_bs;
+    }
     constexpr int STAGE_BYTES = 3 * 32 * MT * WM * CHUNK_BYTES;
     constexpr int EPI_BYTES = conv_epilogue_lds_bytes<float, MT, NT, WM, WN, 1>();
     constexpr int LDS_BYTES = STAGE_BYTES > EPI_BYTES ? STAGE_BYTES : EPI_BYTES;
@@ -303,7 +317,7 @@ void conv_split_kernel(const ConvArgs a) {
 template <int MT, int NT, int WM, int WN, int WPE>
 td_status launch_split(const ConvArgs& a, hipStream_t stream) {
     const int tiles = td_cdiv(a.M, 32 * MT * WM) * td_cdiv(a.Cout, 32 * NT * WN);
-    hipLaunchKernelGGL((conv_split_kernel<MT, NT, WM, WN, WPE>), dim3(tiles), dim3(64 * WM * WN), 0, stream, a);
+    hipLaunchKernelGGL((conv_split_kernel<MT, NT, WM, WN, WPE>), dim3(tiles, a.batch_count > 1 ? a.batch_count : 1), dim3(64 * WM * WN), 0, stream, a);
     TD_KERNEL_CHECK();
     return TD_OK;
 }
@@ -346,10 +360,27 @@ void conv_split_pack(const float* w, int cout, int cin, std::vector<unsigned cha
                 }
 }
 
+size_t conv_split_bank_bytes(int cout, int cin) { return (size_t)((cout + 31) / 32) * (size_t)(cin / 32) * SPLIT_CHUNK_BYTES; }
+
+// the split twin of a Winograd filter bank U [planes][cout][cin]: conv_split_pack on every plane, concatenated
+void conv_split_pack_planes(const float* u, int planes, int cout, int cin, std::vector<unsigned char>& out) {
+    const size_t bank = conv_split_bank_bytes(cout, cin);
+    out.resize((size_t)planes * bank);
+    std::vector<unsigned char> one;
+    for (int p = 0; p < planes; ++p) {
+        conv_split_pack(u + (size_t)p * cout * cin, cout, cin, one);
+        std::copy(one.begin(), one.end(), out.begin() + (size_t)p * bank);
+    }
+}
+
+// A batched launch (batch_count > 1: the planes of a Winograd layer) is admitted for plain planes only: rows [M][Cin] per plane with
+// static count, no residual, and w_bs = the BYTES of one plane's split bank (conv_split_pack of that plane's [Cout][Cin]).
 bool conv_split_ok(const ConvArgs& a, int precision) {
+    const size_t bank = (size_t)((a.Cout + 31) / 32) * (size_t)(a.Cin / 32) * SPLIT_CHUNK_BYTES;
+    const bool planes_ok = a.batch_count <= 1 || (!a.res && !a.m_dyn && a.m_off == 0 && a.stride == 1 && (long long)a.B * a.H * a.W == a.M &&
+                                                  a.x_bs >= (long long)a.M * a.Cin && a.y_bs >= (long long)a.M * a.Cout && a.w_bs == (long long)bank);
     return precision == TD_PRECISION_FP32 && a.w_split && a.KH == 1 && a.KW == 1 && a.pad == 0 && a.stride >= 1 && a.out_mode == 0 &&
-           a.batch_count <= 1 && !a.out_f32 && !a.head_w && a.Cin >= 32 && a.Cin % 32 == 0 &&
-           (size_t)((a.Cout + 31) / 32) * (size_t)(a.Cin / 32) * SPLIT_CHUNK_BYTES < 0xfffffff0ull - (1u << 20);
+           planes_ok && !a.out_f32 && !a.head_w && a.Cin >= 32 && a.Cin % 32 == 0 && bank < 0xfffffff0ull - (1u << 20);
 }
 
 td_status conv_split_launch(const ConvArgs& a, int variant, hipStream_t stream) {

@@ -35,6 +35,8 @@ struct HostTensor {
 
 enum { SPLIT_FC = 1, SPLIT_LATERAL = 2, SPLIT_CONV1 = 4, SPLIT_CONV3 = 8, SPLIT_SHORTCUT = 16,
        SPLIT_DEFAULT = SPLIT_FC | SPLIT_LATERAL | SPLIT_CONV1 | SPLIT_SHORTCUT };
+// layer classes of td_engine::f32_split_wino (the split twin of the F(4x4) filter bank)
+enum { WINO_SPLIT_RES = 1, WINO_SPLIT_FPN = 2, WINO_SPLIT_RPN = 4, WINO_SPLIT_DEFAULT = WINO_SPLIT_RES | WINO_SPLIT_FPN | WINO_SPLIT_RPN };
 
 struct ConvLayer {
     int cout = 0, cin = 0, kh = 1, kw = 1;
@@ -49,6 +51,8 @@ struct ConvLayer {
                               // in the split tail's fragment order (bottleneck.hip). Not w_split: the layer is no conv_path SPLIT layer
     float* wino_u = nullptr;  // fp32 engine, 3x3 layers: Winograd-transformed filters U [16][cout][cin] (winograd.hip)
     float* wino_u43 = nullptr;  // the same for F(4x4,3x3): U [36][cout][cin] (layers with >= 128 channels on both sides)
+    void* wino_u43_split = nullptr;   // fp32 engine, the layer classes of td_engine::f32_split_wino: the 36 planes of wino_u43 as split-bf16
+                              // banks (conv_split_pack per plane, concatenated); the unfolded F(4x4) form then contracts on the TILE_SPLIT ids
 };
 
 struct Block {
@@ -137,6 +141,18 @@ struct td_engine : Workspace {          // (the workspace pointers: workspace.h)
     // with TD_FUSE_TAIL=0 conv2 runs as the SAME kernel's mid-store launch (it stops behind phase 2 and writes t2) and conv3 as the
     // fp32 1x1 launch it always was, which the fused kernel's phase 3 equals bit for bit. Cost: 221 KB per block, +0.66 MB per engine.
     bool f32_split_tail = true;
+    // fp32 engine: the 36 plane contractions of the F(4x4,3x3) layers that do NOT fold (CONV_WINO43, three launches) on the bf16 matrix
+    // cores the same way: each plane is a plain 1x1 contraction V[p] [T x C] . U[p]^T, one batched launch of conv_split_kernel. A FIXED
+    // rule on the layer (TD_F32_SPLIT_WINO, bit mask of layer classes; 0 = fp32 planes, for an A/B on one build), never a timing:
+    // WINO_SPLIT_RES conv2 of res4 / res5, WINO_SPLIT_FPN the FPN outputs, WINO_SPLIT_RPN the RPN conv. A layer of a class has the
+    // twin bank; conv_path takes it where the layer runs the unfolded form with static rows (the folded layers and the mask head never do).
+    // The default is all three classes (7): in the layer table (batch 8, 800 x 800) the contractions of res4 conv2 go 67 - 74 -> 60 - 63 us,
+    // res5 conv2 76 - 77 -> 71 - 72, fpn_output4 67 -> 61, rpn p3 / p4 220 / 69 -> 164 / 60; the 7 x 7 and 4 x 4 maps of 256 channels
+    // (fpn_output5, rpn p5 / p6: 25 / 26 / 15 us) lose 2 - 3 us each and keep their class's rule. Headline 758.5 - 764.4 -> 773.1 - 779.0
+    // tiles/s on one box, alternated (profiles/f32_split_wino.txt).
+    // Cost: 36 N C 6 B per layer (14 MB at 256 x 256, 57 MB at 512 x 512); measured per R50 engine 958 -> 1 288 MB of device memory
+    // (+ 329 MB: 256 / 58 / 14 MB for the three classes) and 0.80 - 0.86 -> 1.04 s of load time.
+    int f32_split_wino = WINO_SPLIT_DEFAULT;
     std::string tune_cache;       // TD_TUNE_CACHE: load / append measured choices (keeps profiled runs free of tuning launches)
     // The tuner times every candidate tile with the L2 (8 x 4 MB) emptied before each launch (a fill of this scratch on the same
     // stream): in the forward a layer's filters and most of its input are NOT in L2 — 50-odd other launches ran since — and a loop of
@@ -320,8 +336,10 @@ td_status bn_fold(const TensorMap& tm, const std::string& p, int c, std::vector<
 }
 
 // fp32 engine: the Winograd filter banks of a 3x3 layer (which form uses them where: conv_path)
-td_status upload_wino(td_engine* e, const std::vector<float>& w_ohwi, ConvLayer& L) {
+// wino_cls (WINO_SPLIT_*): the layer's class under td_engine::f32_split_wino — the F(4x4) bank then gets its split-bf16 twin
+td_status upload_wino(td_engine* e, const std::vector<float>& w_ohwi, ConvLayer& L, int wino_cls) {
     L.wino_u = nullptr;
+    L.wino_u43_split = nullptr;
     if (e->desc.precision != TD_PRECISION_FP32 || !e->winograd || L.kh != 3 || L.kw != 3 || L.cin % 32 != 0 || L.cout % 4 != 0)
         return TD_OK;
     std::vector<float> u((size_t)16 * L.cout * L.cin);
@@ -330,10 +348,16 @@ td_status upload_wino(td_engine* e, const std::vector<float>& w_ohwi, ConvLayer&
     if (st < 0 || e->wino43_min <= 0 || L.cin < e->wino_minc || L.cout < e->wino_minc) return st;
     std::vector<float> u43((size_t)36 * L.cout * L.cin);
     wino43_filter_transform(w_ohwi.data(), L.cout, L.cin, u43.data());
-    return upload(e, u43, &L.wino_u43);
+    if ((st = upload(e, u43, &L.wino_u43)) < 0 || !(e->f32_split_wino & wino_cls)) return st;
+    std::vector<unsigned char> packed;
+    conv_split_pack_planes(u43.data(), 36, L.cout, L.cin, packed);
+    unsigned char* d = nullptr;
+    st = upload(e, packed, &d);
+    L.wino_u43_split = d;
+    return st;
 }
 
-td_status load_conv_bn(td_engine* e, const TensorMap& tm, const std::string& p, ConvLayer& L, int split_cls = 0) {
+td_status load_conv_bn(td_engine* e, const TensorMap& tm, const std::string& p, ConvLayer& L, int split_cls = 0, int wino_cls = 0) {
     const HostTensor* w;
     td_status st = need(tm, p + ".weight", 4, &w);
     if (st < 0) return st;
@@ -345,14 +369,14 @@ td_status load_conv_bn(td_engine* e, const TensorMap& tm, const std::string& p, 
     if ((st = upload_w(e, packed, &L.w)) < 0) return st;
     if ((st = upload_frag(e, packed, L)) < 0) return st;
     if ((st = upload_split(e, packed, L, split_cls)) < 0) return st;
-    if ((st = upload_wino(e, packed, L)) < 0) return st;
+    if ((st = upload_wino(e, packed, L, wino_cls)) < 0) return st;
     std::vector<float> s, b;
     if ((st = bn_fold(tm, p, L.cout, s, b)) < 0) return st;
     if ((st = upload(e, s, &L.scale)) < 0) return st;
     return upload(e, b, &L.bias);
 }
 
-td_status load_conv_bias(td_engine* e, const TensorMap& tm, const std::string& p, ConvLayer& L, int split_cls = 0) {
+td_status load_conv_bias(td_engine* e, const TensorMap& tm, const std::string& p, ConvLayer& L, int split_cls = 0, int wino_cls = 0) {
     const HostTensor *w, *b;
     td_status st = need(tm, p + ".weight", 4, &w);
     if (st < 0) return st;
@@ -369,7 +393,7 @@ td_status load_conv_bias(td_engine* e, const TensorMap& tm, const std::string& p
     if ((st = upload_w(e, packed, &L.w)) < 0) return st;
     if ((st = upload_frag(e, packed, L)) < 0) return st;
     if ((st = upload_split(e, packed, L, split_cls)) < 0) return st;
-    if ((st = upload_wino(e, packed, L)) < 0) return st;
+    if ((st = upload_wino(e, packed, L, wino_cls)) < 0) return st;
     L.scale = nullptr;
     return upload(e, std::vector<float>(b->data, b->data + L.cout), &L.bias);
 }
@@ -518,6 +542,7 @@ td_status td_engine_create(const td_model_desc* desc, int device, td_engine** ou
     if (const char* ft = getenv("TD_FUSE_TAIL")) { e->fuse_tail = atoi(ft) != 0; e->fuse_tail_fp16 = atoi(ft) == 2; }
     if (const char* sp = getenv("TD_F32_SPLIT")) e->f32_split = atoi(sp);
     if (const char* spt = getenv("TD_F32_SPLIT_TAIL")) e->f32_split_tail = atoi(spt) != 0;
+    if (const char* spw = getenv("TD_F32_SPLIT_WINO")) e->f32_split_wino = atoi(spw);
     e->desc = d;
     read_rule_switches(e);
     load_tune_cache(e);
@@ -619,7 +644,7 @@ td_status td_engine_load_weights(td_engine* e, const td_tensor_desc* tensors, si
             // (the split rule: res3 - res5 only — conv2 / conv3 of res2 also exist inside bottleneck_tail_kernel; its conv2 takes the
             // split tail's bank below)
             if ((st = load_conv_bn(e, tm, p + ".conv1", blk.c1, si > 0 ? SPLIT_CONV1 : 0)) < 0) return st;
-            if ((st = load_conv_bn(e, tm, p + ".conv2", blk.c2)) < 0) return st;
+            if ((st = load_conv_bn(e, tm, p + ".conv2", blk.c2, 0, si >= 2 ? WINO_SPLIT_RES : 0)) < 0) return st;
             if ((st = load_conv_bn(e, tm, p + ".conv3", blk.c3, si > 0 ? SPLIT_CONV3 : 0)) < 0) return st;
             if (si == 0 && (st = upload_tail_split(e, pack_ohwi(tm.at(p + ".conv2.weight")), blk.c2, blk.c3.cout)) < 0) return st;
             blk.has_sc = tm.find(p + ".shortcut.weight") != tm.end();
@@ -633,10 +658,10 @@ td_status td_engine_load_weights(td_engine* e, const td_tensor_desc* tensors, si
     }
     for (int l = 0; l < 4; ++l) {
         if ((st = load_conv_bias(e, tm, "backbone.fpn_lateral" + std::to_string(l + 2), e->lateral[l], SPLIT_LATERAL)) < 0) return st;
-        if ((st = load_conv_bias(e, tm, "backbone.fpn_output" + std::to_string(l + 2), e->fpn_out[l])) < 0) return st;
+        if ((st = load_conv_bias(e, tm, "backbone.fpn_output" + std::to_string(l + 2), e->fpn_out[l], 0, WINO_SPLIT_FPN)) < 0) return st;
     }
     e->fpn_c = e->lateral[0].cout;
-    if ((st = load_conv_bias(e, tm, "proposal_generator.rpn_head.conv", e->rpn_conv)) < 0) return st;
+    if ((st = load_conv_bias(e, tm, "proposal_generator.rpn_head.conv", e->rpn_conv, 0, WINO_SPLIT_RPN)) < 0) return st;
     {
         const HostTensor *wo, *bo, *wd, *bd;
         if ((st = need(tm, "proposal_generator.rpn_head.objectness_logits.weight", 4, &wo)) < 0) return st;
@@ -884,8 +909,10 @@ struct WinoBooks {
         const double T = f22 ? (double)n : (double)r.B * ((r.H + 3) / 4) * ((r.W + 3) / 4);     // F(2x2): the slab's tiles
         const double share = f22 ? 1.0 : (double)n / r.B;                                         // folded F(4x4): the image group's part
         const double px = (double)r.B * r.H * r.W;
-        const double xb = 4.0 * px * r.cin, yb = 4.0 * px * r.cout, ub = 4.0 * P * r.cout * r.cin;
-        const double vb = 4.0 * P * T * r.cin, mb = 4.0 * P * T * r.cout, pf = 2.0 * P * T * (double)r.cin * r.cout;
+        // (split planes: the twin bank crosses as 6 bytes per weight; six bf16 MFMAs per 16 k = 6/16 of the fp32 pipe time)
+        const bool splitp = r.form == CONV_WINO43 && r.U_split;
+        const double xb = 4.0 * px * r.cin, yb = 4.0 * px * r.cout, ub = (splitp ? 6.0 : 4.0) * P * r.cout * r.cin;
+        const double vb = 4.0 * P * T * r.cin, mb = 4.0 * P * T * r.cout, pf = 2.0 * P * T * (double)r.cin * r.cout * (splitp ? 6.0 / 16.0 : 1.0);
         if (step == WINO_STEP_INPUT) {
             k.cs.emplace(k.e, k.s, TD_CLS_WINO_XFORM, 0.0, (xb + vb) * share);
         } else if (step == WINO_STEP_GEMM) {
@@ -909,7 +936,7 @@ td_status run_wino(td_engine* e, const WinoRun& r, hipStream_t s) {
 }
 
 ConvLayerFacts layer_facts(const ConvLayer& L) {
-    return {L.cout, L.cin, L.kh, L.kw, L.scale != nullptr, L.out_f32, L.wino_u != nullptr, L.wino_u43 != nullptr, L.w_split != nullptr};
+    return {L.cout, L.cin, L.kh, L.kw, L.scale != nullptr, L.out_f32, L.wino_u != nullptr, L.wino_u43 != nullptr, L.w_split != nullptr || L.wino_u43_split != nullptr};
 }
 
 // One contraction of the forward: ask conv_path which form the layer takes, measure the block tile of the launch shape it names,
@@ -942,6 +969,7 @@ td_status run_conv(td_engine* e, const ConvLayer& L, const void* x_, int B_, int
         wr.x = static_cast<const float*>(x_); wr.U = use_43 ? L.wino_u43 : L.wino_u; wr.scale = L.scale; wr.bias = L.bias; wr.y = static_cast<float*>(y_);
         wr.B = B_; wr.H = H_; wr.W = W_; wr.cin = L.cin; wr.cout = L.cout; wr.relu = relu ? 1 : 0;
         wr.V = e->wino_v; wr.M = e->wino_m; wr.m_dyn = m_dyn; wr.m_mul = m_mul; wr.gemm_cfg = -1;
+        wr.U_split = path.split_planes ? L.wino_u43_split : nullptr;
     }
     if (path.tune) {
         const auto key = std::make_tuple(path.key[0], path.key[1], path.key[2], path.key[3], path.key[4]);
@@ -963,7 +991,7 @@ td_status run_conv(td_engine* e, const ConvLayer& L, const void* x_, int B_, int
     if (e->prof && !m_dyn) {          // category 8: FLOPs the MFMA pipe really executes
         const double padded = use_43 ? (double)(((H_ + 3) / 4) * 4) * (((W_ + 3) / 4) * 4) / ((double)H_ * W_) : 1.0;
         // (a split launch: six bf16 MFMAs, 192 pipe cycles, per 16 k against 512 for the fp32 MFMAs — its pipe time in units of the fp32 rate)
-        e->prof_flops[8] += use_43 ? flops * padded * 0.25 : (use_wino ? flops * 4.0 / 9.0 : (split ? flops * 6.0 / 16.0 : flops));
+        e->prof_flops[8] += use_43 ? flops * padded * 0.25 * (path.split_planes ? 6.0 / 16.0 : 1.0) : (use_wino ? flops * 4.0 / 9.0 : (split ? flops * 6.0 / 16.0 : flops));
         e->prof_launches[8] += use_wino ? 1 : 0;
     }
     if (e->prof && fuse_head) {

@@ -20,7 +20,9 @@ ConvArgs wino_plane_args(const WinoRun& r, int n, long long t0) {
 }
 
 // The 36 plane contractions of F(4x4,3x3) over a whole layer as ONE batched launch: V [36][T][cin] x U -> M [36][T][cout]
-// (m_dyn: the planes keep the stride of the full batch, only the live tiles are computed)
+// (m_dyn: the planes keep the stride of the full batch, only the live tiles are computed). With the split twin of U (WinoRun::U_split,
+// static rows) the same launch runs conv_split_kernel's batched form: w_split and the bank's byte stride ride along, and
+// conv_tile_refusal then lets the TILE_SPLIT ids run it and nothing else.
 ConvArgs wino43_plane_args(const WinoRun& r) {
     const int tiles_img = ((r.H + 3) / 4) * ((r.W + 3) / 4);
     const long long T = (long long)r.B * tiles_img;
@@ -31,6 +33,8 @@ ConvArgs wino43_plane_args(const WinoRun& r) {
     a.M = (int)T; a.m_dyn = r.m_dyn; a.m_mul = r.m_dyn ? tiles_img : 1;
     a.batch_count = 36; a.x_bs = T * r.cin; a.w_bs = (long long)r.cout * r.cin; a.y_bs = T * r.cout;
     a.tile_cfg = r.gemm_cfg;
+    // the split twin (static rows only): the planes contract on the split-bf16 tiles, whose bank stride counts bytes
+    if (r.U_split && !r.m_dyn) { a.w_split = r.U_split; a.w_bs = (long long)conv_split_bank_bytes(r.cout, r.cin); }
     return a;
 }
 
