@@ -795,6 +795,40 @@ td_status td_ring_pairs_area_dev(const double* xy_a, const int64_t* start_a, int
 td_status td_ring_pairs_area(const double* xy_a, const int64_t* start_a, int n_a, const double* xy_b, const int64_t* start_b, int n_b,
                              const int32_t* pairs, int64_t n_pairs, double* out, int32_t* status);
 
+/* ---- evaluation against annotated crowns (reference supplementary/evaluation_compute_scores.py) ----
+ * Candidate pairs between TWO box sets A and B (csrc/boxpairs_ab.hip, boxpairs_ab_host.cpp). Boxes are float64 [n][4] =
+ * (x1, y1, x2, y2). THE PAIR RULE: (i, j), i in A and j in B, is a pair iff
+ *     min(x2_i, x2_j) > max(x1_i, x1_j)  and  min(y2_i, y2_j) > max(y1_i, y1_j)
+ * — an overlap of positive area — decided by comparisons alone: every upper coordinate of the two boxes exceeds every lower one
+ * of the same axis (x2_i > x1_i, x2_j > x1_j, x2_i > x1_j, x2_j > x1_i, likewise y). Nothing is rounded; a NaN coordinate fails
+ * every comparison, so its box pairs with nothing; touching boxes and boxes of zero width or height pair with nothing. The
+ * device calls and the host call give the same set for any input.
+ * td_box_pairs_ab_count: boxes_a, boxes_b, counts are DEVICE memory, the boxes 16-byte aligned; counts int32 [n_a] = pairs of row
+ * i, zeroed on `stream` by the call. td_box_pairs_ab_fill: row_start DEVICE int64 [n_a + 1] = exclusive prefix sum of counts; cols
+ * int32 [row_start[n_a]] receives the column indices of row i in [row_start[i], row_start[i + 1]), in no particular order; cursor:
+ * int32 [n_a] of scratch, zeroed on `stream` by the call. Same boxes as the count pass, which ran the same test. 256 rows of A per
+ * workgroup against chunks of 1 024 boxes of B in LDS. Both return TD_ERR_INVALID (with a message, before any launch) for a null
+ * pointer, misaligned boxes, n_a < 1 or n_b < 1, or more than 67 107 840 boxes on a side (65 535 column chunks, the launch
+ * grid's second dimension). Asynchronous on `stream`.
+ * td_box_pairs_ab: HOST memory, host code (a sweep over B sorted by x1); counts int32 [n_a]; when cols is non-null the column
+ * indices of row i follow those of row i - 1 in cols, ASCENDING within the row; TD_ERR_CAPACITY when they exceed cols_cap
+ * entries (call once with cols = NULL for the counts). n_a = 0 or n_b = 0 is served. TD_ERR_INVALID for a null pointer or a
+ * negative count. */
+td_status td_box_pairs_ab_count(const double* boxes_a, int n_a, const double* boxes_b, int n_b, int32_t* counts, void* stream);
+td_status td_box_pairs_ab_fill(const double* boxes_a, int n_a, const double* boxes_b, int n_b, const int64_t* row_start,
+                               int32_t* cursor, int32_t* cols, void* stream);
+td_status td_box_pairs_ab(const double* boxes_a, int n_a, const double* boxes_b, int n_b, int32_t* counts, int32_t* cols,
+                          int64_t cols_cap);
+/* The matching loop of the reference's calculate_iou over a sparse IoU matrix (HOST memory throughout, host code, O(m + entries)):
+ * CSR rows over the m predictions — row_start int64 [m + 1] from 0, cols int32 = annotation indices in [0, n), iou float64, no
+ * NaN. Predictions are walked in index order; a prediction with selected[i] == 0 is passed over; a selected one takes, of its
+ * entries whose annotation is still unmatched, the one with the largest IoU (the lowest annotation index among equal IoUs,
+ * whatever order the row is stored in) when that IoU is >= t, and stays unmatched otherwise. Out: match_of_pred int32 [m] = the
+ * annotation index or -1, match_iou float64 [m] (0 where unmatched), ann_matched uint8 [n]. TD_ERR_INVALID for a null pointer, a
+ * negative count, row_start[0] != 0, a decreasing row_start, a column outside [0, n), a NaN IoU or t outside (0, 1]. */
+int td_match_greedy(const int64_t* row_start, const int32_t* cols, const double* iou, const uint8_t* selected, int m, int n, double t,
+                    int32_t* match_of_pred, double* match_iou, uint8_t* ann_matched);
+
 /* ---- seam strips (reference helpers.py merge_images 1023-1051 + crop_image 1053-1085; csrc/seam.hip) ----
  * The strip [rows][cols][spp] (DEVICE, dense, aligned to its samples; TD_SAMPLE_U8, TD_SAMPLE_U16 or TD_SAMPLE_F32, 1 <= spp <= 4)
  * that the centre crop of rasterio.merge's "first" mosaic of two rasters holds, from up to two source buffers in one launch, without
