@@ -169,7 +169,7 @@ td_status td_engine_profile_read(td_engine* e, double* ms, int64_t* launches, do
 #define TD_CLS_FC 4          /* box head: fc1, fc2, predictors */
 #define TD_CLS_MASK_HEAD 5   /* mask-head contractions and transforms (rows = live detections, known on the device only) */
 #define TD_CLS_TAIL 6        /* fused bottleneck tail: 3x3 (mid -> mid) + 1x1 (mid -> 4 mid) + shortcut in one launch (res2; fp16: res3 too) */
-#define TD_PEAK_F32_MFMA_TFLOPS 157.3   /* v_mfma_f32_32x32x2_f32, dense (a split-bf16 launch enters the accounting with 6/16 of its FLOPs: its MFMA pipe time at this rate) */
+#define TD_PEAK_F32_MFMA_TFLOPS 157.3   /* v_mfma_f32_32x32x2_f32, dense (a split-bf16 launch enters the accounting with 6/16 of its FLOPs, SPLIT_PIPE_FACTOR of csrc/launch_cost.cpp: its MFMA pipe time at this rate) */
 #define TD_PEAK_F16_MFMA_TFLOPS 2500.0  /* v_mfma_f32_32x32x16_f16, dense */
 #define TD_HBM_ACHIEVABLE_TBS 6.3       /* measured streaming rate (8.0 TB/s spec) */
 td_status td_engine_profile_classes(td_engine* e, double* ms, int64_t* launches, double* exec_flops, double* bytes, double* tmin_ms, int reset);

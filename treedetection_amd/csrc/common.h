@@ -6,6 +6,7 @@
 #include <cstddef>
 #include "../../include/treedet.h"
 #include "conv_path.h"
+#include "launch_cost.h"
 #include <string>
 #include <vector>
 
@@ -248,8 +249,7 @@ struct WinoRun {
 ConvArgs wino_plane_args(const WinoRun& r, int n, long long t0);      // what the tuner times: the launch shapes of the plane contractions
 ConvArgs wino43_plane_args(const WinoRun& r);
 // Optional books of a caller around every launch (the engine's profiling): n = tiles of the slab (F(2x2)) or images of the launch
-// (F(4x4)). A null hook costs a null check per launch.
-enum { WINO_STEP_INPUT, WINO_STEP_GEMM, WINO_STEP_OUTPUT };
+// (F(4x4)); the steps: WINO_STEP_* (launch_cost.h). A null hook costs a null check per launch.
 struct WinoHook {
     void* ctx;
     void (*begin)(void* ctx, int step, long long n);

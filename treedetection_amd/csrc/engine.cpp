@@ -178,7 +178,7 @@ struct td_engine : Workspace {          // (the workspace pointers: workspace.h)
     // optional per-category device timing (td_engine_profile_*)
     bool prof = false;
     bool prof_group_open = false;
-    struct ProfRec { hipEvent_t a, b; int cat; };
+    struct ProfRec { hipEvent_t a, b; int id; };      // a recorded event pair of category / class id
     std::vector<ProfRec> prof_recs;
     std::vector<hipEvent_t> prof_free;
     double prof_ms[TD_PROF_CATEGORIES] = {};
@@ -195,8 +195,7 @@ struct td_engine : Workspace {          // (the workspace pointers: workspace.h)
     double cls_flops[TD_PROF_CLASSES] = {};
     double cls_bytes[TD_PROF_CLASSES] = {};
     double cls_tmin_ms[TD_PROF_CLASSES] = {};
-    struct ClsRec { hipEvent_t a, b; int cls; };
-    std::vector<ClsRec> cls_recs;
+    std::vector<ProfRec> cls_recs;
 };
 
 namespace {
@@ -417,7 +416,8 @@ void publish(td_engine* e, const WsGeom& g, int phase) {
         }
 }
 
-hipEvent_t prof_event(td_engine* e) {
+// an event of the engine's pool, recorded on s
+hipEvent_t prof_event(td_engine* e, hipStream_t s) {
     hipEvent_t ev = nullptr;
     if (!e->prof_free.empty()) {
         ev = e->prof_free.back();
@@ -425,63 +425,62 @@ hipEvent_t prof_event(td_engine* e) {
     } else {
         (void)hipEventCreate(&ev);
     }
+    (void)hipEventRecord(ev, s);
     return ev;
 }
 
-// RAII bracket: records start on construction and stop on destruction (only when profiling is on). A GROUP scope
-// brackets a run of back-to-back launches of one category with ONE event pair (an event per launch costs ≈3 % of
-// the fp32 step and ≈10 % of the fp16 step in extra kernel boundaries); launches inside it only add their counts.
+// the finished event pairs of one book: their times into ms[id], the events back to the pool
+td_status drain_recs(td_engine* e, std::vector<td_engine::ProfRec>& recs, double* ms) {
+    for (auto& r : recs) {
+        TD_HIP_CHECK(hipEventSynchronize(r.b));
+        float t = 0.f;
+        TD_HIP_CHECK(hipEventElapsedTime(&t, r.a, r.b));
+        ms[r.id] += t;
+        e->prof_free.push_back(r.a);
+        e->prof_free.push_back(r.b);
+    }
+    recs.clear();
+    return TD_OK;
+}
+
+// THE booking bracket (RAII) of one launch, or (cat or cls none, launch_cost.h) of a sequence / of one step of it: adds what the launch
+// costs to both books and records start on construction and stop on destruction (only when profiling is on). The category side: a
+// GROUP scope brackets a run of back-to-back launches of one category with ONE event pair (an event per launch costs ≈3 % of the
+// fp32 step and ≈10 % of the fp16 step in extra kernel boundaries); launches inside it only add their counts. The class side: always
+// the model (executed FLOPs, bytes the chosen algorithm moves, t_min); in detail mode also an event pair of its own, inside the other.
 struct ProfScope {
     td_engine* e;
     hipStream_t s;
-    hipEvent_t a = nullptr;
-    int cat;
+    hipEvent_t a = nullptr, cls_a = nullptr;
+    int cat, cls;
     bool group;
-    ProfScope(td_engine* e_, hipStream_t s_, int cat_, double flops = 0.0, double bytes = 0.0, bool group_ = false)
-        : e(e_), s(s_), cat(cat_), group(group_) {
+    ProfScope(td_engine* e_, hipStream_t s_, int cat_, bool group_ = false) : ProfScope(e_, s_, LaunchCost{cat_}, group_) {}
+    ProfScope(td_engine* e_, hipStream_t s_, const LaunchCost& c, bool group_ = false) : e(e_), s(s_), cat(c.cat), cls(c.cls), group(group_) {
         if (!e->prof) return;
-        if (!group) {
-            e->prof_flops[cat] += flops;
-            e->prof_bytes[cat] += bytes;
-            e->prof_launches[cat] += 1;
+        if (cat >= 0 && !group) {
+            e->prof_flops[cat] += c.flops;
+            e->prof_bytes[cat] += c.bytes;
+            e->prof_launches[cat] += c.layers;
+            e->prof_flops[8] += c.exec_flops;
+            e->prof_launches[8] += c.wino ? 1 : 0;
         }
-        if (e->prof_group_open) return;                // counted; the enclosing group owns the events (groups do not nest)
-        a = prof_event(e);
-        (void)hipEventRecord(a, s);
-        if (group) e->prof_group_open = true;
-    }
-    ~ProfScope() {
-        if (!a) return;
-        hipEvent_t b = prof_event(e);
-        (void)hipEventRecord(b, s);
-        e->prof_recs.push_back({a, b, cat});
-        if (group) e->prof_group_open = false;
-    }
-};
-
-// One launch of the contraction family under its speed-of-light class: always adds the model side (executed FLOPs,
-// bytes the chosen algorithm moves, t_min) while profiling is on; in detail mode also an event pair of its own.
-struct ClassScope {
-    td_engine* e;
-    hipStream_t s;
-    hipEvent_t a = nullptr;
-    int cls;
-    ClassScope(td_engine* e_, hipStream_t s_, int cls_, double exec_flops, double bytes) : e(e_), s(s_), cls(cls_) {
-        if (!e->prof) return;
+        if (cat >= 0 && !e->prof_group_open) {         // (else counted; the enclosing group owns the events: groups do not nest)
+            a = prof_event(e, s);
+            if (group) e->prof_group_open = true;
+        }
+        if (cls < 0) return;
         const double peak = (e->desc.precision == TD_PRECISION_FP16 ? TD_PEAK_F16_MFMA_TFLOPS : TD_PEAK_F32_MFMA_TFLOPS) * 1e12;
         e->cls_launches[cls] += 1;
-        e->cls_flops[cls] += exec_flops;
-        e->cls_bytes[cls] += bytes;
-        e->cls_tmin_ms[cls] += 1e3 * std::max(exec_flops / peak, bytes / (TD_HBM_ACHIEVABLE_TBS * 1e12));
-        if (!e->prof_detail) return;
-        a = prof_event(e);
-        (void)hipEventRecord(a, s);
+        e->cls_flops[cls] += c.exec_flops;
+        e->cls_bytes[cls] += c.cls_bytes;
+        e->cls_tmin_ms[cls] += 1e3 * std::max(c.exec_flops / peak, c.cls_bytes / (TD_HBM_ACHIEVABLE_TBS * 1e12));
+        if (e->prof_detail) cls_a = prof_event(e, s);
     }
-    ~ClassScope() {
+    ~ProfScope() {
+        if (cls_a) e->cls_recs.push_back({cls_a, prof_event(e, s), cls});
         if (!a) return;
-        hipEvent_t b = prof_event(e);
-        (void)hipEventRecord(b, s);
-        e->cls_recs.push_back({a, b, cls});
+        e->prof_recs.push_back({a, prof_event(e, s), cat});
+        if (group) e->prof_group_open = false;
     }
 };
 
@@ -889,59 +888,28 @@ td_status tuned_cfg(td_engine* e, const std::tuple<int, int, int, int, int>& key
     return TD_OK;
 }
 
-// The engine's books of every launch of a Winograd sequence (wino_run's hook): its speed-of-light class, the FLOPs it executes and
-// the bytes it moves. Model: P = 16 or 36 plane products of [T x cin] x [cin x cout]; V / M are P T rows (F(2x2): 4x the input /
-// output, F(4x4): 2.25x the padded ones), each crossing HBM once per direction. A device row count: the mask-head class, time only.
+// The engine's books of every launch of a Winograd sequence (wino_run's hook): a class bracket per step, priced by launch_cost.h
 struct WinoBooks {
     td_engine* e;
     hipStream_t s;
-    const WinoRun& r;
-    std::optional<ClassScope> cs;
+    const ConvSite& site;
+    const ConvPath& path;
+    bool head_fused;
+    std::optional<ProfScope> ps;
     static void begin(void* ctx, int step, long long n) {
         WinoBooks& k = *static_cast<WinoBooks*>(ctx);
-        const WinoRun& r = k.r;
-        if (r.m_dyn) {
-            k.cs.emplace(k.e, k.s, TD_CLS_MASK_HEAD, 0.0, 0.0);
-            return;
-        }
-        const bool f22 = r.form == CONV_WINO22;
-        const double P = f22 ? 16.0 : 36.0;
-        const double T = f22 ? (double)n : (double)r.B * ((r.H + 3) / 4) * ((r.W + 3) / 4);     // F(2x2): the slab's tiles
-        const double share = f22 ? 1.0 : (double)n / r.B;                                         // folded F(4x4): the image group's part
-        const double px = (double)r.B * r.H * r.W;
-        // (split planes: the twin bank crosses as 6 bytes per weight; six bf16 MFMAs per 16 k = 6/16 of the fp32 pipe time)
-        const bool splitp = r.form == CONV_WINO43 && r.U_split;
-        const double xb = 4.0 * px * r.cin, yb = 4.0 * px * r.cout, ub = (splitp ? 6.0 : 4.0) * P * r.cout * r.cin;
-        const double vb = 4.0 * P * T * r.cin, mb = 4.0 * P * T * r.cout, pf = 2.0 * P * T * (double)r.cin * r.cout * (splitp ? 6.0 / 16.0 : 1.0);
-        if (step == WINO_STEP_INPUT) {
-            k.cs.emplace(k.e, k.s, TD_CLS_WINO_XFORM, 0.0, (xb + vb) * share);
-        } else if (step == WINO_STEP_GEMM) {
-            // (folded: V and U in, y out; F(2x2) with the input transform inside: x in place of V)
-            k.cs.emplace(k.e, k.s, TD_CLS_WINO_GEMM, pf * share,
-                         r.form == CONV_WINO43_FOLD ? (vb + yb) * share + ub : (f22 && r.fused_input ? xb : vb) + ub + mb);
-        } else if (r.head_w) {
-            k.cs.emplace(k.e, k.s, TD_CLS_WINO_XFORM, 2.0 * px * r.head_n * r.cout, mb + (4.0 * px * r.head_n + 4.0 * r.head_n * r.cout));
-        } else {
-            k.cs.emplace(k.e, k.s, TD_CLS_WINO_XFORM, 0.0, mb + yb);
-        }
+        k.ps.emplace(k.e, k.s, wino_step_cost(k.site, k.path, k.e->wino_fused, k.head_fused, step, n));
     }
-    static void end(void* ctx) { static_cast<WinoBooks*>(ctx)->cs.reset(); }
+    static void end(void* ctx) { static_cast<WinoBooks*>(ctx)->ps.reset(); }
 };
-
-td_status run_wino(td_engine* e, const WinoRun& r, hipStream_t s) {
-    if (!e->prof) return wino_run(r, s);
-    WinoBooks books{e, s, r, std::nullopt};
-    const WinoHook hook{&books, WinoBooks::begin, WinoBooks::end};
-    return wino_run(r, s, &hook);
-}
 
 ConvLayerFacts layer_facts(const ConvLayer& L) {
     return {L.cout, L.cin, L.kh, L.kw, L.scale != nullptr, L.out_f32, L.wino_u != nullptr, L.wino_u43 != nullptr, L.w_split != nullptr || L.wino_u43_split != nullptr};
 }
 
-// One contraction of the forward: ask conv_path which form the layer takes, measure the block tile of the launch shape it names,
-// book the launch, launch. head (optional): the 1x1 layer that is this layer's only consumer — *head_fused tells the caller
-// whether it rode along (head_y written, y_ not) or still needs a launch of its own.
+// One contraction of the forward: ask conv_path which form the layer takes, measure the block tile of the launch shape it names
+// (tuning launches enter no books), book the launch (launch_cost.h), launch. head (optional): the 1x1 layer that is this layer's
+// only consumer — *head_fused tells the caller whether it rode along (head_y written, y_ not) or still needs a launch of its own.
 td_status run_conv(td_engine* e, const ConvLayer& L, const void* x_, int B_, int H_, int W_, int stride, int pad, bool relu, void* y_,
                    const void* res_, int res_shift, hipStream_t s_, const int* m_dyn = nullptr, int m_mul = 1, int out_mode = 0,
                    const ConvLayer* head = nullptr, float* head_y = nullptr, bool* head_fused = nullptr) {
@@ -949,16 +917,11 @@ td_status run_conv(td_engine* e, const ConvLayer& L, const void* x_, int B_, int
     const ConvSite site{layer_facts(L), B_, H_, W_, stride, pad, relu, res_ != nullptr, out_mode, m_dyn != nullptr, m_mul,
                         head != nullptr, head ? layer_facts(*head) : ConvLayerFacts{}};
     const ConvPath path = conv_path(conv_rules(e), site);
-    const bool split = path.form == CONV_SPLIT, use_wino = path.form >= CONV_WINO22, use_43 = path.form >= CONV_WINO43;
+    const bool use_wino = path.form >= CONV_WINO22, use_43 = path.form >= CONV_WINO43;
     const int Ho = (H_ + 2 * pad - L.kh) / stride + 1, Wo = (W_ + 2 * pad - L.kw) / stride + 1;
-    const double M = (double)B_ * Ho * Wo, K = (double)L.kh * L.kw * L.cin;
-    const double flops = 2.0 * M * L.cout * K;
-    const double es = prec_ == TD_PRECISION_FP16 ? 2.0 : 4.0;
-    // (a split layer's filters cross as three bf16 pieces: 6 bytes per weight)
-    const double bytes = es * ((double)B_ * H_ * W_ * L.cin / (stride * stride) + M * L.cout * (res_ ? 2.0 : 1.0)) + (split ? 6.0 : es) * L.cout * K;
     td_status st2;
     ConvArgs ca{};          // the direct launch (tuned tile, fused head below)
-    ca.x = x_; ca.w = L.w; ca.w_frag = L.w_frag; ca.w_split = split ? L.w_split : nullptr; ca.scale = L.scale; ca.bias = L.bias; ca.res = res_; ca.y = y_;
+    ca.x = x_; ca.w = L.w; ca.w_frag = L.w_frag; ca.w_split = path.form == CONV_SPLIT ? L.w_split : nullptr; ca.scale = L.scale; ca.bias = L.bias; ca.res = res_; ca.y = y_;
     ca.B = B_; ca.H = H_; ca.W = W_; ca.Cin = L.cin; ca.Cout = L.cout; ca.KH = L.kh; ca.KW = L.kw;
     ca.stride = stride; ca.pad = pad; ca.Ho = Ho; ca.Wo = Wo;
     ca.res_shift = res_shift; ca.relu = relu ? 1 : 0; ca.out_mode = out_mode;
@@ -974,7 +937,7 @@ td_status run_conv(td_engine* e, const ConvLayer& L, const void* x_, int B_, int
     if (path.tune) {
         const auto key = std::make_tuple(path.key[0], path.key[1], path.key[2], path.key[3], path.key[4]);
         if (use_wino) {     // the batched plane contraction is a launch shape of its own; timed inside the whole sequence, head apart
-            auto wino = [&](int c) { WinoRun q = wr; q.gemm_cfg = c; return run_wino(e, q, s_); };
+            auto wino = [&](int c) { WinoRun q = wr; q.gemm_cfg = c; return wino_run(q, s_); };
             st2 = tuned_cfg(e, key, prec_, use_43 ? wino43_plane_args(wr) : wino_plane_args(wr, path.key[3], 0), s_, wino, &wr.gemm_cfg);
         } else {
             auto direct = [&](int c) { ConvArgs a = ca; a.tile_cfg = c; return conv2d_launch(a, prec_, s_); };
@@ -982,35 +945,17 @@ td_status run_conv(td_engine* e, const ConvLayer& L, const void* x_, int B_, int
         }
         if (st2 < 0) return st2;
     }
-    // the head rides along: by the rule, or (bit-identical either way) when the measured tile owns all 256 output channels. Its
-    // FLOPs / bytes join this launch's; its own input read and this layer's output write disappear.
+    // the head rides along: by the rule, or (bit-identical either way) when the measured tile owns all 256 output channels
     const bool fuse_head = path.head == HEAD_IN_TRANSFORM || (path.head == HEAD_IF_TILE_OWNS_256 && conv_head_capable(ca.tile_cfg, prec_));
     if (head_fused) *head_fused = fuse_head;
-    const double hflops = fuse_head ? 2.0 * M * head->cout * L.cout : 0.0, hbytes = fuse_head ? 4.0 * M * head->cout + es * head->cout * L.cout : 0.0;
-    ProfScope ps(e, s_, m_dyn ? 7 : 0, m_dyn ? 0.0 : flops, m_dyn ? 0.0 : bytes);
-    if (e->prof && !m_dyn) {          // category 8: FLOPs the MFMA pipe really executes
-        const double padded = use_43 ? (double)(((H_ + 3) / 4) * 4) * (((W_ + 3) / 4) * 4) / ((double)H_ * W_) : 1.0;
-        // (a split launch: six bf16 MFMAs, 192 pipe cycles, per 16 k against 512 for the fp32 MFMAs — its pipe time in units of the fp32 rate)
-        e->prof_flops[8] += use_43 ? flops * padded * 0.25 * (path.split_planes ? 6.0 / 16.0 : 1.0) : (use_wino ? flops * 4.0 / 9.0 : (split ? flops * 6.0 / 16.0 : flops));
-        e->prof_launches[8] += use_wino ? 1 : 0;
-    }
-    if (e->prof && fuse_head) {
-        e->prof_flops[0] += hflops;
-        e->prof_flops[8] += hflops;
-        e->prof_launches[0] += 1;          // two layers of the reference in one launch: "launches" keeps counting layers
-        e->prof_bytes[0] += hbytes + es * M * L.cout;       // the unfused pair's algorithmic bytes (every tensor of every layer once)
-    }
+    ProfScope ps(e, s_, conv_cost(prec_, site, path, fuse_head));        // a Winograd layer: the sequence; its steps book their classes
     if (use_wino) {
         if (fuse_head) { wr.head_w = static_cast<const float*>(head->w); wr.head_b = head->bias; wr.head_y = head_y; wr.head_n = head->cout; }
-        return run_wino(e, wr, s_);
+        WinoBooks books{e, s_, site, path, fuse_head, std::nullopt};
+        const WinoHook hook{&books, WinoBooks::begin, WinoBooks::end};
+        return wino_run(wr, s_, e->prof ? &hook : nullptr);
     }
-    const int cls = m_dyn ? TD_CLS_MASK_HEAD : (H_ == 1 && W_ == 1 ? TD_CLS_FC : (L.kh == 1 && L.kw == 1 ? TD_CLS_CONV1X1 : TD_CLS_CONV3X3));
-    if (fuse_head) {
-        ca.head_w = head->w; ca.head_b = head->bias; ca.head_y = head_y; ca.head_n = head->cout;
-        ClassScope cs(e, s_, cls, flops + hflops, bytes - es * M * L.cout + hbytes);
-        return conv2d_launch(ca, prec_, s_);
-    }
-    ClassScope cs(e, s_, cls, m_dyn ? 0.0 : (split ? flops * 6.0 / 16.0 : flops), m_dyn ? 0.0 : bytes);
+    if (fuse_head) { ca.head_w = head->w; ca.head_b = head->bias; ca.head_y = head_y; ca.head_n = head->cout; }
     return conv2d_launch(ca, prec_, s_);
 }
 
@@ -1040,23 +985,13 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
         ConvArgs a{};
         a.B = B; a.Cin = Ls[0]->cin; a.Cout = 256; a.KH = a.KW = 3; a.stride = 1; a.pad = 1; a.relu = relu ? 1 : 0; a.m_mul = 1; a.nlev = nl;
         a.tile_cfg = 17;
-        double flops = 0.0, bytes = 0.0, unfused_bytes = 0.0;
         for (int l = 0; l < nl; ++l) {
             a.lev[l].x = xs[l]; a.lev[l].w = Ls[l]->w; a.lev[l].bias = Ls[l]->bias;
             a.lev[l].y = ys ? ys[l] : nullptr; a.lev[l].head_y = head_ys ? head_ys[l] : nullptr;
             a.lev[l].H = Hs[l]; a.lev[l].W = Ws[l];
-            const double M = (double)B * Hs[l] * Ws[l], K = 9.0 * a.Cin;
-            flops += 2.0 * M * 256 * K + (head ? 2.0 * M * head->cout * 256 : 0.0);
-            bytes += 2.0 * (M * a.Cin + (head ? 0.0 : M * 256) + 256 * K) + (head ? 4.0 * M * head->cout + 2.0 * head->cout * 256 : 0.0);
-            unfused_bytes += head ? 2.0 * 2.0 * M * 256 : 0.0;          // the 256-channel map written and read back by a separate head
         }
         if (head) { a.head_w = head->w; a.head_b = head->bias; a.head_n = head->cout; }
-        ProfScope ps(e, s_, 0, flops, bytes + unfused_bytes);
-        if (e->prof) {
-            e->prof_flops[8] += flops;
-            e->prof_launches[0] += nl * (head ? 2 : 1) - 1;      // "launches" keeps counting the reference's layers
-        }
-        ClassScope cs(e, s_, TD_CLS_CONV3X3, flops, bytes);
+        ProfScope ps(e, s_, grouped_cost(B, a.Cin, Hs, Ws, nl, head ? head->cout : 0));
         return conv_pp8_grouped_launch(a, s_);
     };
     // conv2 (3x3) → conv3 (1x1) + shortcut + ReLU of a bottleneck block as one launch (bottleneck_tail_kernel)
@@ -1069,29 +1004,11 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
         a.w3 = blk.c3.w; a.scale3 = blk.c3.scale; a.bias3 = blk.c3.bias; a.res = shortcut_; a.y = y_;
         a.B = B_; a.H = H_; a.W = W_; a.MID = blk.c2.cout; a.COUT = blk.c3.cout; a.M = B_ * H_ * W_;
         if (split_) a.w2_split = blk.c2.w_tail_split;
-        const double M = (double)a.M, mid = a.MID, co = a.COUT, es = prec == TD_PRECISION_FP16 ? 2.0 : 4.0;
-        // (the split 3x3: six bf16 MFMAs per 16 k — its pipe time in units of the fp32 rate, as run_conv counts a split layer; its
-        // filters cross as three bf16 pieces: 6 bytes per weight)
-        const double f2 = 2.0 * M * mid * (9.0 * mid), f2pipe = split_ ? f2 * 6.0 / 16.0 : f2, w2b = (split_ ? 6.0 : es) * 9.0 * mid * mid;
         if (mid_out_) {
             a.mid_out = static_cast<float*>(mid_out_);
             a.w3 = nullptr; a.scale3 = nullptr; a.bias3 = nullptr; a.res = nullptr; a.y = nullptr;
-            const double bytes = es * 2.0 * M * mid + w2b;         // t1 in, t2 out, conv2's bank
-            ProfScope ps(e, s_, 0, f2, bytes);
-            if (e->prof) e->prof_flops[8] += f2pipe;
-            ClassScope cs(e, s_, TD_CLS_CONV3X3, f2pipe, bytes);
-            return bottleneck_tail_launch(a, prec, s_);
         }
-        const double f3 = 2.0 * M * co * mid, flops = f2 + f3;
-        const double bytes = es * (M * mid + 2.0 * M * co + co * mid) + w2b;       // t1 in, shortcut in, y out, both filter banks
-        ProfScope ps(e, s_, 0, flops, bytes);
-        if (e->prof) {
-            e->prof_flops[8] += f2pipe + f3;
-            e->prof_launches[0] += 1;          // two layers of the reference in one launch: keep "launches" = layers
-            // the unfused pair's algorithmic bytes (what `bytes` of category 0 means: every tensor of every LAYER once)
-            e->prof_bytes[0] += es * 2.0 * M * mid;
-        }
-        ClassScope cs(e, s_, TD_CLS_TAIL, f2pipe + f3, bytes);
+        ProfScope ps(e, s_, tail_cost(prec, a.M, a.MID, a.COUT, split_, mid_out_ != nullptr));
         return bottleneck_tail_launch(a, prec, s_);
     };
     // ---- backbone ------------------------------------------------------------------------------------------
@@ -1127,10 +1044,10 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
             if ((st = maxpool3x3s2_launch(stem_sub, pool_sub, nb_img, Hp / 2, Wp / 2, e->stem_c, prec, s)) < 0) return st; }
         }
         if (!PH(0)) continue;
-        if (!trunk_group && sb >= B) trunk_group.emplace(e, s, 0, 0.0, 0.0, true);
+        if (!trunk_group && sb >= B) trunk_group.emplace(e, s, 0, true);
         const void* x = pool_sub;
         int xh = hs[0], xw = wsz[0];
-        ProfScope backbone_group(e, s, 0, 0.0, 0.0, true);
+        ProfScope backbone_group(e, s, 0, true);
         for (int si = 0; si < 4; ++si) {
             const int nb = (int)e->stages[si].size();
             const int oh = hs[si], ow = wsz[si];
@@ -1182,7 +1099,7 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
     if (PH(0)) {
     // ---- FPN (top-down; the nearest-2x upsampled add rides in the lateral conv's epilogue) ---------------------
     {
-    ProfScope fpn_group(e, s, 0, 0.0, 0.0, true);
+    ProfScope fpn_group(e, s, 0, true);
     // fp16: the four output convs do not depend on each other (only the lateral sums chain top-down), so the laterals run first
     // and the outputs follow as one grouped launch
     const bool group_fpn = prec == TD_PRECISION_FP16 && e->group_levels && groupable(e->fpn_out[0]) && groupable(e->fpn_out[1]) &&
@@ -1203,7 +1120,7 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
     if ((st = subsample2_launch(e->pfeat[3], e->pfeat[4], B, hs[3], wsz[3], e->fpn_c, prec, s)) < 0) return st; }
     // ---- RPN -----------------------------------------------------------------------------------------------------
     {
-        ProfScope rpn_group(e, s, 0, 0.0, 0.0, true);
+        ProfScope rpn_group(e, s, 0, true);
         const bool group_rpn = prec == TD_PRECISION_FP16 && e->group_levels && e->fuse_head && groupable(e->rpn_conv) && e->rpn_head.cin == 256 &&
                                e->rpn_head.kh == 1 && e->rpn_head.kw == 1 && e->rpn_head.cout <= 32 && e->rpn_head.out_f32 && !e->rpn_head.scale;
         if (group_rpn) {
@@ -1275,7 +1192,7 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
     }   // phase 1
     if (PH(2)) {
     {
-    ProfScope box_group(e, s, 0, 0.0, 0.0, true);
+    ProfScope box_group(e, s, 0, true);
     if ((st = run_conv(e, e->fc1, e->pooled7, B * P, 1, 1, 1, 0, true, e->fc1_out, nullptr, 0, s)) < 0) return st;
     if ((st = run_conv(e, e->fc2, e->fc1_out, B * P, 1, 1, 1, 0, true, e->fc2_out, nullptr, 0, s)) < 0) return st;
     if ((st = run_conv(e, e->pred, e->fc2_out, B * P, 1, 1, 1, 0, false, e->pred_out, nullptr, 0, s)) < 0) return st;
@@ -1302,7 +1219,7 @@ td_status forward_impl(td_engine* e, unsigned phase_mask, hipStream_t s) {
     const void* mx = e->pooled14;
     void* mbuf[2] = {e->mbuf0, e->mbuf1};
     {
-    ProfScope mask_group(e, s, 7, 0.0, 0.0, true);
+    ProfScope mask_group(e, s, 7, true);
     for (int i = 0; i < 4; ++i) {
         if ((st = run_conv(e, e->mask_fcn[i], mx, mrows, 14, 14, 1, 1, true, mbuf[i & 1], nullptr, 0, s, e->total_rows, 196)) < 0) return st;
         mx = mbuf[i & 1];
@@ -1453,15 +1370,7 @@ td_status td_engine_profile_enable(td_engine* e, int enable) {
 
 td_status td_engine_profile_classes(td_engine* e, double* ms, int64_t* launches, double* exec_flops, double* bytes, double* tmin_ms, int reset) {
     TD_REQUIRE(e, "td_engine_profile_classes: null engine");
-    for (auto& r : e->cls_recs) {
-        TD_HIP_CHECK(hipEventSynchronize(r.b));
-        float t = 0.f;
-        TD_HIP_CHECK(hipEventElapsedTime(&t, r.a, r.b));
-        e->cls_ms[r.cls] += t;
-        e->prof_free.push_back(r.a);
-        e->prof_free.push_back(r.b);
-    }
-    e->cls_recs.clear();
+    if (td_status st = drain_recs(e, e->cls_recs, e->cls_ms); st < 0) return st;
     for (int c = 0; c < TD_PROF_CLASSES; ++c) {
         if (ms) ms[c] = e->cls_ms[c];
         if (launches) launches[c] = e->cls_launches[c];
@@ -1479,15 +1388,7 @@ td_status td_engine_profile_classes(td_engine* e, double* ms, int64_t* launches,
 
 td_status td_engine_profile_read(td_engine* e, double* ms, int64_t* launches, double* flops, double* bytes, int reset) {
     TD_REQUIRE(e, "td_engine_profile_read: null engine");
-    for (auto& r : e->prof_recs) {
-        TD_HIP_CHECK(hipEventSynchronize(r.b));
-        float t = 0.f;
-        TD_HIP_CHECK(hipEventElapsedTime(&t, r.a, r.b));
-        e->prof_ms[r.cat] += t;
-        e->prof_free.push_back(r.a);
-        e->prof_free.push_back(r.b);
-    }
-    e->prof_recs.clear();
+    if (td_status st = drain_recs(e, e->prof_recs, e->prof_ms); st < 0) return st;
     for (int c = 0; c < TD_PROF_CATEGORIES; ++c) {
         if (ms) ms[c] = e->prof_ms[c];
         if (launches) launches[c] = e->prof_launches[c];

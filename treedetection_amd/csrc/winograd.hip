@@ -6,7 +6,7 @@
 // with 4/9 of the direct convolution's multiplies; they run as ONE batched launch of conv_igemm_kernel (blockIdx.y =
 // xi, 1x1 "convolution" over the plane V_xi), so the MFMA path, its tiles and its tuner are reused. V and M are four
 // times the size of the layer's input / output: the engine therefore walks a layer in SLABS of a few thousand tiles
-// (engine.cpp run_wino) whose V and M planes together stay inside the 256 MiB Infinity Cache — the transforms then hand
+// (engine.cpp run_conv) whose V and M planes together stay inside the 256 MiB Infinity Cache — the transforms then hand
 // over on-die and only the layer's own input and output cross HBM. This file holds the two transforms:
 //   wino_input_kernel   x [B,H,W,C]      → V [16][T][C]      (32 add/sub per patch and channel)
 //   wino_output_kernel  M [16][T][N]     → y [B,H,W,N] = act((A^T M A) * scale + bias)   (24 add/sub per tile and channel)
