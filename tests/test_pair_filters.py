@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from oracle import postprocess_ref as O
+from treedetection_amd import box_pairs as BP
 from treedetection_amd import postprocessing as P
 
 import pair_cases
@@ -97,9 +98,9 @@ def no_device(monkeypatch):
     """The wrappers decide on the host, before anything touches the GPU library."""
     def fail(*a, **k):
         raise AssertionError("the device path was entered")
-    monkeypatch.setattr(P, "connected_pairs_device", fail)
-    monkeypatch.setattr(P._lib, "load", fail)
-    monkeypatch.setattr(P._lib, "stream_ptr", fail)
+    monkeypatch.setattr(BP, "connected_pairs_device", fail)
+    monkeypatch.setattr(BP._lib, "load", fail)
+    monkeypatch.setattr(BP._lib, "stream_ptr", fail)
 
 
 @pytest.mark.parametrize("what, bounds, confidences, iou_threshold", [
@@ -138,7 +139,7 @@ def test_empty_input_returns_what_the_host_functions_return(no_device):
 
 
 def test_too_many_connected_pairs_hand_back(monkeypatch, capsys):
-    monkeypatch.setattr(P, "connected_pairs_device", lambda *a, **k: None)       # what it returns above MAX_DEVICE_PAIRS
+    monkeypatch.setattr(BP, "connected_pairs_device", lambda *a, **k: None)       # what it returns above MAX_DEVICE_PAIRS
     assert P.filter_polygons_by_iou_and_area_device(BOX, [12.0, 4.0], [0.9, 0.8], 0.5, 3) is None
     assert f"more than {1 << 27} connected pairs" in capsys.readouterr().out
 

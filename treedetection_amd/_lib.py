@@ -243,6 +243,11 @@ def check(status: int, what: str = "") -> None:
         raise TdError(f"{what or 'libtreedet_hip'} failed ({status}): {msg}")
 
 
+def transform6(t):
+    """The six coefficients of an affine transform as the ``const double*`` the library takes."""
+    return (C.c_double * 6)(*[float(v) for v in t[:6]])
+
+
 CONV_FORMS = ("direct", "split", "winograd F(2x2)", "winograd F(4x4)", "winograd F(4x4) folded")   # ConvForm (csrc/conv_path.h), in order
 CONV_HEADS = ("own launch", "in the output transform", "if the tile owns 256 channels")            # ConvHead, in order
 

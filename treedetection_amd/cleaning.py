@@ -3,7 +3,7 @@
 field value stays. The crown stage's own de-duplication (postprocessing.filter_polygons_by_iou_and_area, containment) works on
 bounding boxes, which calls neighbours with overlapping boxes and disjoint outlines duplicates; this one does not.
 
-What runs where: candidate pairs come from the boxes (the sparse pair kernels of crownpairs.hip, or a host sweep); the area of
+What runs where: candidate pairs come from the boxes (box_pairs.candidate_pairs: the sparse pair kernels, or a host sweep); the area of
 the intersection of every candidate pair is one launch of ``td_ring_pairs_area_dev`` (ringiou.hip: a wave per pair, the
 fan-decomposition formula of csrc/ring_clip.h in float64) or, with ``device=None``, its host twin ``td_ring_pairs_area`` — the
 two agree bit for bit; IoU is formed here and nowhere else: ``inter / ((area_a + area_b) - inter)``; the selection loop is host
@@ -16,107 +16,13 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
+from .box_pairs import candidate_pairs, candidate_pairs_host  # noqa: F401  (re-exported)
+from .crown_device import nonempty, open_ring, pack_rings, upload_rings
 
 BELOW_ONE = float(np.nextafter(1.0, 0.0))
-MAX_BOX_SPAN = float(1 << 24)       # layer extent (in its units) up to which the float32 pair kernels serve candidate_pairs
-
-
-# ---- candidate pairs from the boxes -------------------------------------------------------------------------------------------
-def candidate_pairs_host(boxes) -> np.ndarray:
-    """int32 [k, 2], i < j, sorted: every pair of float64 boxes (x1, y1, x2, y2) that overlap with positive area — a sweep over
-    the boxes sorted by x1. Boxes with a NaN coordinate pair with nothing. Host numpy."""
-    b = np.asarray(boxes, dtype=np.float64).reshape(-1, 4)
-    n = b.shape[0]
-    if n < 2:
-        return np.zeros((0, 2), np.int32)
-    order = np.argsort(b[:, 0], kind="stable")
-    s = b[order]
-    ends = np.searchsorted(s[:, 0], s[:, 2], side="left")      # the boxes after position r with x1 < x2[r]
-    out = []
-    for r in range(n):
-        e = int(ends[r])
-        if e <= r + 1:
-            continue
-        c = s[r + 1:e]
-        hit = (np.minimum(c[:, 2], s[r, 2]) > np.maximum(c[:, 0], s[r, 0])) & (np.minimum(c[:, 3], s[r, 3]) > np.maximum(c[:, 1], s[r, 1]))
-        k = np.flatnonzero(hit)
-        if k.size:
-            j = order[r + 1 + k]
-            i = np.full(k.size, order[r])
-            out.append(np.stack([np.minimum(i, j), np.maximum(i, j)], axis=1))
-    if not out:
-        return np.zeros((0, 2), np.int32)
-    p = np.concatenate(out)
-    return p[np.lexsort((p[:, 1], p[:, 0]))].astype(np.int32)
-
-
-def _outward_f32(b: np.ndarray) -> np.ndarray:
-    """float64 boxes → float32 boxes that contain them: the lower corner rounded down, the upper corner rounded up."""
-    f = b.astype(np.float32)
-    lo, hi = f[:, :2], f[:, 2:]
-    lo = np.where(lo.astype(np.float64) > b[:, :2], np.nextafter(lo, np.float32(-np.inf)), lo)
-    hi = np.where(hi.astype(np.float64) < b[:, 2:], np.nextafter(hi, np.float32(np.inf)), hi)
-    return np.ascontiguousarray(np.concatenate([lo, hi], axis=1), dtype=np.float32)
-
-
-def candidate_pairs(boxes, device: int = 0) -> np.ndarray:
-    """int32 [k, 2], i < j, sorted: every pair whose float64 boxes overlap with positive area, possibly a few more — the pair
-    kernels of the box filters (postprocessing.connected_pairs_device: td_crown_pairs_count / td_crown_pairs_fill) asked for
-    ``iou > 0``: the boxes are taken relative to the point one unit below and left of the layer's lower-left corner (so no
-    coordinate is below 1: two float32 coordinates that differ then differ by at least 2^-23, and the product of two positive
-    overlaps cannot underflow to the 0 that ``iou > 0`` would reject) and rounded OUTWARD to float32, so rounding can only add
-    pairs; areas all 1, ``iou_threshold`` 0, ``area_threshold`` 1. When that path declines — a non-finite box, a layer wider than
-    2^24 units, a box without a finite positive float32 area, more than MAX_DEVICE_PAIRS pairs — :func:`candidate_pairs_host`
-    serves."""
-    from . import postprocessing as P
-
-    b = np.asarray(boxes, dtype=np.float64).reshape(-1, 4)
-    n = b.shape[0]
-    if n < 2:
-        return np.zeros((0, 2), np.int32)
-    why = None
-    if not np.isfinite(b).all():
-        why = "a box coordinate is not finite"
-    else:
-        rel = b - np.tile(b[:, :2].min(axis=0) - 1.0, 2)
-        if not (rel.max() <= MAX_BOX_SPAN):
-            why = f"the layer is wider than {int(MAX_BOX_SPAN)} units"
-        else:
-            bb = _outward_f32(rel)
-            why = P._boxes_declined(bb)
-    if why is None:
-        rows = P.connected_pairs_device(bb, np.ones(n, np.float16), np.float32(0.0), np.float16(1.0), device)
-        if rows is None:
-            why = f"more than {P.MAX_DEVICE_PAIRS} candidate pairs"
-    if why is not None:
-        P._decline("candidate_pairs", why)
-        return candidate_pairs_host(b)
-    row_start, cols = rows
-    i = np.repeat(np.arange(n, dtype=np.int64), np.diff(row_start))
-    keep = i < cols
-    p = np.stack([i[keep], cols[keep].astype(np.int64)], axis=1)
-    return p[np.lexsort((p[:, 1], p[:, 0]))].astype(np.int32)
 
 
 # ---- areas of ring pairs ------------------------------------------------------------------------------------------------------
-def open_ring(ring) -> np.ndarray:
-    """[m, 2] float64 without the repeated closing vertex (a closed ring, as Layer.rings() gives it, loses its last vertex)."""
-    r = np.asarray(ring, dtype=np.float64).reshape(-1, 2)
-    if r.shape[0] >= 2 and r[0, 0] == r[-1, 0] and r[0, 1] == r[-1, 1]:
-        r = r[:-1]
-    return r
-
-
-def pack_rings(rings: Sequence) -> Tuple[np.ndarray, np.ndarray]:
-    """Open rings concatenated for td_ring_pairs_area: (xy float64 [total, 2], start int64 [n + 1])."""
-    opened = [open_ring(r) for r in rings]
-    start = np.zeros(len(opened) + 1, np.int64)
-    if opened:
-        np.cumsum([r.shape[0] for r in opened], out=start[1:])
-    xy = np.concatenate(opened) if opened and start[-1] else np.zeros((0, 2))
-    return np.ascontiguousarray(xy, dtype=np.float64), start
-
-
 def ring_pairs_area_packed(xy_a, start_a, xy_b, start_b, pairs, device: Optional[int] = 0, host_for_capped: bool = True):
     """td_ring_pairs_area_dev (``device``: a GPU index) or td_ring_pairs_area (``device=None``) on packed rings →
     (out float64 [k, 3] = inter, |area_a|, |area_b|; status int32 [k]). Pairs the kernel leaves to the host (status 1: more than
@@ -132,31 +38,24 @@ def ring_pairs_area_packed(xy_a, start_a, xy_b, start_b, pairs, device: Optional
         if st.ndim != 1 or st.size < 1 or st[0] != 0 or (np.diff(st) < 0).any() or st[-1] != xy.shape[0]:
             raise ValueError(f"ring_pairs_area_packed: start_{who} must rise from 0 to the {xy.shape[0]} vertices of xy_{who}")
     k, n_a, n_b = pairs.shape[0], start_a.size - 1, start_b.size - 1
-    out = np.full((k, 3), np.nan)
-    status = np.zeros(k, np.int32)
+    out, status = np.full((k, 3), np.nan), np.zeros(k, np.int32)
     if k == 0:
         return out, status
     lib = _lib.load()
 
     def host(sel_pairs, sel_out, sel_status):
-        # (an empty vertex array still needs a pointer the library accepts)
-        pa = xy_a if xy_a.size else np.zeros((1, 2))
-        pb = xy_b if xy_b.size else np.zeros((1, 2))
-        _lib.check(lib.td_ring_pairs_area(pa.ctypes.data, start_a.ctypes.data, n_a, pb.ctypes.data, start_b.ctypes.data, n_b,
-                                          sel_pairs.ctypes.data, sel_pairs.shape[0], sel_out.ctypes.data, sel_status.ctypes.data),
-                   "td_ring_pairs_area")
+        _lib.check(lib.td_ring_pairs_area(nonempty(xy_a).ctypes.data, start_a.ctypes.data, n_a, nonempty(xy_b).ctypes.data, start_b.ctypes.data, n_b,
+                                          sel_pairs.ctypes.data, sel_pairs.shape[0], sel_out.ctypes.data, sel_status.ctypes.data), "td_ring_pairs_area")
 
     if device is None:
         host(pairs, out, status)
         return out, status
     import torch
-
     dev = torch.device("cuda", device)
     with torch.cuda.device(dev):
-        up = lambda a: torch.from_numpy(a if a.size else np.zeros(2, a.dtype)).to(dev)
-        d_xa, d_sa = up(xy_a), up(start_a)
-        d_xb, d_sb = (d_xa, d_sa) if same else (up(xy_b), up(start_b))
-        d_p = up(pairs)
+        d_xa, d_sa = upload_rings(xy_a, start_a, dev)
+        d_xb, d_sb = (d_xa, d_sa) if same else upload_rings(xy_b, start_b, dev)
+        d_p = torch.from_numpy(pairs).to(dev)
         d_o = torch.empty((k, 3), dtype=torch.float64, device=dev)
         d_s = torch.empty(k, dtype=torch.int32, device=dev)
         _lib.check(lib.td_ring_pairs_area_dev(d_xa.data_ptr(), d_sa.data_ptr(), n_a, d_xb.data_ptr(), d_sb.data_ptr(), n_b, d_p.data_ptr(), k,
@@ -179,9 +78,8 @@ def iou_of(areas: np.ndarray) -> np.ndarray:
 def ring_pairs_iou(rings_a: Sequence, rings_b: Sequence, pairs, device: Optional[int] = 0) -> Tuple[np.ndarray, np.ndarray]:
     """Polygon IoU of ring pairs → (iou float64 [k], areas float64 [k, 3] = inter, |area_a|, |area_b|). ``pairs``: [k, 2], an
     index into ``rings_a`` and one into ``rings_b`` (the same list twice for pairs within one layer); rings are [m, 2] vertex
-    arrays, closed or open, simple, either winding. ``device``: a GPU index, or None for the host function (same bits). Raises
-    ValueError for a pair the library refuses: an index outside its list, a ring of fewer than 3 vertices, a non-finite
-    coordinate."""
+    arrays, closed or open, simple, either winding. ``device``: a GPU index, or None for the host function (same bits). ValueError
+    for a pair the library refuses: an index outside its list, a ring of fewer than 3 vertices, a non-finite coordinate."""
     xy_a, start_a = pack_rings(rings_a)
     xy_b, start_b = (xy_a, start_a) if rings_b is rings_a else pack_rings(rings_b)
     pairs = np.asarray(pairs, dtype=np.int32).reshape(-1, 2)

@@ -48,7 +48,7 @@ def tile_polygons_json(regions: np.ndarray, offsets: np.ndarray, bits: np.ndarra
     scores = np.ascontiguousarray(scores, dtype=np.float32)
     classes = np.ascontiguousarray(classes[:n], dtype=np.int32)
     words = np.ascontiguousarray(bits).view(np.uint32).reshape(-1)
-    tr = (C.c_double * 6)(*[float(v) for v in transform[:6]])
+    tr = _lib.transform6(transform)
     need = C.c_int64(0)
     cap = 1 << 20
     while True:
@@ -76,7 +76,7 @@ def tile_prediction_file(device: int, regions: np.ndarray, offsets: np.ndarray, 
     classes = np.ascontiguousarray(classes[:n], dtype=np.int32)
     words = rows_host.view(np.uint32).reshape(-1)
     assert words.flags.c_contiguous
-    tr = (C.c_double * 6)(*[float(v) for v in transform[:6]])
+    tr = _lib.transform6(transform)
     wrote = C.c_int64(0)
     st = lib.td_tile_prediction_file(int(device), regions.ctypes.data, offsets.ctypes.data, int(bits_dev_ptr), words.ctypes.data,
                                      words.size, scores.ctypes.data, classes.ctypes.data, n, tr,
@@ -122,7 +122,7 @@ def tile_polygons_json_dev(points: np.ndarray, det_info: np.ndarray, contour_inf
     scores = np.ascontiguousarray(scores, dtype=np.float32)
     classes = np.ascontiguousarray(classes[:n], dtype=np.int32)
     words = None if bits is None else np.ascontiguousarray(bits).view(np.uint32).reshape(-1)
-    tr = (C.c_double * 6)(*[float(v) for v in transform[:6]])
+    tr = _lib.transform6(transform)
     need = C.c_int64(0)
     cap = 1 << 20
     while True:

@@ -69,8 +69,6 @@ __global__ __launch_bounds__(AB_ROWS) void box_pairs_ab_kernel(const AbArgs A) {
     if (!FILL && found) atomicAdd(&A.counts[i], found);
 }
 
-bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
-
 td_status check_sets(const char* who, const double* boxes_a, int n_a, const double* boxes_b, int n_b) {
     TD_REQUIRE(n_a >= 1 && n_b >= 1, "%s: n_a = %d, n_b = %d, at least one box is needed on either side", who, n_a, n_b);
     TD_REQUIRE(n_a <= AB_MAX_N && n_b <= AB_MAX_N, "%s: n_a = %d, n_b = %d, at most %d boxes on either side fit one launch", who, n_a, n_b,

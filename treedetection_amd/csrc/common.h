@@ -40,6 +40,7 @@ int td_polygons_json_text(const int32_t* mask_region, const int64_t* mask_offset
 td_status td_decode_ticket(hipStream_t s, int** ticket, int* cus);
 
 static inline int td_cdiv(int a, int b) { return (a + b - 1) / b; }
+inline bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }     // for pointers read as float4 / double2
 
 // ---- convolution (conv_igemm.hip) -------------------------------------------------------------
 struct ConvArgs {

@@ -118,8 +118,6 @@ __global__ __launch_bounds__(PAIR_ROWS) void crown_pairs_kernel(const PairArgs A
 
 dim3 pair_grid(int n) { return dim3(td_cdiv(n, PAIR_ROWS), td_cdiv(n, PAIR_CHUNK)); }
 
-bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
-
 }  // namespace
 
 extern "C" td_status td_crown_pairs_count(const float* boxes, const uint16_t* areas_f16, int n, float iou_threshold,

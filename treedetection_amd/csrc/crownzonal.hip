@@ -28,6 +28,7 @@
 // raster by atomic maximum (the inverse question: which crown owns this pixel).
 #include "common.h"
 #include "crown_zonal.h"
+#include "wave_f64.h"
 
 namespace {
 
@@ -68,25 +69,6 @@ struct ZonalArgs {
     int32_t* pos;
     int32_t* status;
 };
-
-__device__ __forceinline__ double wave_min(double v) {
-    for (int d = 32; d >= 1; d >>= 1) {
-        const double o = __shfl_xor(v, d);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-    for (int d = 32; d >= 1; d >>= 1) {
-        const double o = __shfl_xor(v, d);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
 
 // Crown q's ring, checked and closed into L.ring[0 .. *m] → its status (0, 1 over ZN_CAP, 2 refused); with status 0 also its
 // float64 bounding box, the same in every lane. start is checked before any vertex is read. (Args: ZonalArgs or LabelArgs.)

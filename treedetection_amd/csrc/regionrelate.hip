@@ -24,6 +24,7 @@
 // list. What an inconsistent index does to the ANSWER is not defined, which is why the entry point can check one first.
 #include "common.h"
 #include "geom_predicates.h"
+#include "wave_f64.h"
 
 namespace {
 
@@ -60,20 +61,6 @@ struct RelLds {
     int cand[RR_CCAP];
 };
 
-__device__ __forceinline__ double wave_min(double v) {
-    for (int d = 32; d >= 1; d >>= 1) {
-        const double o = __shfl_xor(v, d);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-    for (int d = 32; d >= 1; d >>= 1) {
-        const double o = __shfl_xor(v, d);
-        v = o > v ? o : v;
-    }
-    return v;
-}
 __device__ __forceinline__ bool rr_finite(double v) { return v - v == 0.0; }
 
 __device__ __forceinline__ int bin_of(const Rel& R, double y) { return relate_bin_of(y, R.ymin, R.inv_h, R.n_bins); }
@@ -389,8 +376,6 @@ __global__ void region_index_check_kernel(Rel R, int32_t* verdict) {
     }
     if (bad) atomicOr(verdict, bad);
 }
-
-bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
 }  // namespace
 

@@ -14,6 +14,7 @@
 // or a non-finite coordinate — out is NaN.
 #include "common.h"
 #include "ring_clip.h"
+#include "wave_f64.h"
 
 namespace {
 
@@ -29,25 +30,6 @@ struct RingLds {
     double x[RING_CAP];
     double y[RING_CAP];
 };
-
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int d = 32; d >= 1; d >>= 1) v = v + __shfl_xor(v, d);
-    return v;
-}
-__device__ __forceinline__ double wave_min(double v) {
-    for (int d = 32; d >= 1; d >>= 1) {
-        const double o = __shfl_xor(v, d);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-    for (int d = 32; d >= 1; d >>= 1) {
-        const double o = __shfl_xor(v, d);
-        v = o > v ? o : v;
-    }
-    return v;
-}
 
 // one ring into LDS as it lies in memory; → this lane's share of its bounding box, and whether a coordinate was not finite
 __device__ __forceinline__ bool load_ring(const double* __restrict__ xy, int64_t first, int cnt, int lane, double* x, double* y, double* box) {
@@ -141,8 +123,6 @@ __global__ __launch_bounds__(64 * RING_WPB) void ring_pairs_kernel(const double*
         }
     }
 }
-
-bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
 }  // namespace
 

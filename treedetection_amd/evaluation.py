@@ -2,7 +2,7 @@
 ``load_predictions``, ``clip_predictions``, ``calculate_iou``, ``evaluate`` and the loop of its ``main``): IoU-matched precision /
 recall / F1 / mean IoU per confidence threshold and per IoU threshold, and the TP / FP / FN lists per crown.
 
-What runs where: the candidate pairs between the two sets come from their float64 boxes — ``td_box_pairs_ab_count`` /
+What runs where: the candidate pairs between the two sets come from their float64 boxes (box_pairs.box_pairs_ab) — ``td_box_pairs_ab_count`` /
 ``td_box_pairs_ab_fill`` (boxpairs_ab.hip), or with ``device=None`` the host twin ``td_box_pairs_ab``, the same set for any input;
 the intersection area of every candidate pair is one launch of ``td_ring_pairs_area_dev`` (or its host twin, same bits:
 cleaning.ring_pairs_area_packed); IoU is formed in cleaning.iou_of and nowhere else. That sparse IoU matrix of an image is
@@ -32,6 +32,8 @@ import numpy as np
 
 from . import _lib
 from . import cleaning as CL
+from .box_pairs import box_pairs_ab
+from .crown_device import pack_rings, packed_boxes, ring_boxes  # noqa: F401  (ring_boxes: re-exported)
 
 DEFAULT_CONFIDENCE_THRESHOLDS = (0.3, 0.4, 0.5, 0.6, 0.7, 0.8, 0.9)
 DEFAULT_FILTER_PROPERTIES = (("Area", 0.0, True),)
@@ -40,91 +42,7 @@ SCORE_FIELD = "Confidence_score"
 Matrix = Tuple[np.ndarray, np.ndarray, np.ndarray]      # row_start int64 [m + 1], cols int32, iou float64
 
 
-# ---- candidate pairs between two box sets -----------------------------------------------------------------------------------
-def _boxes(b) -> np.ndarray:
-    b = np.ascontiguousarray(b, dtype=np.float64)
-    if b.size == 0:
-        return np.zeros((0, 4))
-    if b.ndim != 2 or b.shape[1] != 4:
-        raise ValueError(f"box_pairs_ab: boxes must be [n, 4] (x1, y1, x2, y2), got shape {b.shape}")
-    return b
-
-
-def _pairs_of_rows(counts: np.ndarray, cols: np.ndarray, n_b: int) -> np.ndarray:
-    i = np.repeat(np.arange(counts.size, dtype=np.int64), counts)
-    key = i * max(n_b, 1) + cols
-    order = np.argsort(key, kind="stable")
-    return np.stack([i[order], cols[order].astype(np.int64)], axis=1).astype(np.int32)
-
-
-def _box_pairs_ab_host(a: np.ndarray, b: np.ndarray) -> np.ndarray:
-    lib = _lib.load()
-    counts = np.zeros(a.shape[0], np.int32)
-    _lib.check(lib.td_box_pairs_ab(a.ctypes.data, a.shape[0], b.ctypes.data, b.shape[0], counts.ctypes.data, None, 0), "td_box_pairs_ab")
-    total = int(counts.sum(dtype=np.int64))
-    cols = np.zeros(max(total, 1), np.int32)
-    _lib.check(lib.td_box_pairs_ab(a.ctypes.data, a.shape[0], b.ctypes.data, b.shape[0], counts.ctypes.data, cols.ctypes.data, total),
-               "td_box_pairs_ab")
-    return _pairs_of_rows(counts, cols[:total], b.shape[0])
-
-
-def box_pairs_ab(boxes_a, boxes_b, device: Optional[int] = 0) -> np.ndarray:
-    """int32 [k, 2], sorted lexicographically: every (i, j) whose float64 boxes ``boxes_a[i]`` and ``boxes_b[j]`` (x1, y1, x2, y2)
-    overlap with positive area — the pair rule of include/treedet.h: comparisons only, nothing rounded, a box with a NaN pairs with
-    nothing, touching boxes are no pair. ``device``: a GPU index (td_box_pairs_ab_count, a prefix sum, td_box_pairs_ab_fill), or
-    None for the host twin td_box_pairs_ab — the same set. The device path leaves more than postprocessing.MAX_DEVICE_PAIRS pairs
-    to the host twin; an empty set on either side is no launch."""
-    a, b = _boxes(boxes_a), _boxes(boxes_b)
-    n_a, n_b = a.shape[0], b.shape[0]
-    if n_a == 0 or n_b == 0:
-        return np.zeros((0, 2), np.int32)
-    if device is None:
-        return _box_pairs_ab_host(a, b)
-    import torch
-
-    from . import postprocessing as P
-
-    lib = _lib.load()
-    dev = torch.device("cuda", device)
-    with torch.cuda.device(dev):
-        d_a, d_b = torch.from_numpy(a).to(dev), torch.from_numpy(b).to(dev)
-        counts = torch.empty(n_a, dtype=torch.int32, device=dev)
-        _lib.check(lib.td_box_pairs_ab_count(d_a.data_ptr(), n_a, d_b.data_ptr(), n_b, counts.data_ptr(), _lib.stream_ptr()),
-                   "td_box_pairs_ab_count")
-        row_start = torch.zeros(n_a + 1, dtype=torch.int64, device=dev)
-        torch.cumsum(counts, 0, dtype=torch.int64, out=row_start[1:])
-        total = int(row_start[-1].item())
-        if total > P.MAX_DEVICE_PAIRS:
-            P._decline("box_pairs_ab", f"more than {P.MAX_DEVICE_PAIRS} candidate pairs")
-            return _box_pairs_ab_host(a, b)
-        if total == 0:
-            return np.zeros((0, 2), np.int32)
-        cols = torch.empty(total, dtype=torch.int32, device=dev)
-        cursor = torch.empty(n_a, dtype=torch.int32, device=dev)
-        _lib.check(lib.td_box_pairs_ab_fill(d_a.data_ptr(), n_a, d_b.data_ptr(), n_b, row_start.data_ptr(), cursor.data_ptr(), cols.data_ptr(),
-                                            _lib.stream_ptr()), "td_box_pairs_ab_fill")
-        h_counts, h_cols = counts.cpu().numpy(), cols.cpu().numpy()
-    return _pairs_of_rows(h_counts, h_cols, n_b)
-
-
 # ---- the sparse IoU matrix of an image ----------------------------------------------------------------------------------------
-def packed_boxes(xy: np.ndarray, start: np.ndarray) -> np.ndarray:
-    """float64 [n, 4] (x1, y1, x2, y2) of rings packed as cleaning.pack_rings packs them; a ring without vertices gets a NaN box
-    (it pairs with nothing), and so does a ring with a NaN coordinate."""
-    n = start.size - 1
-    out = np.full((n, 4), np.nan)
-    full = np.flatnonzero(np.diff(start) > 0)
-    if full.size:                                   # (reduceat over the non-empty rings: their segments follow one another in xy)
-        out[full, :2] = np.minimum.reduceat(xy, start[full], axis=0)
-        out[full, 2:] = np.maximum.reduceat(xy, start[full], axis=0)
-    return out
-
-
-def ring_boxes(rings: Sequence) -> np.ndarray:
-    """:func:`packed_boxes` of a list of rings (closed or open)."""
-    return packed_boxes(*CL.pack_rings(rings))
-
-
 def crown_iou_matrix(pred_rings: Sequence, ann_rings: Sequence, device: Optional[int] = 0) -> Matrix:
     """The IoU of every prediction with every annotation it overlaps, as CSR rows over the predictions → (row_start int64 [m + 1],
     cols int32 = annotation indices, ascending within a row, iou float64): :func:`box_pairs_ab` on the rings' boxes,
@@ -133,8 +51,8 @@ def crown_iou_matrix(pred_rings: Sequence, ann_rings: Sequence, device: Optional
     ``device``: a GPU index, or None for the host functions — the same matrix bit for bit. ValueError for a candidate pair the
     area function refuses (a ring of fewer than 3 vertices, a non-finite coordinate)."""
     m = len(pred_rings)
-    xy_a, start_a = CL.pack_rings(pred_rings)
-    xy_b, start_b = CL.pack_rings(ann_rings)
+    xy_a, start_a = pack_rings(pred_rings)
+    xy_b, start_b = pack_rings(ann_rings)
     pairs = box_pairs_ab(packed_boxes(xy_a, start_a), packed_boxes(xy_b, start_b), device)
     if pairs.shape[0] == 0:
         return np.zeros(m + 1, np.int64), np.zeros(0, np.int32), np.zeros(0)

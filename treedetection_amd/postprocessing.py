@@ -1,25 +1,19 @@
-"""Crown post-processing (reference TreeDetection/postprocessing.py): confidence / area filters, box-IoU
-de-duplication, per-crown height and NDVI statistics from the nDSM and RGBI rasters, height / NDVI / border / containment
-selection, attributes (Area, TreeHeight, Centroid, Diameter, is_contained, num_contained) and the ``processed_*.gpkg``
-layers — the only consumer of the nDSM side band.
+"""Crown post-processing (reference TreeDetection/postprocessing.py): confidence / area filters, box-IoU de-duplication, per-crown
+height and NDVI statistics from the nDSM and RGBI rasters, height / NDVI / border / containment selection, attributes (Area,
+TreeHeight, Centroid, Diameter, is_contained, num_contained) and the ``processed_*.gpkg`` layers — the only consumer of the nDSM
+side band. This is the top of the crown stage: the device wrappers it calls lie below it, in crown_rasters.py,
+box_pairs.py and cleaning.py on crown_device.py, and their names are imported here, where callers have always found them.
 
-What runs where: the per-crown raster statistics — in the reference a cupy test of every crown against EVERY pixel —
-are one launch of ``td_crown_stats`` per raster (libtreedet_hip.so; a workgroup per crown over its circle's bounding
-box, same membership arithmetic; with ``crown_statistics: polygon`` instead one launch of ``td_crown_zonal_dev`` per raster over the
-pixels inside each crown's OUTLINE, a wave per crown — :func:`crown_zonal_stats`; off by default: same files); the N x N box
-filters and the selection rules are small host numpy, written to follow the reference line by line *including* its quirks,
-which are listed in DESIGN.md §7 and marked ``# ref:`` below; with
-``device_filters: true`` the pair tests of the two box filters run on the GPU and only the sparse result comes back
-(``td_crown_pairs_count`` / ``td_crown_pairs_fill``, crownpairs.hip; same arithmetic, same results); with ``clean_crowns: true`` the
-layer is first thinned by the IoU of the crown OUTLINES (:mod:`treedetection_amd.cleaning`; off by default: same files); with
-``crown_rasters: height | image`` a uint32 label raster of the layer's crowns is drawn on the GPU and written beside it
-(``td_crown_labels_dev``, :func:`crown_label_raster`, :func:`write_crown_raster`; off by default: no such file, same layers).
-GDAL's bilinear decimation of the rasters (``ndvi_scaling_factor`` 0.2 in the example config) is restated from its
-published algorithm (:func:`resample_bilinear_gdal`, both directions); with ``device_decode: true`` the rasters are decoded in
-HBM and the same taps are applied there, NDVI included (:func:`resample_on_device`, ``td_resample_gdal_dev``). Not reproduced: fiona's
-schema handling (the layer is written by
-:mod:`treedetection_amd.gpkg`), and cupy's float32 reduction order for mean / variance / centroid (accumulated in
-float64, rounded once). The reference holds no fixture for this stage: parity is unpinned (oracle/postprocess_ref.py).
+What runs where: the raster statistics — in the reference a cupy test of every crown against EVERY pixel — are one launch per raster
+(bounding circles; ``crown_statistics: polygon``: the OUTLINES); the N x N box filters and the selection rules are small host numpy
+that follows the reference line by line *including* its quirks (marked ``# ref:`` below); opt-in, same files without:
+``device_filters: true`` (the filters' pair tests on the GPU), ``clean_crowns: true`` (the layer thinned by outline IoU first),
+``crown_rasters: height | image`` (a uint32 label raster written beside the layer, :func:`write_crown_raster`). GDAL's bilinear
+decimation of the rasters (``ndvi_scaling_factor`` 0.2 in the example config) is restated from its published algorithm
+(:func:`resample_bilinear_gdal`); with ``device_decode: true`` the rasters are decoded in HBM and the same taps applied there, NDVI
+included (:func:`resample_on_device`). Not reproduced: fiona's schema handling (:mod:`treedetection_amd.gpkg` writes the layer) and
+cupy's float32 reduction order for mean / variance / centroid (accumulated in float64, rounded once). The reference holds no fixture
+for this stage: parity is unpinned (oracle/postprocess_ref.py).
 """
 from __future__ import annotations
 
@@ -34,7 +28,11 @@ import torch
 import yaml
 
 from . import _lib
-from .geotiff import GeoTiff, device_decode_long_jpeg_setting, device_decode_planar_setting, device_decode_setting
+from .box_pairs import MAX_DEVICE_PAIRS, connected_pairs_device, containment_device, filter_polygons_by_iou_and_area_device, greedy_removal  # noqa: F401
+from .cleaning import clean_crowns, clean_crowns_setting
+from .crown_device import pack_rings, upload_rings
+from .crown_rasters import _window, crown_circles, crown_label_raster, crown_priorities, crown_stats, crown_zonal_stats, labels_from_priorities  # noqa: F401
+from .geotiff import GeoTiff, device_decode_long_jpeg_setting, device_decode_planar_setting, device_decode_setting, write_geotiff
 from .gpkg import polygon_blob, read_layer, write_blobs
 from .stitching import simplify_ring
 
@@ -54,24 +52,6 @@ def _cfg(config, key):
 
 
 # ---- rasters ---------------------------------------------------------------------------------------------
-def _geo_to_raster(t, x, y) -> Tuple[int, int]:
-    """utilities.geo_to_raster: (int(row), int(col)), truncation toward zero."""
-    if t[0] == 0 or t[4] == 0:
-        raise ValueError(f"Affine transform scaling factors are zero: {t[0]}, {t[4]}")
-    return int((y - t[5]) / t[4]), int((x - t[2]) / t[0])
-
-
-def _window(transform, n_rows, n_cols, bounds) -> Tuple[int, int, int, int]:
-    """The reference's subset of a raster for ``bounds`` (postprocessing.py:45-57; its row / col names are swapped
-    twice and cancel): (row_lo, col_lo, row_hi, col_hi)."""
-    minx, miny, maxx, maxy = bounds
-    r_a, c_a = _geo_to_raster(transform, minx, miny)
-    r_b, c_b = _geo_to_raster(transform, maxx, maxy)
-    c_lo, c_hi = sorted([min(c_a, n_cols - 1), max(c_b, 0)])
-    r_lo, r_hi = sorted([min(r_a, n_rows - 1), max(r_b, 0)])
-    return r_lo, c_lo, r_hi, c_hi
-
-
 def _decimation_weights(n_src: int, n_dst: int):
     """Taps of GDAL's convolution resampler for a bilinear (triangle) kernel when shrinking n_src → n_dst pixels
     (gcore/overview.cpp GDALResampleChunk_Convolution: kernel radius 1 stretched by the decimation ratio, weights
@@ -202,51 +182,6 @@ def resample_on_device(tensor: torch.Tensor, out_h: int, out_w: int, bands: Sequ
     return dst      # (tmp and the tables go back to torch's allocator on the stream the kernels run on: reuse is ordered after them)
 
 
-def crown_circles(rings: Sequence[np.ndarray]) -> np.ndarray:
-    """[n,3] float32 (cx, cy, r): centre of the bounding box of the float32 vertex coordinates and the largest vertex
-    distance from it (postprocessing.py:79-95)."""
-    out = np.zeros((len(rings), 3), np.float32)
-    for i, r in enumerate(rings):
-        x, y = r[:, 0].astype(np.float32), r[:, 1].astype(np.float32)
-        cx = (x.min() + x.max()) / np.float32(2)
-        cy = (y.min() + y.max()) / np.float32(2)
-        dx, dy = x - cx, y - cy
-        out[i] = (cx, cy, np.sqrt(dx ** 2 + dy ** 2).max())
-    return out
-
-
-def crown_stats(raster, transform, bounds, circles: np.ndarray, mode: int, radius_scale: float = 1.0,
-                device: int = 0, clamp_shape: Optional[Tuple[int, int]] = None) -> np.ndarray:
-    """td_crown_stats over one raster → [n,3] (mode 0: max height, x, y) or [n,4] (mode 1: NDVI min, max, mean, var).
-    ``raster``: a numpy array [rows, cols] (copied to ``device``), or a contiguous float32 CUDA tensor [rows, cols] (a raster
-    decoded in HBM, GeoTiff.decode_to_device), which the kernel reads where it lies."""
-    n = circles.shape[0]
-    cols_out = 3 if mode == 0 else 4
-    if n == 0:
-        return np.zeros((0, cols_out), np.float32)
-    on_device = isinstance(raster, torch.Tensor)
-    if on_device and not (raster.is_cuda and raster.dtype == torch.float32 and raster.dim() == 2 and raster.is_contiguous()):
-        raise ValueError(f"crown_stats: a raster tensor must be a contiguous float32 CUDA tensor [rows, cols], got {raster.dtype} "
-                         f"{tuple(raster.shape)} on {raster.device}")
-    rows, cols = raster.shape
-    cr, cc = clamp_shape if clamp_shape else (rows, cols)
-    r_lo, c_lo, r_hi, c_hi = _window(transform, cr, cc, bounds)
-    r_hi, c_hi = min(r_hi, rows - 1), min(c_hi, cols - 1)
-    lib = _lib.load()
-    import ctypes as C
-    dev = raster.device if on_device else torch.device("cuda", device)
-    d_r = raster if on_device else torch.from_numpy(np.ascontiguousarray(raster, dtype=np.float32)).to(dev)
-    d_c = torch.from_numpy(np.ascontiguousarray(circles, dtype=np.float32)).to(dev)
-    d_o = torch.empty((n, cols_out), dtype=torch.float32, device=dev)
-    tr = (C.c_double * 6)(*[float(v) for v in transform[:6]])
-    win = (C.c_int32 * 4)(r_lo, c_lo, r_hi, c_hi)
-    with torch.cuda.device(dev):
-        _lib.check(lib.td_crown_stats(d_r.data_ptr(), rows, cols, tr, win, d_c.data_ptr(), n, mode, float(radius_scale),
-                                      d_o.data_ptr(), _lib.stream_ptr()), "td_crown_stats")
-    return d_o.cpu().numpy()
-
-
-# ---- zonal statistics over the crown outlines (opt-in: ``crown_statistics: polygon``) ------------------------------------------
 def crown_statistics_setting(value="circle") -> str:
     """The ``crown_statistics`` config key: "circle" (default, also for None: the reference's bounding circles, td_crown_stats) or
     "polygon" (the pixels whose centres lie inside the crown's outline, td_crown_zonal_dev). Anything else is refused."""
@@ -256,75 +191,6 @@ def crown_statistics_setting(value="circle") -> str:
     return value
 
 
-def _zonal_raster_check(raster) -> None:
-    if isinstance(raster, torch.Tensor) and not (raster.is_cuda and raster.dtype == torch.float32 and raster.dim() == 2 and raster.is_contiguous()):
-        raise ValueError(f"crown_zonal_stats: a raster tensor must be a contiguous float32 CUDA tensor [rows, cols], got {raster.dtype} "
-                         f"{tuple(raster.shape)} on {raster.device}")
-
-
-def _zonal_host(raster: np.ndarray, transform, xy: np.ndarray, start: np.ndarray):
-    """td_crown_zonal on host arrays → (out float32 [n, 4], pos int32 [n, 3], status int32 [n])."""
-    import ctypes as C
-    n = start.size - 1
-    out, pos, status = np.empty((n, 4), np.float32), np.empty((n, 3), np.int32), np.empty(n, np.int32)
-    r = np.ascontiguousarray(raster, dtype=np.float32)
-    pts = xy if xy.size else np.zeros((1, 2))                # (an empty vertex array still needs a pointer the library accepts)
-    tr = (C.c_double * 6)(*[float(v) for v in transform[:6]])
-    _lib.check(_lib.load().td_crown_zonal(r.ctypes.data, r.shape[0], r.shape[1], tr, pts.ctypes.data, xy.shape[0], start.ctypes.data, n,
-                                          out.ctypes.data, pos.ctypes.data, status.ctypes.data), "td_crown_zonal")
-    return out, pos, status
-
-
-def upload_rings(xy: np.ndarray, start: np.ndarray, dev):
-    """Packed rings (cleaning.pack_rings) as the two device tensors td_crown_zonal_dev reads: upload once, pass to every launch."""
-    return (torch.from_numpy(xy if xy.size else np.zeros((1, 2))).to(dev), torch.from_numpy(start).to(dev))
-
-
-def crown_zonal_stats(raster, transform, rings, device: Optional[int] = 0, packed=None, uploaded=None):
-    """Zonal statistics of one raster over crown outlines → (stats float32 [n, 4] = min, max, mean, population variance; count
-    int32 [n]; max_pos int32 [n, 2] = raster row, column of the maximum; status int32 [n]). A pixel belongs to a crown when its
-    centre lies inside the closed ring or on it (include/treedet.h, td_crown_zonal). ``raster``: a numpy array [rows, cols]
-    (copied to ``device``), or a contiguous float32 CUDA tensor, which the kernel reads where it lies. ``rings``: [m, 2] vertex
-    arrays, closed or open, either winding. ``device``: a GPU index (td_crown_zonal_dev, a wave per crown) or None (td_crown_zonal
-    on the host: the same status, count, min, max and position). Crowns the kernel leaves out (status 1: more than
-    ``_lib.ZONAL_RING_CAP`` vertices) are decided by the host function alone and merged, status included. Refused crowns
-    (status 2: fewer than 3 vertices, a non-finite coordinate) come back as NaN / -1. ``packed`` = cleaning.pack_rings(rings) and
-    ``uploaded`` = upload_rings(*packed, dev), when the caller has them already (two rasters, one ring set)."""
-    from .cleaning import pack_rings
-    import ctypes as C
-
-    _zonal_raster_check(raster)
-    xy, start = packed if packed is not None else pack_rings(rings)
-    n = start.size - 1
-    if n == 0:
-        return np.zeros((0, 4), np.float32), np.zeros(0, np.int32), np.zeros((0, 2), np.int32), np.zeros(0, np.int32)
-    on_device = isinstance(raster, torch.Tensor)
-    if device is None:
-        out, pos, status = _zonal_host(raster.cpu().numpy() if on_device else raster, transform, xy, start)
-        return out, pos[:, 0].copy(), pos[:, 1:].copy(), status
-    rows, cols = raster.shape
-    dev = raster.device if on_device else torch.device("cuda", device)
-    with torch.cuda.device(dev):
-        d_r = raster if on_device else torch.from_numpy(np.ascontiguousarray(raster, dtype=np.float32)).to(dev)
-        d_xy, d_start = uploaded if uploaded is not None else upload_rings(xy, start, dev)
-        d_o = torch.empty((n, 4), dtype=torch.float32, device=dev)
-        d_p = torch.empty((n, 3), dtype=torch.int32, device=dev)
-        d_s = torch.empty(n, dtype=torch.int32, device=dev)
-        tr = (C.c_double * 6)(*[float(v) for v in transform[:6]])
-        _lib.check(_lib.load().td_crown_zonal_dev(d_r.data_ptr(), rows, cols, tr, d_xy.data_ptr(), xy.shape[0], d_start.data_ptr(), n,
-                                                  d_o.data_ptr(), d_p.data_ptr(), d_s.data_ptr(), _lib.stream_ptr()), "td_crown_zonal_dev")
-        out, pos, status = d_o.cpu().numpy(), d_p.cpu().numpy(), d_s.cpu().numpy()
-    capped = np.flatnonzero(status == 1)
-    if capped.size:                                          # the host function decides these crowns alone
-        sub = [xy[start[k]:start[k + 1]] for k in capped]
-        sub_start = np.zeros(capped.size + 1, np.int64)
-        np.cumsum([r.shape[0] for r in sub], out=sub_start[1:])
-        h_raster = raster.cpu().numpy() if on_device else raster
-        out[capped], pos[capped], status[capped] = _zonal_host(h_raster, transform, np.ascontiguousarray(np.concatenate(sub)), sub_start)
-    return out, pos[:, 0].copy(), pos[:, 1:].copy(), status
-
-
-# ---- crown label rasters (opt-in: ``crown_rasters``) ---------------------------------------------------------------------------
 def crown_rasters_setting(value=False):
     """The ``crown_rasters`` config key: False (default, also for None: no raster), "height" or "image" (the grid the labels are
     drawn on). Anything else is refused."""
@@ -333,121 +199,6 @@ def crown_rasters_setting(value=False):
     if not isinstance(value, str) or value not in ("height", "image"):
         raise ValueError(f"crown_rasters must be false, 'height' or 'image', got {value!r}")
     return value
-
-
-def _u32_values(values, n: int) -> np.ndarray:
-    """``values`` as uint32 [n]: integers in [0, 2^32) only."""
-    v = np.asarray(values)
-    if n == 0 and v.size == 0:
-        return np.zeros(0, np.uint32)
-    if v.shape != (n,) or v.dtype.kind not in "iu":
-        raise ValueError(f"crown_label_raster: values must be {n} unsigned integers below 2^32, got {v.dtype} {v.shape}")
-    if n and (int(v.min()) < 0 or int(v.max()) >= 1 << 32):
-        raise ValueError("crown_label_raster: values must be unsigned integers below 2^32")
-    return np.array(v, dtype=np.uint32)                      # (a copy of its own: writable, C-contiguous)
-
-
-def _labels_host(labels: np.ndarray, transform, xy: np.ndarray, start: np.ndarray, values: np.ndarray) -> np.ndarray:
-    """td_crown_labels over ``labels`` (uint32 [rows, cols], C-contiguous) in place → status int32 [n]."""
-    import ctypes as C
-    n = start.size - 1
-    status = np.empty(n, np.int32)
-    pts = xy if xy.size else np.zeros((1, 2))                # (an empty vertex array still needs a pointer the library accepts)
-    vals = values if n else np.zeros(1, np.uint32)
-    tr = (C.c_double * 6)(*[float(v) for v in transform[:6]])
-    _lib.check(_lib.load().td_crown_labels(labels.shape[0], labels.shape[1], tr, pts.ctypes.data, xy.shape[0], start.ctypes.data,
-                                           vals.ctypes.data, n, labels.ctypes.data, status.ctypes.data), "td_crown_labels")
-    return status
-
-
-def crown_label_raster(rings, values, transform, shape, device: Optional[int] = 0, out=None, packed=None, uploaded=None):
-    """Crown outlines drawn into a label raster → (labels uint32 [rows, cols], status int32 [n]):
-    ``labels[r, c] = max(labels before, max{values[q] : the centre of pixel (r, c) belongs to ring q})`` (include/treedet.h,
-    td_crown_labels; membership is crown_zonal_stats's). The maximum is unsigned and order-free, so the raster is the same bits on
-    the host and on the device. ``values``: one unsigned integer below 2^32 per ring (anything else: ValueError); 0 draws nothing.
-    ``transform``, ``shape`` = (rows, cols): the grid. ``device``: None — td_crown_labels on numpy arrays; ``out``, a C-contiguous
-    uint32 array [rows, cols], is composited over in place. A GPU index — td_crown_labels_dev, a wave per crown, on a tensor that is
-    allocated and zeroed unless ``out`` is given: a contiguous CUDA tensor [rows, cols] of 32-bit integers (int32 holds the bits
-    where torch.uint32 lacks an op), drawn over where it lies and returned as it is; without ``out`` the labels come back as a
-    numpy uint32 array. Crowns the kernel leaves out (status 1: more than ``_lib.ZONAL_RING_CAP`` vertices) are drawn by the host
-    function after the download and merged with np.maximum — the same raster, the rule being order-free —, their status the
-    host's. Refused crowns (status 2) draw nothing. ``packed`` / ``uploaded`` as for crown_zonal_stats."""
-    from .cleaning import pack_rings
-    import ctypes as C
-
-    xy, start = packed if packed is not None else pack_rings(rings)
-    n = start.size - 1
-    vals = _u32_values(values, n)
-    rows, cols = int(shape[0]), int(shape[1])
-    if rows < 1 or cols < 1 or rows * cols >= 1 << 31:
-        raise ValueError(f"crown_label_raster: a {rows} x {cols} raster: both at least 1 and fewer than 2^31 pixels")
-    if device is None:
-        if out is None:
-            out = np.zeros((rows, cols), np.uint32)
-        elif not (isinstance(out, np.ndarray) and out.dtype == np.uint32 and out.shape == (rows, cols) and out.flags.c_contiguous):
-            raise ValueError(f"crown_label_raster: out must be a C-contiguous uint32 array [{rows}, {cols}]")
-        return out, _labels_host(out, transform, xy, start, vals)
-    given = out is not None
-    if given and not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype in (torch.int32, torch.uint32) and tuple(out.shape) == (rows, cols)
-                      and out.is_contiguous()):
-        raise ValueError(f"crown_label_raster: out must be a contiguous int32 / uint32 CUDA tensor [{rows}, {cols}]")
-    dev = out.device if given else torch.device("cuda", device)
-    with torch.cuda.device(dev):
-        d_l = out if given else torch.zeros((rows, cols), dtype=torch.int32, device=dev)
-        if n == 0:
-            return (d_l if given else np.zeros((rows, cols), np.uint32)), np.zeros(0, np.int32)
-        d_xy, d_start = uploaded if uploaded is not None else upload_rings(xy, start, dev)
-        d_v = torch.from_numpy(vals.view(np.int32)).to(dev)
-        d_s = torch.empty(n, dtype=torch.int32, device=dev)
-        tr = (C.c_double * 6)(*[float(v) for v in transform[:6]])
-        _lib.check(_lib.load().td_crown_labels_dev(rows, cols, tr, d_xy.data_ptr(), xy.shape[0], d_start.data_ptr(), d_v.data_ptr(), n,
-                                                   d_l.data_ptr(), d_s.data_ptr(), _lib.stream_ptr()), "td_crown_labels_dev")
-        status = d_s.cpu().numpy()
-        capped = np.flatnonzero(status == 1)
-        if not capped.size:
-            return (d_l if given else d_l.cpu().numpy().view(np.uint32)), status
-        # the host function draws these crowns alone, into a raster of their own; the maximum of the two is the whole rule
-        sub = [xy[start[k]:start[k + 1]] for k in capped]
-        sub_start = np.zeros(capped.size + 1, np.int64)
-        np.cumsum([r.shape[0] for r in sub], out=sub_start[1:])
-        extra = np.zeros((rows, cols), np.uint32)
-        status[capped] = _labels_host(extra, transform, np.ascontiguousarray(np.concatenate(sub)), sub_start, np.ascontiguousarray(vals[capped]))
-        merged = np.maximum(d_l.cpu().numpy().view(np.uint32), extra)
-        if not given:
-            return merged, status
-        d_l.copy_(torch.from_numpy(merged.view(np.int32)).to(dev).view(d_l.dtype))
-        return d_l, status
-
-
-def crown_priorities(scores, labels=None):
-    """Distinct drawing priorities for crowns that may overlap → (priority uint32 [n], table uint32 [n + 1]). The higher score gets
-    the higher priority; among equal scores the LOWER index does; the priorities are 1 .. n, so under crown_label_raster's maximum
-    a pixel goes to the best crown that holds it. ``table[priority[k]] = labels[k]`` (default k + 1) and ``table[0] = 0`` take a
-    raster of composited priorities back to labels (labels_from_priorities). NaN scores are refused."""
-    s = np.asarray(scores, dtype=np.float64).reshape(-1)
-    n = s.size
-    if np.isnan(s).any():
-        raise ValueError("crown_priorities: a score is NaN")
-    if n >= (1 << 31) - 1:
-        raise ValueError("crown_priorities: too many crowns")
-    order = np.lexsort((-np.arange(n), s))                  # ascending score; among equal scores descending index
-    priority = np.empty(n, np.uint32)
-    priority[order] = np.arange(1, n + 1, dtype=np.uint32)
-    table = np.zeros(n + 1, np.uint32)
-    table[priority] = np.arange(1, n + 1, dtype=np.uint32) if labels is None else _u32_values(labels, n)
-    return priority, table
-
-
-def labels_from_priorities(raster, table: np.ndarray):
-    """A raster of composited priorities (crown_label_raster over crown_priorities' values) → the labels, ``table[raster]``. A CUDA
-    tensor of 32-bit integers is looked up on the device, through 32-bit indices — no temporary larger than the raster — and comes
-    back as a tensor of the same dtype; a numpy array gives a numpy uint32 array."""
-    table = np.ascontiguousarray(table, dtype=np.uint32)
-    if isinstance(raster, torch.Tensor):
-        d_t = torch.from_numpy(table.view(np.int32)).to(raster.device)
-        idx = raster.view(torch.int32).reshape(-1)          # priorities are at most n < 2^31: the bits are the index
-        return torch.index_select(d_t, 0, idx).view(raster.dtype).reshape(raster.shape)
-    return table[np.asarray(raster)]
 
 
 # ---- box filters (host numpy, the reference's dtypes) -------------------------------------------------------
@@ -500,142 +251,6 @@ def containment(bounds, threshold):
     is_c[np.arange(n), np.arange(n)] = False
     num = is_c.sum(axis=1)
     return ([float(ratios[:, j].max()) for j in range(n)], [bool(is_c[:, j].any()) for j in range(n)], [int(v) for v in num])
-
-
-# ---- the same two filters with the pair tests on the GPU (crownpairs.hip; opt-in: ``device_filters: true``) ------------------
-MAX_DEVICE_PAIRS = 1 << 27      # connected pairs the device path stores (512 MB of int32 indices); beyond it the host function serves
-
-
-def _decline(who: str, why: str) -> None:
-    print(f"{who}: {why}: using the host function")
-
-
-def _boxes_declined(bb: np.ndarray) -> Optional[str]:
-    """Why the pair kernels must not see these float32 boxes (they skip disjoint pairs, which is only the reference's answer for
-    finite boxes of finite positive area), or None."""
-    if not np.isfinite(bb).all():
-        return "a box coordinate is not finite"
-    with np.errstate(over="ignore", invalid="ignore"):
-        area = (bb[:, 2] - bb[:, 0]) * (bb[:, 3] - bb[:, 1])
-    if not (np.isfinite(area) & (area > 0)).all():
-        return "a box has no finite positive float32 area"
-    return None
-
-
-def _weak_threshold(threshold, dtype):
-    """``threshold`` in the type numpy compares an array of ``dtype`` with it in — ``dtype`` itself for a Python number (and for a
-    numpy scalar that does not widen it) — or None when the comparison would run in a wider type than the kernels compute in."""
-    if np.result_type(dtype, threshold) != dtype:
-        return None
-    with np.errstate(over="ignore"):
-        return dtype(threshold)
-
-
-def connected_pairs_device(bb: np.ndarray, ar: np.ndarray, iou_thr: np.float32, area_thr: np.float16, device: int = 0):
-    """The de-duplication mask of :func:`filter_polygons_by_iou_and_area` as sparse rows: (row_start int64 [n + 1], cols int32
-    [row_start[n]]) — the j != i with ``mask[i][j]``, row i in ``cols[row_start[i]:row_start[i + 1]]`` in no particular order — or
-    None when there are more than MAX_DEVICE_PAIRS of them. td_crown_pairs_count, a prefix sum, td_crown_pairs_fill. ``bb``: float32
-    [n, 4], n >= 1; ``ar``: float16 [n]. The preconditions are the caller's (:func:`filter_polygons_by_iou_and_area_device`)."""
-    n = bb.shape[0]
-    lib = _lib.load()
-    dev = torch.device("cuda", device)
-    with torch.cuda.device(dev):
-        d_b = torch.from_numpy(np.ascontiguousarray(bb, dtype=np.float32)).to(dev)
-        d_a = torch.from_numpy(np.ascontiguousarray(ar, dtype=np.float16)).to(dev)
-        counts = torch.empty(n, dtype=torch.int32, device=dev)
-        thr_bits = int(np.float16(area_thr).view(np.uint16))
-        _lib.check(lib.td_crown_pairs_count(d_b.data_ptr(), d_a.data_ptr(), n, float(np.float32(iou_thr)), thr_bits, counts.data_ptr(),
-                                            0.0, None, None, _lib.stream_ptr()), "td_crown_pairs_count")
-        row_start = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-        torch.cumsum(counts, 0, dtype=torch.int64, out=row_start[1:])
-        total = int(row_start[-1].item())
-        if total > MAX_DEVICE_PAIRS:
-            return None
-        cols = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
-        if total:
-            cursor = torch.empty(n, dtype=torch.int32, device=dev)
-            _lib.check(lib.td_crown_pairs_fill(d_b.data_ptr(), d_a.data_ptr(), n, float(np.float32(iou_thr)), thr_bits, row_start.data_ptr(),
-                                               cursor.data_ptr(), cols.data_ptr(), _lib.stream_ptr()), "td_crown_pairs_fill")
-        return row_start.cpu().numpy(), cols[:total].cpu().numpy()
-
-
-def greedy_removal(row_start: np.ndarray, cols: np.ndarray, conf: np.ndarray, self_connected: Optional[np.ndarray] = None) -> np.ndarray:
-    """td_crown_pairs_greedy: the group loop of :func:`filter_polygons_by_iou_and_area` over sparse rows → removed bool [n].
-    ``conf``: float16 [n] without NaN; ``self_connected``: the mask's diagonal (None = set everywhere). Host code."""
-    n = len(conf)
-    rs = np.ascontiguousarray(row_start, dtype=np.int64)
-    cl = np.ascontiguousarray(cols, dtype=np.int32)
-    cf = np.ascontiguousarray(conf, dtype=np.float16)
-    sc = None if self_connected is None else np.ascontiguousarray(self_connected, dtype=np.uint8)
-    if rs.shape != (n + 1,) or (sc is not None and sc.shape != (n,)) or (n and cl.shape != (int(rs[-1]),)):
-        raise ValueError("greedy_removal: row_start needs n + 1 entries, cols row_start[n], self_connected n")
-    removed = np.zeros(n, np.uint8)
-    _lib.check(_lib.load().td_crown_pairs_greedy(rs.ctypes.data, cl.ctypes.data, cf.ctypes.data, None if sc is None else sc.ctypes.data, n,
-                                                 removed.ctypes.data), "td_crown_pairs_greedy")
-    return removed.astype(bool)
-
-
-def filter_polygons_by_iou_and_area_device(bounds, areas, confidences, iou_threshold, area_threshold, device=0) -> Optional[List[int]]:
-    """:func:`filter_polygons_by_iou_and_area` with the N x N mask replaced by td_crown_pairs_count / td_crown_pairs_fill (sparse
-    rows of connected pairs, the same float32 / float16 arithmetic) and the group loop by td_crown_pairs_greedy → the same kept
-    indices. None (one printed line) = use the host function: an input outside what the kernels were argued for — a non-finite
-    coordinate, a box without a finite positive float32 area, a NaN confidence, ``iou_threshold`` < 0, a threshold numpy would
-    compare in a wider type — or more than MAX_DEVICE_PAIRS connected pairs."""
-    who = "filter_polygons_by_iou_and_area_device"
-    n = len(areas)
-    if n == 0:
-        return []
-    bb = np.array([[np.float32(v) for v in b] for b in bounds], dtype=np.float32).reshape(-1, 4)
-    conf = np.array(confidences, dtype=np.float16)
-    ar = np.array(areas, dtype=np.float16)
-    iou_thr, area_thr = _weak_threshold(iou_threshold, np.float32), _weak_threshold(area_threshold, np.float16)
-    why = _boxes_declined(bb)
-    if why is None and np.isnan(conf).any():
-        why = "a confidence is NaN"
-    if why is None and (iou_thr is None or area_thr is None):
-        why = "a threshold is not compared in float32 / float16"
-    if why is None and iou_thr < 0:
-        why = f"iou_threshold {iou_threshold} is negative"
-    if why is not None:
-        return _decline(who, why)
-    pairs = connected_pairs_device(bb, ar, iou_thr, area_thr, device)
-    if pairs is None:
-        return _decline(who, f"more than {MAX_DEVICE_PAIRS} connected pairs")
-    # the mask's diagonal, which the sparse rows leave out: it decides how a row's own confidence ties (td_crown_pairs_greedy)
-    box_area = (bb[:, 2] - bb[:, 0]) * (bb[:, 3] - bb[:, 1])
-    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
-        diagonal = (box_area / (box_area + box_area - box_area) > iou_thr) & (np.abs(ar - ar) / np.maximum(ar, ar) < area_thr)
-    removed = greedy_removal(pairs[0], pairs[1], conf, diagonal)
-    return [int(i) for i in np.flatnonzero(~removed)]
-
-
-def containment_device(bounds, threshold, device=0):
-    """:func:`containment` with the pair tests in td_crown_pairs_count → the same triple, or None (one printed line) = use the host
-    function: a non-finite coordinate, a box without a finite positive float32 area, ``threshold`` <= 0 or compared in a wider type
-    than float32. The ratio returned is 1.0 for every box: the diagonal of the ratio matrix is exactly 1 for a finite positive area
-    and no entry exceeds it (float subtraction and multiplication are monotone, so iw * ih <= the inner box's area)."""
-    who = "containment_device"
-    b = np.array(bounds, dtype=np.float32).reshape(-1, 4)
-    n = b.shape[0]
-    if n == 0:
-        return [], [], []
-    thr = _weak_threshold(threshold, np.float32)
-    why = _boxes_declined(b)
-    if why is None and thr is None:
-        why = "the threshold is not compared in float32"
-    if why is None and thr <= 0:
-        why = f"containment_threshold {threshold} is not positive"
-    if why is not None:
-        return _decline(who, why)
-    lib = _lib.load()
-    dev = torch.device("cuda", device)
-    with torch.cuda.device(dev):
-        d_b = torch.from_numpy(np.ascontiguousarray(b)).to(dev)
-        out = torch.empty((2, n), dtype=torch.int32, device=dev)
-        _lib.check(lib.td_crown_pairs_count(d_b.data_ptr(), None, n, 0.0, 0, None, float(thr), out[0].data_ptr(), out[1].data_ptr(),
-                                            _lib.stream_ptr()), "td_crown_pairs_count")
-        num, is_c = out.cpu().numpy()
-    return [1.0] * n, [bool(v) for v in is_c], [int(v) for v in num]
 
 
 def _device_filters_on(config) -> bool:
@@ -786,7 +401,6 @@ def process_layer(rings: List[np.ndarray], scores: Sequence[Optional[float]], co
         return []
     # 4: statistics
     if zonal:         # crown_statistics: polygon — the pixels inside each outline, every raster on its own transform, no half radius
-        from .cleaning import pack_rings
         packed = pack_rings([f["ring"] for f in features])
         uploaded = upload_rings(*packed, torch.device("cuda", device))       # one upload for both launches
         hz = crown_zonal_stats(height, h_t, None, device, packed, uploaded)[0]
@@ -877,7 +491,6 @@ COLUMNS = ("Confidence_score", "poly_id", "Area", "TreeHeight", "Centroid", "Dia
 def process_single_file(file_path, processed_file_path, height_data_path, rgbi_data_path, device_id=0, config=None):
     """postprocessing.py:876-943: one stitched layer → ``processed_<name>.gpkg``; returns ``file_path`` or None on error
     (printed, like the reference)."""
-    from .cleaning import clean_crowns, clean_crowns_setting
     thin = clean_crowns_setting((config or {}).get("clean_crowns", False))      # (a bad value is refused, not printed)
     crown_statistics_setting((config or {}).get("crown_statistics", "circle"))  # (likewise)
     rasters = crown_rasters_setting((config or {}).get("crown_rasters", False)) # (likewise)
@@ -920,7 +533,6 @@ def write_crown_raster(path: str, rings, scores, grid_path: str, device: int = 0
     and EPSG from its header), label k + 1 for ``rings[k]``, 0 = no crown (GDAL_NODATA 0), tiled, LZW. Where crowns overlap, the
     higher score wins and among equal scores the lower index (crown_priorities): the priorities are composited on the GPU
     (crown_label_raster) and taken back to labels there (labels_from_priorities)."""
-    from .geotiff import write_geotiff
     g = GeoTiff(grid_path)
     rows, cols, t, epsg = g.height, g.width, g.transform, g.epsg
     g.close()

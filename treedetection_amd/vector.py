@@ -18,6 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
+from .crown_device import decline, nonempty, take_rings
 
 Polygon = List[np.ndarray]
 
@@ -225,7 +226,7 @@ class Region:
         self.last_deferred, self.last_deferred_queries = 0, np.zeros(0, dtype=np.int64)
         if n == 0 or self.n_rings == 0:
             if device is not None and n:
-                _decline("Region.relate", "the region is empty")
+                decline("Region.relate", "the region is empty")
             return flags.astype(bool), flags.astype(bool)
         qs = [np.ascontiguousarray(q, dtype=np.float64).reshape(-1, 2) for q in queries]
         q_start = np.zeros(n + 1, dtype=np.int64)
@@ -236,7 +237,7 @@ class Region:
             if why is None:
                 flags = self._relate_device(q_xy, q_start, n, int(device))
                 return (flags & 1).astype(bool), (flags & 2).astype(bool)
-            _decline("Region.relate", why)
+            decline("Region.relate", why)
         # (a ring the library refuses reaches it here, device or not, and raises there)
         self._relate_host(q_xy, q_start, n, flags)
         return (flags & 1).astype(bool), (flags & 2).astype(bool)
@@ -267,7 +268,6 @@ class Region:
 
     def _relate_device(self, q_xy, q_start, n, device: int) -> np.ndarray:
         import torch
-
         lib = _lib.load()
         dev = torch.device("cuda", device)
         with torch.cuda.device(dev):
@@ -277,7 +277,7 @@ class Region:
                 edge_ring, bin_start, bin_edges = self._index[:3]
                 R = self._on_device[device] = {"xy": up(self.xy), "ring_start": up(self.ring_start), "ring_poly": up(self.ring_poly),
                                                "edge_ring": up(edge_ring), "bin_start": up(bin_start),
-                                               "bin_edges": up(bin_edges if bin_edges.size else np.zeros(1, np.int32)),
+                                               "bin_edges": up(nonempty(bin_edges)),
                                                "n_bin_edges": int(bin_edges.size), "checked": False}
             ymin, ymax, inv_h = self._index[3:]
             d_q, d_qs = up(q_xy), up(q_start)
@@ -295,23 +295,13 @@ class Region:
         deferred = np.flatnonzero(status == 1)
         self.last_deferred, self.last_deferred_queries = int(deferred.size), deferred
         if deferred.size:
-            lens = np.diff(q_start)[deferred]
-            sub_start = np.zeros(deferred.size + 1, dtype=np.int64)
-            sub_start[1:] = np.cumsum(lens)
-            sub_xy = np.concatenate([q_xy[q_start[i]:q_start[i + 1]] for i in deferred])
             sub_flags = np.zeros(deferred.size, dtype=np.uint8)
-            self._relate_host(sub_xy, sub_start, int(deferred.size), sub_flags)
+            self._relate_host(*take_rings(q_xy, q_start, deferred), int(deferred.size), sub_flags)
             flags[deferred] = sub_flags
         return flags
 
 
 INT32_LIMIT = 2 ** 31 - 1
-
-
-def _decline(who: str, why: str) -> None:
-    from .postprocessing import _decline as decline
-
-    decline(who, why)
 
 
 def build_edge_index(xy: np.ndarray, ring_start: np.ndarray):
