@@ -718,6 +718,36 @@ td_status td_crown_labels_dev(int rows, int cols, const double* transform, const
 td_status td_crown_labels(int rows, int cols, const double* transform, const double* xy, int64_t n_xy, const int64_t* start,
                           const uint32_t* value, int n, uint32_t* labels, int32_t* status);
 
+/* Treetops in a height raster (reference supplementary/pretraining_generate_voronoi.py:32-74, 294-320: gaussian_filter, then the
+ * local maxima of a maximum_filter above a height; csrc/treetops.h is the rule, shared by both functions). raster: float32
+ * [rows][cols], fewer than 2^31 pixels. weights: HOST float64 [2 * radius + 1], the normalised 1-D Gaussian as scipy builds it, built
+ * by the caller (no exp of the C library or the device enters the result); finite and symmetric. radius = 0 with weights = [1.0]:
+ * no smoothing. window: odd k >= 1, h = k / 2. floor: float32, not NaN.
+ * Smoothing: two 1-D passes, axis 0 first, then axis 1, each output rounded to float32 once; an index outside [0, n) is reflected
+ * (d c b a | a b c d | d c b a: p = 2n, i = i mod p, i = p - 1 - i if i >= n; any n). One output, in float64, multiply and add
+ * rounded separately:  t = in[l] * w[r];  for ii = -r .. -1: t = t + (in[l+ii] + in[l-ii]) * w[r+ii];  out[l] = (float)t  —
+ * scipy.ndimage.gaussian_filter (float32 in and out) bit for bit.
+ * Treetop: with s the smoothed raster, pixel (row, col) is one iff s > floor and s >= s' for every non-NaN s' among the in-range
+ * pixels of the k x k window centred on it; a NaN s never is; every pixel of a plateau that equals its window maximum is. With
+ * NaN-free s this is argwhere((s == maximum_filter(s, size=k)) & (s > floor)). The reference applies maximum_filter to a copy with
+ * NaN where s <= 2.5 instead, which differs only where a NaN enters a window and there depends on scipy's comparison order.
+ * Out: marks uint8 [rows][cols] = 1 / 0, every pixel written; smoothed float32 [rows][cols] when non-null (a NaN is a NaN: its
+ * sign and payload are not part of the rule); counts int32 [rows] when non-null = the marks of each row.
+ * td_treetops_dev: raster, marks, smoothed, counts are DEVICE memory; one launch, a workgroup per output tile (64 x 64, or 32 x 32
+ * when radius + h > 13), the raw tile with its halo of radius + h staged in LDS, both passes and the separable maximum there — no
+ * smoothed raster travels through memory between the passes; counts is zeroed on `stream` by the call and receives one atomic add
+ * per tile row that holds a treetop; radius <= TD_TREETOP_RADIUS_CAP and window <= TD_TREETOP_WINDOW_CAP (at most 64 KB of LDS);
+ * asynchronous on `stream`. td_treetops: HOST memory, host code, any radius and window; marks and smoothed equal the device's bit
+ * for bit. Both return TD_ERR_INVALID (with a message, before anything runs) for a null raster, weights or marks, rows or cols < 1
+ * or 2^31 pixels and more, an even window or window < 1, radius < 0, a non-finite or asymmetric weight table, a NaN floor and, on
+ * the device, a parameter over its cap. */
+#define TD_TREETOP_RADIUS_CAP 8
+#define TD_TREETOP_WINDOW_CAP 15
+td_status td_treetops_dev(const float* raster, int rows, int cols, const double* weights, int radius, int window, float floor,
+                          uint8_t* marks, float* smoothed, int32_t* counts, void* stream);
+td_status td_treetops(const float* raster, int rows, int cols, const double* weights, int radius, int window, float floor,
+                      uint8_t* marks, float* smoothed, int32_t* counts);
+
 /* GDAL's separable triangle-filter resampling (src.read(out_shape=..., resampling=bilinear), reference postprocessing.py:781-797)
  * of a raster that lies in device memory, with the NDVI rule of helpers.ndvi_array_from_rgbi (880-895) fused into the second pass.
  * src: DEVICE uint8 [height][width][c] pixel-interleaved (TD_SAMPLE_U8, c <= 4) or DEVICE float32 [height][width] (TD_SAMPLE_F32,

@@ -16,3 +16,5 @@ from .engine import Engine  # noqa: F401
 from .evaluation import (box_pairs_ab, clip_predictions, crown_iou_matrix, evaluate, evaluate_dirs,  # noqa: F401
                          load_annotations, load_predictions, match_crowns)
 from .prediction import Predictor  # noqa: F401
+from .treetops import (crown_treetops, find_treetops, gaussian_weights, smooth_height, treetop_marks,  # noqa: F401
+                       treetops_file)

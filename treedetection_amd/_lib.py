@@ -29,6 +29,7 @@ RING_PAIR_CAP, RING_PAIR_WPB, RING_PAIR_GRID = 1024, 4, 2048   # ringiou.hip: ve
 # TD_RELATE_*_CAP (regionrelate.hip): points of a query ring, meeting parameters of one query edge, distinct region rings a query meets
 RELATE_QUERY_CAP, RELATE_MEET_CAP, RELATE_RING_CAP = 256, 254, 64
 ZONAL_RING_CAP = 512   # TD_ZONAL_RING_CAP (crownzonal.hip): vertices of an open crown ring the kernel holds
+TREETOP_RADIUS_CAP, TREETOP_WINDOW_CAP = 8, 15   # TD_TREETOP_*_CAP (treetops.hip): the smoothing radius and the window the kernel holds
 
 
 class TdError(RuntimeError):
@@ -122,6 +123,9 @@ SIGNATURES = {
                                       C.c_void_p, C.c_void_p, C.c_void_p]),
     "td_crown_labels": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
                                   C.c_void_p, C.c_void_p]),
+    "td_treetops_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p]),
+    "td_treetops": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "td_resample_gdal_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int]
                              + [C.c_void_p] * 4 + [C.c_int, C.c_int64] + [C.c_void_p] * 4 + [C.c_int, C.c_int64]
                              + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),

@@ -26,7 +26,11 @@ Region.relate(device=...); false: not one byte of any output changes; the tile f
 postprocessing.crown_zonal_stats; "circle": not one byte of any output changes), ``crown_rasters`` (false | "height" | "image",
 default false: beside every ``processed_<name>.gpkg`` a label raster ``processed_<name>_crowns.tif`` on the full grid of the height
 or of the image raster — uint32, label k + 1 for the k-th feature of the layer, 0 = no crown, the higher Confidence_score on top,
-drawn on the GPU a wave per crown — postprocessing.crown_label_raster; the layers are the same bytes either way).
+drawn on the GPU a wave per crown — postprocessing.crown_label_raster; the layers are the same bytes either way),
+``crown_treetops`` (true | false, default false: not one byte of any output changes; true: the treetops of the height raster's full
+grid — ``treetop_sigma`` 0.5, ``treetop_window`` 7, ``treetop_min_height`` 3.0: smoothed, then the maxima of the window above the
+height, one launch, treedetection_amd.treetops — counted per crown in an integer column ``Treetops`` of every processed feature
+and written as a point layer ``processed_<name>_treetops.gpkg`` beside the layer).
 """
 from __future__ import annotations
 
@@ -180,6 +184,7 @@ def get_config(config_path: str):
         "fp16_min_batch": 0, "device_contours": "auto", "device_decode": "auto", "device_filters": "auto",
         "device_decode_long_jpeg": False, "device_decode_planar": False, "clean_crowns": False, "device_seams": False,
         "device_outlines": False, "crown_statistics": "circle", "crown_rasters": False,
+        "crown_treetops": False, "treetop_sigma": 0.5, "treetop_window": 7, "treetop_min_height": 3.0,
     }
     for k, v in defaults.items():
         config[k] = config.get(k, v)

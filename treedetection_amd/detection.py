@@ -405,8 +405,8 @@ def postprocess_files(config):
     for name in sorted(os.listdir(pred_dir)):
         if not (name.endswith(".geojson") or name.endswith(".gpkg")) or not name.startswith("processed_"):
             continue
-        copies = [name]
-        raster = os.path.basename(crown_raster_path(name))          # ``crown_rasters``: the label raster goes next to its layer
+        copies = [name]                                             # (``crown_treetops``: processed_<name>_treetops.gpkg is one of these names itself)
+        raster =os.path.basename(crown_raster_path(name))          # ``crown_rasters``: the label raster goes next to its layer
         if crown_rasters_setting(config.get("crown_rasters", False)) and os.path.exists(os.path.join(pred_dir, raster)):
             copies.append(raster)
         for item in copies:

@@ -184,6 +184,8 @@ def exclude_outlines(config, logger=None):
         for file in sorted(os.listdir(pred_dir)):
             if not (file.endswith(".geojson") or file.endswith(".gpkg")) or not file.startswith("processed_"):
                 continue
+            if file.endswith("_treetops.gpkg"):             # ``crown_treetops``: the point layer beside a processed layer holds no crowns
+                continue
             path = os.path.join(pred_dir, file)
             try:
                 crowns = read_layer(path)

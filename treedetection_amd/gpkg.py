@@ -73,6 +73,24 @@ def parse_polygon_blob(blob: bytes) -> Tuple[int, np.ndarray]:
     return srs_id, np.frombuffer(blob, dtype="<f8", count=2 * npts, offset=off + 13).reshape(npts, 2).copy()
 
 
+def point_blob(x: float, y: float, srs_id: int) -> bytes:
+    """GeoPackage binary geometry of a point: 'GP', version 0, flags = little endian and NO envelope (the standard asks for none
+    on a point), srs id, then WKB (byte order 1, type 1, x, y)."""
+    return struct.pack("<2sBBi", b"GP", 0, 0b00000001, int(srs_id)) + struct.pack("<BIdd", 1, 1, float(x), float(y))
+
+
+def parse_point_blob(blob: bytes) -> Tuple[int, Tuple[float, float]]:
+    """Inverse of :func:`point_blob` (tests, downstream tools): → (srs_id, (x, y))."""
+    magic, version, flags, srs_id = struct.unpack_from("<2sBBi", blob, 0)
+    if magic != b"GP" or version != 0 or not (flags & 1):
+        raise ValueError("not a little-endian GeoPackage geometry blob")
+    off = 8 + {0: 0, 1: 32, 2: 48, 3: 48, 4: 64}[(flags >> 1) & 7]
+    order, gtype, x, y = struct.unpack_from("<BIdd", blob, off)
+    if order != 1 or gtype != 1:
+        raise ValueError("expected a WKB point")
+    return srs_id, (x, y)
+
+
 _SCHEMA = """
 CREATE TABLE gpkg_spatial_ref_sys (srs_name TEXT NOT NULL, srs_id INTEGER PRIMARY KEY, organization TEXT NOT NULL,
   organization_coordsys_id INTEGER NOT NULL, definition TEXT NOT NULL, description TEXT);
@@ -102,10 +120,13 @@ def write_polygons(path: str, rings: Sequence[np.ndarray], columns: Dict[str, Se
 
 
 def write_blobs(path: str, blobs: Iterable, columns: Dict[str, Sequence], epsg: Optional[int],
-                extent: Optional[Tuple[float, float, float, float]], layer: Optional[str] = None) -> None:
-    """One polygon layer from ready GeoPackage geometry blobs (bytes / memoryview, e.g. from td_stitch_tile_json).
+                extent: Optional[Tuple[float, float, float, float]], layer: Optional[str] = None, geometry_type: str = "POLYGON") -> None:
+    """One layer from ready GeoPackage geometry blobs (bytes / memoryview, e.g. from td_stitch_tile_json) of ``geometry_type``:
+    "POLYGON", the default, or "POINT" (:func:`point_blob`).
     ``columns``: name → per-feature values (float → DOUBLE, int → INTEGER, else TEXT); ``extent`` = (minx, miny, maxx,
     maxy) of the layer or None; ``epsg=None`` writes srs_id 4326 like the reference's empty frame (helpers.py:541-543)."""
+    if geometry_type not in ("POLYGON", "POINT"):
+        raise ValueError(f"write_blobs: geometry_type must be 'POLYGON' or 'POINT', got {geometry_type!r}")
     layer = layer or os.path.splitext(os.path.basename(path))[0]
     srs_id = int(epsg) if epsg else 4326
     final = path
@@ -141,11 +162,11 @@ def write_blobs(path: str, blobs: Iterable, columns: Dict[str, Sequence], epsg: 
 
         names = list(columns)
         cols_sql = "".join(f', "{n}" {sql_type(columns[n])}' for n in names)
-        con.execute(f'CREATE TABLE "{layer}" (fid INTEGER PRIMARY KEY AUTOINCREMENT NOT NULL, geom POLYGON{cols_sql})')
+        con.execute(f'CREATE TABLE "{layer}" (fid INTEGER PRIMARY KEY AUTOINCREMENT NOT NULL, geom {geometry_type}{cols_sql})')
         ext = tuple(extent) if extent else (None, None, None, None)
         con.execute("INSERT INTO gpkg_contents (table_name, data_type, identifier, description, min_x, min_y, max_x, max_y, srs_id) "
                     "VALUES (?, 'features', ?, '', ?, ?, ?, ?, ?)", (layer, layer, *ext, srs_id))
-        con.execute("INSERT INTO gpkg_geometry_columns VALUES (?, 'geom', 'POLYGON', ?, 0, 0)", (layer, srs_id))
+        con.execute("INSERT INTO gpkg_geometry_columns VALUES (?, 'geom', ?, ?, 0, 0)", (layer, geometry_type, srs_id))
         ph = ",".join("?" * (1 + len(names)))
         quoted = ", ".join(f'"{n}"' for n in names)
         # columns as plain Python lists once (numpy scalars converted here, not per row), rows by zip: a stitched layer of a

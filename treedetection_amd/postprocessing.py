@@ -8,7 +8,8 @@ What runs where: the raster statistics — in the reference a cupy test of every
 (bounding circles; ``crown_statistics: polygon``: the OUTLINES); the N x N box filters and the selection rules are small host numpy
 that follows the reference line by line *including* its quirks (marked ``# ref:`` below); opt-in, same files without:
 ``device_filters: true`` (the filters' pair tests on the GPU), ``clean_crowns: true`` (the layer thinned by outline IoU first),
-``crown_rasters: height | image`` (a uint32 label raster written beside the layer, :func:`write_crown_raster`). GDAL's bilinear
+``crown_rasters: height | image`` (a uint32 label raster written beside the layer, :func:`write_crown_raster`), ``crown_treetops:
+true`` (the treetops of the height raster counted per crown and written as a point layer, treetops.py). GDAL's bilinear
 decimation of the rasters (``ndvi_scaling_factor`` 0.2 in the example config) is restated from its published algorithm
 (:func:`resample_bilinear_gdal`); with ``device_decode: true`` the rasters are decoded in HBM and the same taps applied there, NDVI
 included (:func:`resample_on_device`). Not reproduced: fiona's schema handling (:mod:`treedetection_amd.gpkg` writes the layer) and
@@ -35,6 +36,7 @@ from .crown_rasters import _window, crown_circles, crown_label_raster, crown_pri
 from .geotiff import GeoTiff, device_decode_long_jpeg_setting, device_decode_planar_setting, device_decode_setting, write_geotiff
 from .gpkg import polygon_blob, read_layer, write_blobs
 from .stitching import simplify_ring
+from .treetops import crown_treetops, find_treetops, treetops_path, write_treetops_layer  # noqa: F401
 
 # config.py of the reference defaults none of these four (the stage raises AttributeError without them); its
 # example/config.yml sets them and documents 0.2 / 1.0 as the scaling defaults. The NDVI thresholds have no documented
@@ -201,6 +203,27 @@ def crown_rasters_setting(value=False):
     return value
 
 
+def crown_treetops_setting(config) -> Optional[dict]:
+    """The ``crown_treetops`` config key with its three parameters: None for false (the default, also for None), else the keyword
+    arguments of treetops.crown_treetops — ``treetop_sigma`` (default 0.5: a finite number, not negative), ``treetop_window`` (7: an
+    odd integer, at least 1), ``treetop_min_height`` (3.0: a number, not NaN). Anything else is refused."""
+    value = config.get("crown_treetops", False)
+    if value is None or value is False:
+        return None
+    if value is not True:
+        raise ValueError(f"crown_treetops must be true or false, got {value!r}")
+    number = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool)
+    sigma, window, floor = (config.get(k) if config.get(k) is not None else d
+                            for k, d in (("treetop_sigma", 0.5), ("treetop_window", 7), ("treetop_min_height", 3.0)))
+    if not number(sigma) or not math.isfinite(sigma) or sigma < 0:
+        raise ValueError(f"treetop_sigma must be a finite number, not negative, got {sigma!r}")
+    if not isinstance(window, (int, np.integer)) or isinstance(window, bool) or window < 1 or window % 2 == 0:
+        raise ValueError(f"treetop_window must be an odd integer, at least 1, got {window!r}")
+    if not number(floor) or math.isnan(floor):
+        raise ValueError(f"treetop_min_height must be a number, got {floor!r}")
+    return {"sigma": float(sigma), "window": int(window), "min_height": float(floor)}
+
+
 # ---- box filters (host numpy, the reference's dtypes) -------------------------------------------------------
 def _box_iou(b: np.ndarray) -> np.ndarray:
     xA = np.maximum(b[:, 0][:, None], b[:, 0])
@@ -348,9 +371,11 @@ def _ndvi_on_device(rg: GeoTiff, n_scale: float, config, device: int):
 
 # ---- one layer -----------------------------------------------------------------------------------------
 def process_layer(rings: List[np.ndarray], scores: Sequence[Optional[float]], config, height_path: str, rgbi_path: str,
-                  device: int = 0) -> List[dict]:
+                  device: int = 0, keep: Optional[dict] = None) -> List[dict]:
     """process_geojson + process_features (postprocessing.py:722-808, 478-720) for the crowns of one image → the list
-    of output features ``{"ring": [m,2], "properties": {...}}`` in the reference's order (duplicates included)."""
+    of output features ``{"ring": [m,2], "properties": {...}}`` in the reference's order (duplicates included). ``keep``: a dict
+    that receives the height raster as the statistics read it, {"height": array or CUDA tensor, "transform"}, for a caller that
+    reads it again (``crown_treetops``)."""
     device_filters = _device_filters_on(config)
     zonal = crown_statistics_setting(config.get("crown_statistics", "circle")) == "polygon"
     conf_thr, iou_thr, area_thr = _cfg(config, "confidence_threshold"), _cfg(config, "iou_threshold"), _cfg(config, "area_threshold")
@@ -377,6 +402,8 @@ def process_layer(rings: List[np.ndarray], scores: Sequence[Optional[float]], co
     h_t = (hg.transform[0] * (hg.width / height.shape[1]), hg.transform[1], hg.transform[2],
            hg.transform[3], hg.transform[4] * (hg.height / height.shape[0]), hg.transform[5])
     h_b = hg.bounds                                       # bounds: left, bottom, right, top
+    if keep is not None:
+        keep.update(height=height, transform=h_t, full_grid=tuple(height.shape) == (hg.height, hg.width))
     rg = GeoTiff(rgbi_path)
     ndvi = _ndvi_on_device(rg, n_scale, config, device)
     if ndvi is None:
@@ -494,6 +521,8 @@ def process_single_file(file_path, processed_file_path, height_data_path, rgbi_d
     thin = clean_crowns_setting((config or {}).get("clean_crowns", False))      # (a bad value is refused, not printed)
     crown_statistics_setting((config or {}).get("crown_statistics", "circle"))  # (likewise)
     rasters = crown_rasters_setting((config or {}).get("crown_rasters", False)) # (likewise)
+    tops_args = crown_treetops_setting(config or {})                             # (likewise)
+    tops, kept_raster = None, {}
     try:
         device = int(str(device_id).replace("cuda:", "") or 0) if str(device_id) != "cpu" else 0
         layer = read_layer(file_path)
@@ -502,9 +531,16 @@ def process_single_file(file_path, processed_file_path, height_data_path, rgbi_d
         if thin:        # ``clean_crowns: true``: the layer is thinned by polygon IoU first, rings and scores together (host functions)
             kept = clean_crowns(layer_rings, scores, iou_threshold=0.7, confidence=0, area_threshold=0, device=None)
             layer_rings, scores = [layer_rings[i] for i in kept], [scores[i] for i in kept]
-        feats = process_layer(layer_rings, scores, config, height_data_path, rgbi_data_path, device)
+        feats = process_layer(layer_rings, scores, config, height_data_path, rgbi_data_path, device, **({"keep": kept_raster} if tops_args else {}))
         rings = [f["ring"] for f in feats]
         cols = {c: [f["properties"][c] for f in feats] for c in COLUMNS}
+        if tops_args:   # ``crown_treetops``: a failure here is printed and costs the column and the point layer, not the layer
+            try:
+                per_crown, tops = crown_treetops(*_treetop_raster(height_data_path, kept_raster, config, device), rings,
+                                                 cols["Confidence_score"], device=device, **tops_args)
+                cols["Treetops"] = [int(v) for v in per_crown]
+            except Exception as e:
+                print(f"Error finding the treetops of {file_path}: {e}")
         if rings:
             xy = np.concatenate(rings)
             extent = (float(xy[:, 0].min()), float(xy[:, 1].min()), float(xy[:, 0].max()), float(xy[:, 1].max()))
@@ -514,6 +550,11 @@ def process_single_file(file_path, processed_file_path, height_data_path, rgbi_d
     except Exception as e:
         print(f"Error postprocessing file {file_path}: {e}")
         return None
+    if tops is not None:
+        try:
+            write_treetops_layer(treetops_path(processed_file_path), tops, layer.srs_id)
+        except Exception as e:
+            print(f"Error writing the treetops of {file_path}: {e}")
     if rasters:         # ``crown_rasters``: the layer is written; a failure here is printed and does not lose it
         try:
             write_crown_raster(crown_raster_path(processed_file_path), rings, cols.get("Confidence_score", []),
@@ -521,6 +562,22 @@ def process_single_file(file_path, processed_file_path, height_data_path, rgbi_d
         except Exception as e:
             print(f"Error writing the crown raster of {file_path}: {e}")
     return file_path
+
+
+def _treetop_raster(height_path: str, kept: dict, config, device: int):
+    """The height raster on its FULL grid for ``crown_treetops`` → (raster, transform): what process_layer's statistics read (``kept``,
+    an array or a CUDA tensor) when ``height_scaling_factor`` left the grid alone, else the file read once more at scale 1, in HBM
+    when :func:`_height_on_device` takes it."""
+    if kept.get("full_grid"):
+        return kept["height"], kept["transform"]
+    hg = GeoTiff(height_path)
+    try:
+        height = _height_on_device(hg, 1.0, config, device)
+        if height is None:
+            height = np.ascontiguousarray(hg.read()[0], dtype=np.float32)
+        return height, hg.transform
+    finally:
+        hg.close()
 
 
 def crown_raster_path(layer_path: str) -> str:
@@ -561,6 +618,8 @@ def load_recovery_data_with_params(directory, config, logger=None):
     params = {k: (v if not (isinstance(v, float) and math.isinf(v)) else str(v)) for k, v in params.items()}
     if crown_statistics_setting(config.get("crown_statistics", "circle")) == "polygon":      # (only then: "circle" files stay valid)
         params["crown_statistics"] = "polygon"
+    if crown_treetops_setting(config):                    # (likewise: layers written without the column are not taken for done)
+        params["crown_treetops"] = crown_treetops_setting(config)
     if os.path.exists(recovery_file):
         try:
             with open(recovery_file) as f:
