@@ -417,7 +417,9 @@ int64_t td_tiff_lzw_encode(const uint8_t* src, int64_t n, uint8_t* dst, int64_t 
  * each. comp: DEVICE copy of the file's compressed bytes (padded by >= 8 bytes); block_off / block_nbytes: DEVICE int64
  * [nblocks], position and size of every LZW strip / tile in comp; blocks_out: DEVICE [nblocks][block_cap] bytes, block b decoded
  * at b * block_cap (block_cap = bytes of a full block); decoded: DEVICE int64 [nblocks], status: DEVICE int32 [2 * nblocks + 1] (the
- * first nblocks entries are the blocks' status, the rest is scratch for the second pass) — bytes produced (low 32 bits; the high 32
+ * first nblocks entries are the blocks' status; behind them lies the wide-pass list, which stays readable after the launch: status[nblocks] =
+ * how many blocks the first pass left to the second one (an epoch's output outgrew the 16-bit table: a table-adding code arrived more
+ * than 65535 - 4096 bytes into it), then their block numbers in no particular order; the entries behind those are not written) — bytes produced (low 32 bits; the high 32
  * bits count the strings that were copied through memory instead of the LDS ring: a diagnostic), and 0 = ok,
  * 1 = corrupt stream, 2 = more than block_cap bytes (the rules of td_tiff_lzw_decode). Asynchronous on `stream`, whose device must be
  * the calling thread's current one. The decoder waves share workgroups (6 - 12 each, one workgroup per CU at most) and take their blocks

@@ -75,6 +75,12 @@ extern "C" int64_t td_tiff_lzw_decode(const uint8_t* src, int64_t n, uint8_t* ds
                 *--w = suffix[c];
                 c = prefix[c];
             }
+        } else if (op < cap) {                         // the string that crosses the capacity: the part that fits (as the device decoder)
+            int c = code;
+            for (int64_t at = op + len - 1; at >= op; --at) {
+                if (at < cap) dst[at] = suffix[c];
+                c = prefix[c];
+            }
         }
         op += len;
         old = code;
